@@ -6,6 +6,7 @@ synthetic AbdomenMRI-shaped batches -- BASELINE.json config 2: 256x256x1, batch 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --dump-outputs DIR      # + DIR/{loss,params,grads}.npy of the last timed step
 
 A step = zero_grad + forward + Dice/CE deep-supervision loss + backward + clip_grad_norm_(12) + AdamW
 (reference nnUNetTrainer.py:833-863), inputs resident in HBM before the timed region
@@ -20,6 +21,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -46,6 +48,31 @@ CONFIGS = {
             name="Endovis17-shaped 512x640x3, 8 classes, shipped flash scaling (variant A), fp16 operands / fp32 sums + "
                  "GradScaler (BASELINE.json configs[4])"),
 }
+
+
+DUMP_MAX_ELEMS = 4 << 20     # per dumped vector (16 MB of float32); larger vectors are sampled at fixed, seeded positions
+
+
+def step_outputs(loss, net):
+    """What the timed step leaves its caller: the loss it returned, and the parameters it updated with the gradients it
+    computed (module order, flattened; a parameter without a gradient contributes zeros).  Copied to the host at once,
+    before any later step overwrites them."""
+    params = list(net.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+    n = flat_p.numel()
+    if n > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ELEMS, replace=False))
+        idx = torch.from_numpy(idx).to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    return {"loss": loss.detach().float().reshape(1).cpu().numpy(), "params": flat_p.cpu().numpy(),
+            "grads": flat_g.cpu().numpy()}
+
+
+def write_outputs(out_dir, outputs):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def pmc_traffic(kernel, batch):
@@ -189,6 +216,7 @@ def main_3d(args, cfg, world, rank, dev, dev_index, ddp):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    outputs = step_outputs(loss, net) if args.dump_outputs and rank == 0 else None
     roof = None
     if dominant is not None:
         res = profiling.collect()[dominant]
@@ -219,6 +247,8 @@ def main_3d(args, cfg, world, rank, dev, dev_index, ddp):
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_3d(size, strides, cfg["classes"])
         print(json.dumps(line), flush=True)
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
     if ddp:
         dist.destroy_process_group()
 
@@ -252,7 +282,12 @@ def main():
                          "config 2 the step is GPU-bound either way (61.58 vs 61.63 ms measured A/B on one box) and "
                          "eager launches let the roofline kernel be event-timed inside the timed region itself")
     ap.add_argument("--no-graph", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "loss, updated parameters and their gradients (seeded sample when larger than %d values)" % DUMP_MAX_ELEMS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     cfg = dict(CONFIGS[args.config])
     if args.precision is not None and args.precision != cfg["precision"]:
@@ -377,6 +412,7 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    outputs = step_outputs(loss, net) if args.dump_outputs and rank == 0 else None
 
     # the path nnUNetv2_train drives reads the loss back every step (`l.detach().cpu().numpy()`, reference B:863; the plugin's
     # train_step mirrors it): the same steps once more with that host synchronisation, reported beside the headline
@@ -436,6 +472,8 @@ def main():
         if world == 1 and not args.no_cpu_baseline and args.config == 2:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
     if ddp:
         dist.destroy_process_group()
 

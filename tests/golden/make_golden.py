@@ -1,8 +1,9 @@
 """Generate the golden fixtures in this directory from the REFERENCE's own classes.
 
-Run in the build container only (needs /root/reference; the GPU box never runs this):
+Needs a checkout of the reference repository (aticejiang/MLAgg-UNet), named by MLAGG_REFERENCE; the tests
+only read the fixtures it writes:
 
-    python tests/golden/make_golden.py
+    MLAGG_REFERENCE=<reference checkout> python tests/golden/make_golden.py
 
 The reference's model code (T = nnUNetTrainer_MLAgg_2D_dt_MS.py, M = MambaSkip.py) is
 imported unmodified with stand-ins registered in ``sys.modules`` for the third-party
@@ -27,7 +28,9 @@ import torch.nn as nn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference/mlagg"
+if "MLAGG_REFERENCE" not in os.environ:
+    raise SystemExit("set MLAGG_REFERENCE to a checkout of the reference repository (aticejiang/MLAgg-UNet)")
+REF = os.path.join(os.environ["MLAGG_REFERENCE"], "mlagg")
 sys.dont_write_bytecode = True
 sys.path.insert(0, ROOT)
 sys.path.insert(0, REF)

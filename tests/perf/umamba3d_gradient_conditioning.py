@@ -1,7 +1,9 @@
 """How far the reference arithmetic (fp32, CPU) of the 3-D network is from float64 on the golden case: the spread that bounds what an
 elementwise gradient comparison of any fp32 implementation with the golden can show (LeakyReLU sign flips behind every InstanceNorm:
 a fraction f of flipped elements moves a gradient by ~sqrt(f) in relative L2).  Measured: 1.5e-5 (last norm) ... 8.5e-3."""
-import sys; sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import sys, os
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 from oracle import mlagg_oracle as O, umamba3d_oracle as U
 import test_umamba3d_gpu as T
