@@ -16,7 +16,6 @@ stage (the reference flips NCHW <-> NLC per block and again around every depthwi
 produced once per stage for the MIOpen convolutions that consume the stage output.
 """
 import math
-import os
 from typing import Sequence
 
 import torch
@@ -107,7 +106,7 @@ class DropPath(nn.Module):
 
     def residual_norm(self, skip, branch, norm):
         """(x, norm(x)) with x = skip + drop_path(branch): the junction and the LayerNorm that follows it in one K6 pass."""
-        if branch.is_cuda and ops.FUSED_RESIDUAL_NORM:
+        if branch.is_cuda:
             return ops.residual_layer_norm(skip, branch, self.scale_mask(branch), norm.weight, norm.bias, norm.eps)
         x = self.residual(skip, branch)
         return x, norm(x)
@@ -132,8 +131,7 @@ class _ConvMixin:
       fused(x, res, act, dtype)    act(conv(x) + bias + res) with everything behind the convolution in one K13 pass; in the 16-bit
                                    modes the epilogue reads the 16-bit convolution output and writes ``dtype`` (default fp32: the
                                    map joins the residual stream) -- no cast kernel on either side;
-      forward(x)                   conv(x) + bias as an fp32 map.
-    In fp32 mode the weight gradient of dense 3x3 / 1x1 stride-1 convolutions may go to K15 (ops.K15_2D, off: MIOpen wins)."""
+      forward(x)                   conv(x) + bias as an fp32 map."""
 
     def _lib_conv(self, x, w):
         raise NotImplementedError
@@ -148,7 +146,7 @@ class _ConvMixin:
         cdt = ops.conv_dtype()
         if cdt == torch.float32:
             return self._fp32_conv(x)
-        if ops.LP_K and x.dtype == torch.float32:
+        if x.dtype == torch.float32:
             y = self._lp_conv(x, ops.conv_form())                    # K18 / K19, one rounded product, fp32 map out (round 4)
             if y is not None:
                 return y
@@ -162,7 +160,7 @@ class _ConvMixin:
         y = self.raw(x)
         if y.dtype == torch.float32:
             return ops.channel_epilogue(y, self.bias, res if res is None or res.dtype == torch.float32 else res.float(), act)
-        if y.numel() // (y.shape[0] * y.shape[1]) % 4 or not ops.LP_IO:
+        if y.numel() // (y.shape[0] * y.shape[1]) % 4:
             return ops.channel_epilogue(y.float(), self.bias, None if res is None else res.float(), act)
         return ops.channel_epilogue_lp(y, self.bias, res, act, dtype or torch.float32)
 
@@ -170,7 +168,7 @@ class _ConvMixin:
         y = self.raw(x)
         if y.dtype == torch.float32:
             return y if self.bias is None else ops.channel_bias(y, self.bias)
-        if y.numel() // (y.shape[0] * y.shape[1]) % 4 or not ops.LP_IO:
+        if y.numel() // (y.shape[0] * y.shape[1]) % 4:
             y = y.float()
             return y if self.bias is None else ops.channel_bias(y, self.bias)
         return ops.channel_epilogue_lp(y, self.bias, None, ops.EPI_NONE, torch.float32)
@@ -187,8 +185,6 @@ class Conv2d(_ConvMixin, nn.Conv2d):
             return ops.conv1x1(x, self.weight)                       # K18
         if ops.conv3x3_supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
             return ops.conv3x3(x, self.weight)                       # K19
-        if self.groups == 1 and ops.K15_2D and tuple(self.dilation) == (1, 1):
-            return ops.conv_nd(x, self.weight, self.stride, self.padding)
         return self._lib_conv(x, self.weight)
 
     def _lp_conv(self, x, form):
@@ -222,7 +218,7 @@ class ConvTranspose2d(_ConvMixin, nn.ConvTranspose2d):
         # transposed-convolution solvers are the faster ones
         I, O = self.weight.shape[:2]
         P = int(x.shape[2] * x.shape[3])
-        return (ops.K18_THIN and self._pointwise() and ops.conv1x1_supported(x, self.weight, (1, 1), (0, 0), (1, 1), 1, form)
+        return (self._pointwise() and ops.conv1x1_supported(x, self.weight, (1, 1), (0, 0), (1, 1), 1, form)
                 and ops._k18_product(O, I, P, form) and ops._k18_product(I, O, P, form))
 
     def _t2(self, x, form):
@@ -265,9 +261,9 @@ def _chain_dtype(x):
     the kernels' vector path applies (plane size a multiple of 4), else None (= keep fp32)."""
     cdt = ops.conv_dtype()
     pixels = x.numel() // (x.shape[0] * x.shape[1])
-    if cdt == torch.float32 or not ops.LP_IO or pixels % 4:
+    if cdt == torch.float32 or pixels % 4:
         return None
-    if ops.LP_K and pixels >= ops.LP_K_MIN_PIXELS:       # the map's stride-1 convolutions are K18 / K19 here: they read fp32
+    if pixels >= ops.LP_K_MIN_PIXELS:                    # the map's stride-1 convolutions are K18 / K19 here: they read fp32
         return None
     return cdt
 
@@ -314,36 +310,27 @@ class RMSNormWeight(nn.Module):
         self.weight = nn.Parameter(torch.ones(dim))
 
 
-WEIGHT_STACKS = os.environ.get("MLAGG_WEIGHT_STACKS", "1") == "1"      # 0: torch.cat per use (the round-2 form)
-GLU_FUSED = os.environ.get("MLAGG_GLU_FUSED", "1") == "1"               # 0: the gated MLP's product as a torch multiplication
-DWC_MERGED = os.environ.get("MLAGG_DWC_MERGED", "1") == "1"             # 0: one depthwise conv per channel half of the MLLA block
-
-
 class _StackFn(torch.autograd.Function):
     """The stacked matrix as a function of its sources: forward hands out the (already refreshed) buffer, backward cuts the gradient
-    into the sources' row blocks -- a view where a source is stacked whole, a zero-filled copy where only rows [lo, hi) of it are.
-    The cutting runs on the leaf-gradient stream (ops._LeafStream): what comes out goes straight to the parameters' AccumulateGrad
-    nodes, so the gradient of a stacked projection never has to be waited for inside backward."""
+    into the sources' row blocks -- a view where a source is stacked whole, a zero-filled copy where only rows [lo, hi) of it are."""
 
     @staticmethod
     def forward(ctx, buf, ranges, *params):
-        ctx.ranges, ctx.shapes, ctx.sources = ranges, [tuple(p.shape) for p in params], list(params)
-        ops.note_leaf_use(*params)
+        ctx.ranges, ctx.shapes = ranges, [tuple(p.shape) for p in params]
         return buf.detach()
 
     @staticmethod
     def backward(ctx, g):
         out, off = [None, None], 0
-        with ops._LeafStream(g, ok=ops.leaf_single_use(ctx.sources)):
-            for (lo, hi), shape in zip(ctx.ranges, ctx.shapes):
-                piece = g[off:off + hi - lo]
-                if lo == 0 and hi == shape[0]:
-                    out.append(piece)
-                else:
-                    full = torch.zeros(shape, device=g.device, dtype=g.dtype)
-                    full[lo:hi] = piece
-                    out.append(full)
-                off += hi - lo
+        for (lo, hi), shape in zip(ctx.ranges, ctx.shapes):
+            piece = g[off:off + hi - lo]
+            if lo == 0 and hi == shape[0]:
+                out.append(piece)
+            else:
+                full = torch.zeros(shape, device=g.device, dtype=g.dtype)
+                full[lo:hi] = piece
+                out.append(full)
+            off += hi - lo
         return tuple(out)
 
 
@@ -395,8 +382,6 @@ class _Stack:
 
     def get(self):
         srcs = self._norm(self.sources())
-        if not WEIGHT_STACKS:
-            return torch.cat([t[lo:hi] for t, lo, hi in srcs])
         views = self._views(srcs)
         if self.stale(srcs):
             with torch.no_grad():
@@ -404,15 +389,11 @@ class _Stack:
             self.sig = self.signature(srcs)
         out = _StackFn.apply(self.buf, [(lo, hi) for _, lo, hi in srcs], *[t for t, _, _ in srcs])
         out._mlagg_buffer = self.buf                            # ops.WeightImageSet keeps THIS (no grad_fn), never the graph-bound view
-        out._mlagg_leaf_safe = True                             # its gradient goes to AccumulateGrad nodes only (see _StackFn.backward)
-        out._mlagg_sources = [t for t, _, _ in srcs]            # ... of THESE parameters (ops.leaf_single_use)
         return out
 
 
 def refresh_stacks(stacks):
     """One multi-tensor copy for every stack of a network whose sources changed (called at the start of its forward)."""
-    if not WEIGHT_STACKS:
-        return
     dst, src, done = [], [], []
     for st in stacks:
         srcs = st._norm(st.sources())
@@ -535,22 +516,12 @@ class MLLABlock(nn.Module):
         # act_proj and in_proj in ONE GEMM over stacked weights: (B, N, 2C) = [act | in]
         ai = ops.linear(xn, self._w_stack.get(), self._b_stack.get())
         h = C // 2
-        if not DWC_MERGED:                                     # round-3 form: one depthwise conv per channel half
-            act_pre, xa_in, za_in = ops.split_cols(ai, (C, h, h))
-            wa, wz = self.dwc.weight.split([h, h], dim=0)
-            ba, bz = self.dwc.bias.split([h, h], dim=0)
-            xa = ops.dwconv3x3_nlc(xa_in, wa, ba, H, W, silu=True)
-            za = ops.dwconv3x3_nlc(za_in, wz, bz, H, W, silu=True)
-            return self._after_dwc(x, xa, za, act_pre, next_norm)
         act_pre, xz_in = ops.split_cols(ai, (C, C))
         # ONE depthwise conv over both channel halves (round 4: one launch instead of two in forward and in each of the three backward
         # kernels, and no split of dwc.weight / dwc.bias); the branches read their halves as column blocks of the result -- the
         # projection kernels take a row stride -- and write their input gradients into one buffer (split_cols)
         xz = ops.dwconv3x3_nlc(xz_in, self.dwc.weight, self.dwc.bias, H, W, silu=True)
         xa, za = ops.split_cols(xz, (h, h))
-        return self._after_dwc(x, xa, za, act_pre, next_norm)
-
-    def _after_dwc(self, x, xa, za, act_pre, next_norm):
         gated = ops.gate(self.attn[0](xa), self.attn[1](za), act_pre)       # K7: cat(.) * SiLU(act_proj(.))
         dp = self.drop_path if isinstance(self.drop_path, DropPath) else _NO_DROP
         x, n2 = dp.residual_norm(x, self.out_proj(gated), self.norm2)
@@ -762,15 +733,10 @@ class UnetResBlock(nn.Module):
         # 16-bit modes: every map of the block is written by / read by 16-bit convolutions only (the block output feeds the
         # transposed / 1x1 convolutions of decoder0 and the head): all of them stay 16-bit in memory, K10 converts on the fly
         ct = _chain_dtype(x) if x.is_cuda else None
-        pair = None
-        if hasattr(self, "conv3") and x.is_cuda and x.dtype == torch.float32 and (ops.conv_dtype() == torch.float32 or ops.LP_K):
-            form = ops.conv_form()
-            if ops.conv_pair_supported(x, self.conv1.conv, self.conv3.conv, form):
-                pair = ops.conv_pair(x, self.conv1.conv.weight, self.conv3.conv.weight, form)   # one input gradient from both (K18 adds to K19's)
-        c1 = pair[0] if pair is not None else (self.conv1.conv.raw(x) if x.is_cuda else self.conv1(x))
+        c1 = self.conv1.conv.raw(x) if x.is_cuda else self.conv1(x)
         out = _instance_norm_act(self.norm1, c1, ops.ACT_LEAKY, 0.01, None, ct)
         if hasattr(self, "conv3"):
-            c3 = pair[1] if pair is not None else (self.conv3.conv.raw(x) if x.is_cuda else self.conv3(x))
+            c3 = self.conv3.conv.raw(x) if x.is_cuda else self.conv3(x)
             res = _instance_norm_act(self.norm3, c3, out_dtype=ct)
         else:
             res = x
@@ -910,7 +876,7 @@ class ConvolutionalGLU(nn.Module):  # reference M:559-577
 
     def forward(self, x, H, W):
         xg, vg = ops.split_cols(self.fc1(x), (self.hidden, self.hidden))      # the depthwise convolution's backward writes both halves in place
-        if x.is_cuda and GLU_FUSED:
+        if x.is_cuda:
             # SiLU(dwconv(x)) * v in the convolution's epilogue (round 4: the product and its two backward products were ATen kernels)
             return self.fc2(ops.dwconv3x3_gated(xg, vg, self.dwconv.dwconv.weight, self.dwconv.dwconv.bias, H, W))
         g = ops.dwconv3x3_nlc(xg, self.dwconv.dwconv.weight, self.dwconv.dwconv.bias, H, W, silu=True)

@@ -64,11 +64,6 @@ import os as _os
 LP_CONV = _os.environ.get("MLAGG_LP_CONV", "1") == "1"
 
 
-# 16-bit modes: maps that only 16-bit library convolutions read or write stay bf16 / fp16 in memory; K10 / K13 convert on the fly
-# (MLAGG_LP_IO=0: the round-2 form, fp32 maps everywhere with a cast kernel on both sides of every convolution)
-LP_IO = _os.environ.get("MLAGG_LP_IO", "1") == "1"
-
-
 def conv_dtype():
     return compute_dtype() if LP_CONV else torch.float32
 
@@ -76,8 +71,7 @@ def conv_dtype():
 # 16-bit modes, round 4: the 1 x 1 / 3 x 3 stride-1 convolutions run on K18 / K19 in the ONE-product operand form (csrc/opmode.h: operands
 # rounded once to bf16 / fp16 in registers, fp32 sums) straight on the fp32 maps -- the kernels of the fp32 step at a sixth of its matrix
 # work, no cast kernels, no NHWC transposes.  Maps below LP_K_MIN_PIXELS pixels, strided and transposed convolutions stay 16-bit library
-# calls.  MLAGG_LP_K=0: every convolution of the 16-bit modes on the library (the round-3 form).
-LP_K = _os.environ.get("MLAGG_LP_K", "1") == "1"
+# calls.
 LP_K_MIN_PIXELS = int(_os.environ.get("MLAGG_LP_K_MIN_PIXELS", "1024"))
 _DTYPE_BF16X3 = 3
 _FORM_TORCH = {1: torch.bfloat16, 2: torch.float16, 3: torch.float32}
@@ -107,129 +101,6 @@ def _lib_conv_bwd(dy, x, w, padding, mask, form):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
-
-
-# ------------------------------------------------------------------------------------------------
-# Leaf gradients on a second stream.  Nothing in backward consumes a weight / bias gradient: only the optimizer (and the data-parallel
-# exchange) read them, after the last backward kernel.  Inside ``with leaf_grad_overlap():`` (trainer.train_step wraps backward in
-# it) the weight-gradient launches of the projection and convolution Functions go to a side stream that forks off the data-gradient
-# chain where their operands are ready; the context's exit joins it back.  The data-gradient chain -- the critical path of backward --
-# gets shorter by the weight-gradient kernels and their reductions, which fill the gaps the small-grid kernels of the chain leave
-# on the 256 CUs.  Operands handed to the side stream stay referenced until the join (see _LeafStream).  Captured into a hipGraph
-# the fork / join become graph edges.
-# Outside the context (a bare ``loss.backward()``) everything stays on the current stream.
-# ------------------------------------------------------------------------------------------------
-# Measured (profiles/round4_e_leaf_stream_ab.log): 37.9 -> 37.7 ms per eager step (0.6 %), but 38.4 -> 39.8 ms under hipGraph replay (the
-# fork / join edges cost more than the overlap returns: the backward chain's kernels already fill the chip).  OFF by default.
-LEAF_STREAM = _os.environ.get("MLAGG_LEAF_STREAM", "0") == "1"
-_LEAF = {"on": False, "side": None, "main": None, "used": False, "epoch": 0, "keep": []}
-
-
-def leaf_grads_ready():
-    """Make the CURRENT stream wait for every leaf gradient enqueued so far (the data-parallel exchange calls it before it gathers a
-    bucket in the middle of backward)."""
-    if _LEAF["on"] and _LEAF["used"]:
-        torch.cuda.current_stream().wait_stream(_LEAF["side"])
-
-
-class leaf_grad_overlap:
-    def __init__(self, enabled=True):
-        self.enabled = enabled
-
-    def __enter__(self):
-        if self.enabled and LEAF_STREAM and torch.cuda.is_available():
-            _LEAF["main"] = torch.cuda.current_stream()
-            if _LEAF["side"] is None or _LEAF["side"].device != _LEAF["main"].device:
-                _LEAF["side"] = torch.cuda.Stream(device=_LEAF["main"].device)
-            _LEAF["on"], _LEAF["used"] = True, False
-        return self
-
-    def __exit__(self, *exc):
-        _LEAF["epoch"] += 1                                      # the uses counted by note_leaf_use belong to the forward just consumed
-        if _LEAF["on"]:
-            _LEAF["on"] = False
-            if _LEAF["used"]:
-                _LEAF["main"].wait_stream(_LEAF["side"])         # every leaf gradient is complete before anything reads it
-            _LEAF["keep"].clear()                                # (freed behind the join: reuse on the main stream is ordered after it)
-        return False
-
-
-_LEAF_USES = {}
-
-
-def _leaf_base(t):
-    return t._base if t._is_view() and t._base is not None else t
-
-
-def note_leaf_use(*tensors):
-    """Forward-time bookkeeping: how many projections of THIS forward a parameter feeds (see leaf_single_use)."""
-    for t in tensors:
-        if t is None:
-            continue
-        p = _leaf_base(t)
-        if not (p.is_leaf and p.requires_grad):
-            continue
-        u = _LEAF_USES.get(id(p))
-        if u is None or u[0] != _LEAF["epoch"]:
-            _LEAF_USES[id(p)] = [_LEAF["epoch"], 1, p]         # (p itself is kept: an id must not be recycled)
-        else:
-            u[1] += 1
-
-
-def leaf_single_use(tensors):
-    """True when every parameter behind ``tensors`` received ONE use in the forward being differentiated.  A parameter that feeds two
-    projections (kv.weight of the pooled branch: a row slice inside the stacked q | v | sr projection and the whole matrix on the
-    pooled tokens) gets two gradient contributions, and AccumulateGrad adds the second in place on the backward stream: both must
-    then be produced on that stream, so such projections keep their weight gradients off the leaf-gradient stream."""
-    for t in tensors:
-        if t is None:
-            continue
-        u = _LEAF_USES.get(id(_leaf_base(t)))
-        if u is not None and u[0] == _LEAF["epoch"] and u[1] > 1:
-            return False
-    return True
-
-
-def _leaf_sources(*tensors):
-    out = []
-    for t in tensors:
-        if t is not None:
-            out += getattr(t, "_mlagg_sources", [t])
-    return out
-
-
-def _leaf_ok(*tensors):
-    """True when the gradients of these forward arguments go NOWHERE but to AccumulateGrad nodes: parameters themselves, or tensors
-    whose producer promises it (weight stacks, the padded x_proj: ``_mlagg_leaf_safe``).  A gradient that another backward node reads
-    (a sliced or cast weight) must be produced on the backward stream."""
-    return all(t is None or t.is_leaf or getattr(t, "_mlagg_leaf_safe", False) for t in tensors)
-
-
-class _LeafStream:
-    """with _LeafStream(dy, x, ...): launches inside go to the side stream (when the overlap is on), behind everything enqueued so far."""
-
-    def __init__(self, *operands, ok=True):
-        self.operands, self.prev, self.ok = operands, None, ok
-
-    def __enter__(self):
-        if _LEAF["on"] and self.ok:
-            cur = torch.cuda.current_stream()
-            side = _LEAF["side"]
-            if cur.device == side.device:
-                side.wait_stream(cur)
-                # the operands stay REFERENCED until the join: (i) their memory cannot be handed out again while the side stream
-                # reads it, and (ii) autograd cannot add another gradient contribution INTO them in place on the backward stream (it
-                # does that to a gradient nobody else holds: the dy of out_proj is also the gradient of the residual skip)
-                _LEAF["keep"].extend(t for t in self.operands if t is not None)
-                self.prev = cur
-                torch.cuda.set_stream(side)
-                _LEAF["used"] = True
-        return self
-
-    def __exit__(self, *exc):
-        if self.prev is not None:
-            torch.cuda.set_stream(self.prev)
-        return False
 
 
 # flop of the matrix products this package's own kernels run, per family (bench.py's roofline.mfma): None = not counting
@@ -362,9 +233,8 @@ def selective_scan_lowrank_fn(u, dtr, Wdt, A, B, C, D=None, delta_bias=None, del
 
 # ------------------------------------------------------------------------------------------------
 # K1f: the MSMM scan on token-major tensors (csrc/selscan_tok.hip) -- SS2D_skip.forward_corev0 behind x_proj + the four-way sum
-# (reference MambaSkip.py:405-473, 534) as ONE op; MLAGG_MSMM_FUSED=0: the round-3 chain (K1' cross_scan / cross_merge around K1)
+# (reference MambaSkip.py:405-473, 534) as ONE op; shapes outside it take the round-3 chain (K1' cross_scan / cross_merge around K1)
 # ------------------------------------------------------------------------------------------------
-MSMM_FUSED = _os.environ.get("MLAGG_MSMM_FUSED", "1") == "1"
 MSMM_XB = 36                      # floats per direction of a padded x_proj row: [dt0 dt1 dt2 0 | B(16) | C(16)]
 _SCAN_INDEX = {}
 
@@ -397,8 +267,6 @@ class PadXProjFn(torch.autograd.Function):
     def forward(ctx, w):
         K, per, dI = w.shape
         ctx.per = per
-        ctx.leaf, ctx.leaf_params = w.is_leaf, [w]
-        note_leaf_use(w)
         out = w.new_zeros(K, MSMM_XB, dI)
         out[:, :3] = w[:, :3]
         out[:, 4:] = w[:, 3:]
@@ -406,17 +274,12 @@ class PadXProjFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        with _LeafStream(g, ok=ctx.leaf and leaf_single_use(ctx.leaf_params)):   # the projection's weight gradient may live on the leaf-gradient stream
-            g3 = g.view(-1, MSMM_XB, g.shape[-1])
-            return torch.cat([g3[:, :3], g3[:, 4:]], dim=1)
+        g3 = g.view(-1, MSMM_XB, g.shape[-1])
+        return torch.cat([g3[:, :3], g3[:, 4:]], dim=1)
 
 
 def pad_x_proj(w):
-    out = PadXProjFn.apply(w)
-    if w.is_leaf:
-        out._mlagg_leaf_safe = True                    # its gradient reaches x_proj_weight's AccumulateGrad through PadXProjFn only
-        out._mlagg_sources = [w]
-    return out
+    return PadXProjFn.apply(w)
 
 
 class MsmmScanFn(torch.autograd.Function):
@@ -467,7 +330,7 @@ def msmm_scan(xc, xdbl, idx, Wdt, A, D=None, delta_bias=None):
 
 
 def msmm_scan_supported(xc, d_state, dt_rank):
-    return bool(MSMM_FUSED and xc.is_cuda and xc.dim() == 3 and
+    return bool(xc.is_cuda and xc.dim() == 3 and
                 _lib.lib().mlagg_msmm_scan_supported(int(xc.shape[2]), int(d_state), int(dt_rank), 4, int(xc.shape[1])))
 
 
@@ -571,16 +434,12 @@ class SplitPlanesFn(torch.autograd.Function):
         return (buf, None) + (None,) * len(sizes)
 
 
-GRAD_ARENA = _os.environ.get("MLAGG_GRAD_ARENA", "1") == "1"
-PLANE_ARENA = _os.environ.get("MLAGG_PLANE_ARENA", "1") == "1"
-
-
 def split_planes(t, sizes):
     """``t.split(sizes, dim=1)`` of an NCHW map whose pieces feed this package's kernels (the (mamba | conv) halves of the MSMM inputs,
     MambaSkip.py:727-733): the same views, and the kernels' backward passes -- the token transpose, K19's data gradient -- write their
     results into ONE (B, C, H, W) gradient buffer, which the split's backward hands on instead of concatenating the pieces
     (``CatArrayBatchedCopy`` behind SplitWithSizesBackward: 163 us of the step).  A piece whose consumer cannot is copied into place."""
-    if not (PLANE_ARENA and GRAD_ARENA and t.is_cuda and t.requires_grad and torch.is_grad_enabled() and t.dim() == 4 and t.is_contiguous()
+    if not (t.is_cuda and t.requires_grad and torch.is_grad_enabled() and t.dim() == 4 and t.is_contiguous()
             and t.dtype == torch.float32 and (t.shape[2] * t.shape[3]) % 4 == 0):
         return t.split(list(sizes), dim=1)
     arena = _GradArena(t.shape, t.device)
@@ -603,13 +462,11 @@ def transpose_2d_into(src, dst):
                "mlagg_transpose_2d_into")
     return dst
 
-FUSED_RESIDUAL_NORM = _os.environ.get("MLAGG_FUSED_RESIDUAL_NORM", "1") == "1"
-
 
 def split_cols(t, sizes):
     """``t.split(sizes, dim=-1)`` of a fresh (B, N, total) projection output whose pieces feed this package's kernels: the pieces are
     the same strided views, and the kernels' backward passes write into ONE gradient buffer (see _GradSlot)."""
-    if not (GRAD_ARENA and t.is_cuda and t.requires_grad and torch.is_grad_enabled() and t.dim() == 3 and t.is_contiguous()
+    if not (t.is_cuda and t.requires_grad and torch.is_grad_enabled() and t.dim() == 3 and t.is_contiguous()
             and all(w % 4 == 0 for w in sizes)):
         return t.split(list(sizes), dim=-1)
     arena = _GradArena(t.shape, t.device)
@@ -984,12 +841,9 @@ def local_diff_attn(q, kv, lam, subln_w, lepe_w, lepe_b, H, W, nh, scale):
     return LocalDiffAttnFn.apply(q, kv, lam, subln_w, lepe_w, lepe_b, H, W, nh, scale, _claim(q), _claim(kv))
 
 
-K4_LP = _os.environ.get("MLAGG_K4_LP", "1") == "1"
-
-
 def pooled_diff_attn(q, k_pool, v_pool, lam, subln_w, nh, scale):
     cdt = compute_dtype()
-    if cdt != torch.float32 and K4_LP and k_pool.shape[1] <= 320:
+    if cdt != torch.float32 and k_pool.shape[1] <= 320:
         return PooledDiffAttnLpFn.apply(q, k_pool, v_pool, lam, subln_w, nh, scale, cdt, _claim(q))
     return PooledDiffAttnFn.apply(q, k_pool, v_pool, lam, subln_w, nh, scale, _claim(q))
 
@@ -1035,9 +889,8 @@ def _mfma_rows(t, name):
 # ------------------------------------------------------------------------------------------------
 # K5, round-4 form (csrc/linear_x3.hip): the weight operand is an IMAGE (its three bf16 pieces, laid out for the kernel; the same for
 # W^T for the data gradient), built once per step for every projection of a network in ONE launch (WeightImageSet) or, for a weight
-# nobody registered, on the fly.  MLAGG_K5_V2=0: the round-3 kernels + the library GEMM for short token counts.
+# nobody registered, on the fly.
 # ------------------------------------------------------------------------------------------------
-K5_V2 = _os.environ.get("MLAGG_K5_V2", "1") == "1"
 # end of round 4: stages 2 / 3 (10 240 / 2 560 tokens) too -- against the TUNED library GEMMs the kernel wins 11 of 16 products there
 # (tools/bench_linear_x3.py with BENCH_TUNED_GEMM=1) and the step 0.1-0.3 ms on two boxes (profiles/round4_m_x3_min_rows_ab.log); mid-round,
 # before the fused Mlp epilogues and the per-network image set, the same switch had lost 0.2 ms
@@ -1145,7 +998,7 @@ def weight_images(w):
 
 
 def _x3_ok(M, N, K):
-    return K5_V2 and M >= X3_MIN_ROWS and bool(_lib.lib().mlagg_linear_x3_supported(M, N, K))
+    return M >= X3_MIN_ROWS and bool(_lib.lib().mlagg_linear_x3_supported(M, N, K))
 
 
 def _x3(x2, xs, img, bias, M, N, K, epilogue=0, pre=None, pre_stride=0, out_shape=None, out=None, out_stride=None):
@@ -1182,7 +1035,7 @@ def _linear_wgrad(dy2, dys, x, O, I, has_bias):
 
 class LinearFn(torch.autograd.Function):
     """y = x W^T + b for token-major activations: forward and dx on K5 (round-4 form on weight images at every token count from
-    X3_MIN_ROWS up; MLAGG_K5_V2=0 / 16-bit modes: the round-3 kernels for long token counts, the library GEMM below), dW / db on K5w."""
+    X3_MIN_ROWS up; 16-bit modes: the round-3 kernels for long token counts, the library GEMM below), dW / db on K5w."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, slot=None):
@@ -1191,9 +1044,6 @@ class LinearFn(torch.autograd.Function):
         ctx.has_bias = bias is not None
         ctx.cdt = cdt = compute_dtype()
         ctx.imgT = None
-        ctx.leaf = _leaf_ok(weight, bias)
-        ctx.leaf_params = _leaf_sources(weight, bias)
-        note_leaf_use(weight, bias)
         O, I = weight.shape
         M = x.numel() // I
         if cdt == torch.float32 and x.is_cuda and _x3_ok(M, O, I):
@@ -1260,8 +1110,7 @@ class LinearFn(torch.autograd.Function):
                 dx = dy.matmul(weight)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             # weight / bias gradients stay fp32 in every mode (K5w: the token sum is the long one)
-            with _LeafStream(dy2, x, ok=ctx.leaf and leaf_single_use(ctx.leaf_params)):
-                dW, db = _linear_wgrad(dy2, dys, x, O, I, ctx.has_bias)
+            dW, db = _linear_wgrad(dy2, dys, x, O, I, ctx.has_bias)
         return dx, dW, db, None
 
 
@@ -1292,9 +1141,6 @@ class MlpFn(torch.autograd.Function):
         pre, act = _x3(x2, xs, img1, b1, M, H, I, epilogue=1)
         y = _x3(act, H, img2, b2, M, O, H, out_shape=x.shape[:-1] + (O,))
         ctx.save_for_backward(x, w1, w2, pre, act)
-        ctx.leaf = _leaf_ok(w1, b1, w2, b2)
-        ctx.leaf_params = _leaf_sources(w1, b1, w2, b2)
-        note_leaf_use(w1, b1, w2, b2)
         ctx.images = (img1T, img2T)
         ctx.bias = (b1 is not None, b2 is not None)
         return y
@@ -1307,12 +1153,9 @@ class MlpFn(torch.autograd.Function):
         O = w2.shape[0]
         dy2, dys = _mfma_rows(dy, "dy")
         M = dy2.shape[0]
-        ok = ctx.leaf and leaf_single_use(ctx.leaf_params)
-        with _LeafStream(dy2, act, ok=ok):
-            dW2, db2 = _linear_wgrad(dy2, dys, act, O, H, ctx.bias[1])
+        dW2, db2 = _linear_wgrad(dy2, dys, act, O, H, ctx.bias[1])
         dpre = _x3(dy2, dys, img2T, None, M, H, O, epilogue=2, pre=pre, pre_stride=H)          # (dy . W2) * GELU'(pre)
-        with _LeafStream(dpre, x, ok=ok):
-            dW1, db1 = _linear_wgrad(dpre, H, x, H, I, ctx.bias[0])
+        dW1, db1 = _linear_wgrad(dpre, H, x, H, I, ctx.bias[0])
         dx = _x3(dpre, H, img1T, None, M, I, H, out_shape=x.shape) if ctx.needs_input_grad[0] else None
         return dx, dW1, db1, dW2, db2
 
@@ -2084,13 +1927,10 @@ def _require_map(t, name, shape=None):
     return t
 
 
-SLICE_GRADS = _os.environ.get("MLAGG_SLICE_GRADS", "1") == "1"     # 0: copy channel-slice gradients before the kernels (the round-3 form)
-
-
 def _map_slice(t, name):
     """A gradient map as the K10 / shuffle kernels can read it without a copy: (tensor, elements between samples) -- dense, or a channel
     slice of a wider dense map (what ``torch.cat([a, b], 1)``'s backward hands to the producers of a and b); anything else is copied."""
-    if SLICE_GRADS and t.is_cuda and t.dim() >= 3 and not t.is_contiguous():
+    if t.is_cuda and t.dim() >= 3 and not t.is_contiguous():
         inner, want = 1, []
         for v in reversed(t.shape[1:]):
             want.append(inner)
@@ -2229,7 +2069,6 @@ K18_FWD_MIN_K = int(_os.environ.get("MLAGG_K18_FWD_MIN_K", "96"))
 K18_WGRAD_MIN_PIXELS = int(_os.environ.get("MLAGG_K18_WGRAD_MIN_PIXELS", "4096"))
 
 
-K18_THIN = _os.environ.get("MLAGG_K18_THIN", "1") == "1"
 K18_THIN_CH = 32
 
 
@@ -2240,8 +2079,8 @@ def _k18_product(O, I, P, form=_DTYPE_BF16X3):
     if not bool(_lib.lib().mlagg_conv1x1_supported(O, I16, P)):
         return False
     if form != _DTYPE_BF16X3:                # one product per block: a stream of the maps, ahead of cast + library + cast wherever it runs
-        return P >= LP_K_MIN_PIXELS and (I == I16 or K18_THIN)
-    if K18_THIN and P >= K18_FWD_MIN_PIXELS and min(O, I) <= K18_THIN_CH:
+        return P >= LP_K_MIN_PIXELS
+    if P >= K18_FWD_MIN_PIXELS and min(O, I) <= K18_THIN_CH:
         # a thin side (the 14-class heads and their data gradients): one pass over the wide map, where the library's GEMM kernels
         # took 101 us forward / 261 us backward for 48 -> 14 channels at 256 x 256 (profiles/round4_i_library_convolutions_by_shape.md)
         return True
@@ -2278,8 +2117,6 @@ class Conv1x1Fn(torch.autograd.Function):
             y = _lib_conv_fwd(x, weight, 0, form)
         ctx.save_for_backward(x, w)
         ctx.wshape, ctx.form = weight.shape, form
-        ctx.leaf, ctx.leaf_params = _leaf_ok(weight), [weight]
-        note_leaf_use(weight)
         return y
 
     @staticmethod
@@ -2300,17 +2137,13 @@ class Conv1x1Fn(torch.autograd.Function):
             else:
                 dx = _lib_conv_bwd(dy, x, w.view(ctx.wshape), 0, (True, False, False), form)[0]
         if ctx.needs_input_grad[1]:
-            with _LeafStream(dy, x, ok=ctx.leaf and leaf_single_use(ctx.leaf_params)):
-                dW = torch.empty(O, I, device=x.device, dtype=torch.float32)
-                ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, O, I, P), device=x.device, dtype=torch.float32)
-                _flop("K18", 2 * B * O * I * P)
-                _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, P, form,
-                                                      _stream()), "mlagg_conv1x1_wgrad_lp")
+            dW = torch.empty(O, I, device=x.device, dtype=torch.float32)
+            ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, O, I, P), device=x.device, dtype=torch.float32)
+            _flop("K18", 2 * B * O * I * P)
+            _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, P, form,
+                                                  _stream()), "mlagg_conv1x1_wgrad_lp")
             dW = dW.view(ctx.wshape)
         return dx, dW, None
-
-
-CONVT2 = _os.environ.get("MLAGG_CONVT2", "1") == "1"
 
 
 def _pixel_shuffle2(src, B, O, H, W, inverse):
@@ -2338,8 +2171,6 @@ class ConvT2x2Fn(torch.autograd.Function):
         _conv1x1_k18(x, xb, w4, z, B, 4 * O, I, P, form)
         ctx.save_for_backward(x, w4)
         ctx.form, ctx.O = form, O
-        ctx.leaf, ctx.leaf_params = _leaf_ok(weight), [weight]
-        note_leaf_use(weight)
         return _pixel_shuffle2(z, B, O, H, W, False)
 
     @staticmethod
@@ -2360,19 +2191,18 @@ class ConvT2x2Fn(torch.autograd.Function):
             _flop("K18", 2 * B * 4 * O * I * P)
             _conv1x1_k18(dyu, 4 * O * P, wt, dx, B, I, 4 * O, P, form)
         if ctx.needs_input_grad[1]:
-            with _LeafStream(dyu, x, ok=ctx.leaf and leaf_single_use(ctx.leaf_params)):
-                dW4 = torch.empty(4 * O, I, device=x.device, dtype=torch.float32)
-                ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, 4 * O, I, P), device=x.device, dtype=torch.float32)
-                _flop("K18", 2 * B * 4 * O * I * P)
-                _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(dyu), 4 * O * P, _ptr(x), x.stride(0), _ptr(dW4), _ptr(ws), B, 4 * O, I, P, form,
-                                                      _stream()), "mlagg_conv1x1_wgrad_lp")
-                dW = dW4.view(2, 2, O, I).permute(3, 2, 0, 1).contiguous()
+            dW4 = torch.empty(4 * O, I, device=x.device, dtype=torch.float32)
+            ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, 4 * O, I, P), device=x.device, dtype=torch.float32)
+            _flop("K18", 2 * B * 4 * O * I * P)
+            _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(dyu), 4 * O * P, _ptr(x), x.stride(0), _ptr(dW4), _ptr(ws), B, 4 * O, I, P, form,
+                                                  _stream()), "mlagg_conv1x1_wgrad_lp")
+            dW = dW4.view(2, 2, O, I).permute(3, 2, 0, 1).contiguous()
         return dx, dW, None
 
 
 def conv_t2x2_supported(x, weight, stride, padding, output_padding, dilation, groups, form=_DTYPE_BF16X3):
     """A kernel-2 / stride-2 transposed convolution (no padding) on an fp32 device map whose three products K18 takes."""
-    if not (CONVT2 and K18 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and groups == 1):
+    if not (K18 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and groups == 1):
         return False
     if tuple(weight.shape[2:]) != (2, 2) or any(int(v) != 2 for v in stride) or any(int(v) != 0 for v in padding) or \
             any(int(v) != 0 for v in output_padding) or any(int(v) != 1 for v in dilation):
@@ -2458,8 +2288,6 @@ class Conv3x3Fn(torch.autograd.Function):
             y = _lib_conv_fwd(x, w, 1, form)
         ctx.save_for_backward(x, w)
         ctx.form = form
-        ctx.leaf, ctx.leaf_params = _leaf_ok(weight), [weight]
-        note_leaf_use(weight)
         return y
 
     @staticmethod
@@ -2480,16 +2308,14 @@ class Conv3x3Fn(torch.autograd.Function):
             lib = _lib.lib()
             if _k19_wgrad(O, I, H, W, form):
                 dy, dyb, _ = _planes(dy, "dy")
-                with _LeafStream(dy, x, ok=ctx.leaf and leaf_single_use(ctx.leaf_params)):
-                    dW = torch.empty(O, I, 3, 3, device=x.device, dtype=torch.float32)
-                    ws = torch.empty(lib.mlagg_conv3x3_wgrad_workspace_floats(B, O, I, H, W), device=x.device, dtype=torch.float32)
-                    _flop("K19", 2 * 9 * B * O * I * H * W)
-                    _lib.check(lib.mlagg_conv3x3_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, H, W, form,
-                                                          _stream()), "mlagg_conv3x3_wgrad_lp")
+                dW = torch.empty(O, I, 3, 3, device=x.device, dtype=torch.float32)
+                ws = torch.empty(lib.mlagg_conv3x3_wgrad_workspace_floats(B, O, I, H, W), device=x.device, dtype=torch.float32)
+                _flop("K19", 2 * 9 * B * O * I * H * W)
+                _lib.check(lib.mlagg_conv3x3_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, H, W, form,
+                                                      _stream()), "mlagg_conv3x3_wgrad_lp")
             else:
                 dyc = dy.contiguous()
-                with _LeafStream(dyc, x, w, ok=ctx.leaf and leaf_single_use(ctx.leaf_params)):
-                    dW = _lib_conv_bwd(dyc, x, w, 1, (False, True, False), form)[1]
+                dW = _lib_conv_bwd(dyc, x, w, 1, (False, True, False), form)[1]
         return dx, dW, None, None
 
 
@@ -2566,97 +2392,6 @@ class Conv3x3x3Fn(torch.autograd.Function):
         return dx, dW
 
 
-# measured and NOT adopted (off): on every two-branch block 35.18 vs 35.10 ms, only where K18 runs the 1 x 1 data gradient anyway 35.14 vs 35.11
-# (profiles/round4_m_conv_pair_ab.log) -- the accumulate's extra read of the map costs what the add_ kernel cost
-CONV_PAIR = _os.environ.get("MLAGG_CONV_PAIR", "0") == "1"
-CONV_PAIR_ALWAYS = _os.environ.get("MLAGG_CONV_PAIR_ALWAYS", "0") == "1"
-
-
-class ConvPairFn(torch.autograd.Function):
-    """(conv3x3(x, W3, padding 1), conv1x1(x, W1)) of ONE input map: conv1 and conv3 of a UnetResBlock whose channel count changes (MONAI
-    structure behind T:1340-1368, M:581-667).  Forward products as in Conv3x3Fn / Conv1x1Fn; backward: K19 writes the 3 x 3 data gradient
-    and K18 ADDS the 1 x 1 data gradient to it (mlagg_conv1x1_fwd_acc) -- autograd's add_ over the (B, I, H, W) map (114 us at 256 x 256)
-    is gone, which pays for K18 on contractions it otherwise leaves to the library."""
-
-    @staticmethod
-    def forward(ctx, x, w3, w1, form=_DTYPE_BF16X3):
-        x, xb, P = _planes(x, "x")
-        B, I, H, W = x.shape
-        O3, O1 = w3.shape[0], w1.shape[0]
-        w3c = _require(w3.contiguous(), "w3")
-        w1c = _require(w1.reshape(O1, I).contiguous(), "w1")
-        c3 = _conv3x3_k19(x, xb, w3c, False, O3, I, H, W, form) if _k19_product(O3, I, H, W, form) else _lib_conv_fwd(x, w3c, 1, form)
-        if _k18_product(O1, I, P, form):
-            c1 = torch.empty(B, O1, H, W, device=x.device, dtype=torch.float32)
-            _flop("K18", 2 * B * O1 * I * P)
-            _conv1x1_k18(x, xb, w1c, c1, B, O1, I, P, form)
-        else:
-            c1 = _lib_conv_fwd(x, w1, 0, form)
-        ctx.save_for_backward(x, w3c, w1c)
-        ctx.form, ctx.w1shape = form, w1.shape
-        ctx.leaf, ctx.leaf_params = _leaf_ok(w3, w1), [w3, w1]
-        note_leaf_use(w3, w1)
-        return c3, c1
-
-    @staticmethod
-    def backward(ctx, d3, d1):
-        x, w3, w1 = ctx.saved_tensors
-        B, I, H, W = x.shape
-        O3, O1, P, form = w3.shape[0], w1.shape[0], H * W, ctx.form
-        lib = _lib.lib()
-        d3, d3b, _ = _planes(d3, "d3")
-        d1, d1b, _ = _planes(d1, "d1")
-        dx = dW3 = dW1 = None
-        if ctx.needs_input_grad[0]:
-            dx = _conv3x3_k19(d3, d3b, w3, True, I, O3, H, W, form) if _k19_product(I, O3, H, W, form) else \
-                _lib_conv_bwd(d3, x, w3, 1, (True, False, False), form)[0].contiguous()
-            if bool(lib.mlagg_conv1x1_supported(I, -(-O1 // 16) * 16, P)):
-                wt = transpose_2d(w1.unsqueeze(0))[0]                                  # (I, O1)
-                _flop("K18", 2 * B * O1 * I * P)
-                _conv1x1_k18(d1, d1b, wt, dx, B, I, O1, P, form, accumulate=True)
-            else:
-                dx += _lib_conv_bwd(d1, x, w1.view(ctx.w1shape), 0, (True, False, False), form)[0]
-        ok = ctx.leaf and leaf_single_use(ctx.leaf_params)
-        if ctx.needs_input_grad[1]:
-            if _k19_wgrad(O3, I, H, W, form):
-                with _LeafStream(d3, x, ok=ok):
-                    dW3 = torch.empty(O3, I, 3, 3, device=x.device, dtype=torch.float32)
-                    ws = torch.empty(lib.mlagg_conv3x3_wgrad_workspace_floats(B, O3, I, H, W), device=x.device, dtype=torch.float32)
-                    _flop("K19", 2 * 9 * B * O3 * I * P)
-                    _lib.check(lib.mlagg_conv3x3_wgrad_lp(_ptr(d3), d3b, _ptr(x), x.stride(0), _ptr(dW3), _ptr(ws), B, O3, I, H, W, form,
-                                                          _stream()), "mlagg_conv3x3_wgrad_lp")
-            else:
-                dW3 = _lib_conv_bwd(d3.contiguous(), x, w3, 1, (False, True, False), form)[1]
-        if ctx.needs_input_grad[2]:
-            with _LeafStream(d1, x, ok=ok):
-                dW1 = torch.empty(O1, I, device=x.device, dtype=torch.float32)
-                ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, O1, I, P), device=x.device, dtype=torch.float32)
-                _flop("K18", 2 * B * O1 * I * P)
-                _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(d1), d1b, _ptr(x), x.stride(0), _ptr(dW1), _ptr(ws), B, O1, I, P, form, _stream()),
-                           "mlagg_conv1x1_wgrad_lp")
-            dW1 = dW1.view(ctx.w1shape)
-        return dx, dW3, dW1, None
-
-
-def conv_pair_supported(x, conv3, conv1, form=_DTYPE_BF16X3):
-    """Both convolutions of the pair are bias-free stride-1 layers K19 / K18 take (at least their weight gradients) on this map, and the
-    input wants a gradient (else there is no sum to fuse)."""
-    if not (CONV_PAIR and x.is_cuda and x.requires_grad and torch.is_grad_enabled()):
-        return False
-    if not (conv3.bias is None and conv1.bias is None
-            and conv3x3_supported(x, conv3.weight, conv3.stride, conv3.padding, conv3.dilation, conv3.groups, form)
-            and conv1x1_supported(x, conv1.weight, conv1.stride, conv1.padding, conv1.dilation, conv1.groups, form)):
-        return False
-    # only where K18 runs the 1 x 1 data gradient anyway: forcing it onto a 48-deep contraction (96 -> 48 at 256 x 256: 110 vs the
-    # library's 88 us) cost more than the saved add_ (35.18 vs 35.10 ms, profiles/round4_m_conv_pair_ab.log)
-    O1, I = int(conv1.weight.shape[0]), int(conv1.weight.shape[1])
-    return CONV_PAIR_ALWAYS or _k18_product(I, O1, int(x.shape[2] * x.shape[3]), form)
-
-
-def conv_pair(x, w3, w1, form=_DTYPE_BF16X3):
-    return ConvPairFn.apply(x, w3, w1, form)
-
-
 def conv3x3x3_supported(x, weight, stride, padding):
     if not (K19_3D and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3)):
         return False
@@ -2673,11 +2408,10 @@ def _pad_geometry(D, H, W, stride, wide=False):
     return Dq.value, Hq.value, Wq.value, guard.value
 
 
-# K15 for the 2-D network's dense convolutions: OFF.  Measured on the 21 convolution shapes of the 256 x 256 step
-# (profiles/round3_conv_wgrad_2d_shapes_k15_vs_miopen.log): MIOpen's weight-gradient solvers are 1.1-1.9x faster on the 3x3 shapes
-# (K15 incl. its two pad copies reaches 28-59 TFLOP/s there) and 4-7x on the 1x1 shapes (plain GEMMs); step 43.5 -> 56.2 ms with it
-# on.  It pays where MIOpen has no tuned solver: the 3-D convolutions (8.2 s -> 66 ms per step at 2 x 96x160x160 voxels).
-K15_2D = _os.environ.get("MLAGG_K15_2D", "0") == "1"
+# The models run K15 on the weight gradients of 3-D convolutions only, where MIOpen has no tuned solver (8.2 s -> 66 ms per step at
+# 2 x 96x160x160 voxels).  Not on the 2-D network's dense convolutions: measured on the 21 convolution shapes of the 256 x 256 step
+# (profiles/round3_conv_wgrad_2d_shapes_k15_vs_miopen.log), MIOpen's weight-gradient solvers are 1.1-1.9x faster on the 3x3 shapes
+# (K15 incl. its two pad copies reaches 28-59 TFLOP/s there) and 4-7x on the 1x1 shapes (plain GEMMs); step 43.5 -> 56.2 ms with it.
 # K16 (forward / data gradient of the 3-D stride-1 convolutions on the tap-GEMM kernel) -- MLAGG_K16=0: MIOpen
 K16 = _os.environ.get("MLAGG_K16", "1") == "1"
 

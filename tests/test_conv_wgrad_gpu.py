@@ -272,28 +272,20 @@ def test_split_planes_hands_on_one_gradient_buffer(monkeypatch, H, W):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,I,O,H,W", [(2, 96, 48, 32, 32), (1, 192, 96, 16, 16), (2, 48, 40, 8, 16)])
-def test_convolution_pair_sums_the_input_gradient_in_the_kernel(monkeypatch, B, I, O, H, W):
-    """ops.conv_pair = (conv3x3(x, W3), conv1x1(x, W1)) of one map (UnetResBlock conv1 / conv3, M:581-667): outputs and weight gradients
-    equal the separate Functions bit for bit; the input gradient -- K18 adding its product to K19's -- equals float64's sum."""
-    from mlagg_unet_amd import ops
-    for name, v in (("K19_MIN_PIXELS", 0), ("K18_FWD_MIN_PIXELS", 0), ("K18_FWD_MIN_K", 16), ("K18_WGRAD_MIN_PIXELS", 0), ("K19_WGRAD_MIN_PIXELS", 0)):
-        monkeypatch.setattr(ops, name, v)
+def test_conv1x1_accumulates_into_its_output(B, I, O, H, W):
+    """K18 ADDING its product to what the output already holds (mlagg_conv1x1_fwd_acc, accumulate on): y0 + conv2d(x, W) from O to
+    I channels -- contractions of 48 and 96, and a ragged 40 on zero-padded weight columns -- against float64."""
+    from mlagg_unet_amd import _lib, ops
+    P = H * W
+    assert _lib.lib().mlagg_conv1x1_supported(I, -(-O // 16) * 16, P)
     g = torch.Generator().manual_seed(I + O)
-    x = torch.randn(B, I, H, W, generator=g).to(DEV)
-    w3 = (torch.randn(O, I, 3, 3, generator=g) * (9 * I) ** -0.5).to(DEV)
-    w1 = (torch.randn(O, I, 1, 1, generator=g) * I ** -0.5).to(DEV)
-    g3, g1 = torch.randn(B, O, H, W, generator=g).to(DEV), torch.randn(B, O, H, W, generator=g).to(DEV)
-    res = []
-    for paired in (True, False):
-        xs, a3, a1 = x.clone().requires_grad_(True), w3.clone().requires_grad_(True), w1.clone().requires_grad_(True)
-        c3, c1 = ops.conv_pair(xs, a3, a1) if paired else (ops.conv3x3(xs, a3), ops.conv1x1(xs, a1))
-        torch.autograd.backward([c3, c1], [g3, g1])
-        res.append((c3.detach(), c1.detach(), a3.grad, a1.grad, xs.grad))
-    for a, b in zip(res[0][:4], res[1][:4]):
-        assert torch.equal(a, b)
-    xr, r3, r1 = x.double().requires_grad_(True), w3.double(), w1.double()
-    torch.autograd.backward([F.conv2d(xr, r3, None, 1, 1), F.conv2d(xr, r1)], [g3.double(), g1.double()])
-    err = float((res[0][4].double() - xr.grad).abs().max() / xr.grad.abs().max())
+    x = torch.randn(B, O, H, W, generator=g).to(DEV)
+    w = (torch.randn(I, O, generator=g) * O ** -0.5).to(DEV)
+    y0 = torch.randn(B, I, H, W, generator=g).to(DEV)
+    y = y0.clone()
+    ops._conv1x1_k18(x, x.stride(0), w, y, B, I, O, P, ops._DTYPE_BF16X3, accumulate=True)
+    want = y0.double() + F.conv2d(x.double(), w.double().view(I, O, 1, 1))
+    err = float((y.double() - want).abs().max() / want.abs().max())
     assert err < 2e-6, err
 
 

@@ -112,3 +112,15 @@ def test_weight_stacks_survive_two_forwards_and_never_serve_stale_rows():
     a.data.add_(1.0)                                      # ... then rewritten behind autograd's back (what ClipAdamW's kernels do)
     ops.invalidate_weight_images()                        # ... which is why ClipAdamW bumps the epoch
     assert torch.equal(st.get()[:3], a.detach())
+
+
+def test_a_forward_keeps_no_reference_to_its_parameters():
+    """A projection's forward leaves nothing behind that holds its parameters: once the caller drops them they are freed."""
+    import gc
+    import weakref
+    w, b = torch.nn.Parameter(torch.randn(8, 4)), torch.nn.Parameter(torch.randn(8))
+    ops.linear(torch.randn(2, 3, 4), w, b)
+    ref = weakref.ref(w)
+    del w, b
+    gc.collect()
+    assert ref() is None

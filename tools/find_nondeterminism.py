@@ -48,7 +48,7 @@ def main():
             if not torch.equal(g, ref[2][n]):
                 rel = float((g - ref[2][n]).abs().max() / (ref[2][n].abs().max() + 1e-30))
                 bad[n] = max(bad.get(n, 0.0), rel)
-    print(f"mode: K15_2D={os.environ.get('MLAGG_K15_2D', '0')} cudnn.deterministic={a.deterministic} det_loss={os.environ.get('MLAGG_DETERMINISTIC', '0')}")
+    print(f"mode: cudnn.deterministic={a.deterministic}")
     print(f"logits bit-identical: {not bad_out}; loss bit-identical: {not bad_loss}; gradients that differ: {len(bad)} of {len(ref[2])}")
     for n, _ in net.named_parameters():
         if n in bad:

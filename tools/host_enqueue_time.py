@@ -45,8 +45,7 @@ def main():
         t2 = time.perf_counter()
         host.append((t1 - t0) * 1e3)
         total.append((t2 - t0) * 1e3)
-    print(f"config {a.config} {cfg['precision']}: host enqueue {sorted(host)[len(host) // 2]:.2f} ms, step incl. GPU {sorted(total)[len(total) // 2]:.2f} ms "
-          f"(flags: arena={os.environ.get('MLAGG_GRAD_ARENA', '1')} resln={os.environ.get('MLAGG_FUSED_RESIDUAL_NORM', '1')})")
+    print(f"config {a.config} {cfg['precision']}: host enqueue {sorted(host)[len(host) // 2]:.2f} ms, step incl. GPU {sorted(total)[len(total) // 2]:.2f} ms")
 
 
 if __name__ == "__main__":
