@@ -352,6 +352,27 @@ int mlagg_conv3x3_wgrad_lp(const float *dy, long dy_batch, const float *x, long 
                            int I, int H, int W, int dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K19t: the 3 x 3, stride-2, padding-1 transposed convolution of PatchExpand (nnUNetTrainer_MLAgg_2D_dt_MS.py:506-513, conv1 =
+ * nn.ConvTranspose2d(cin, cout, 3, stride=2, padding=1)) and its two gradients, in the operand form `dtype` (MLAGG_DTYPE_BF16X3: fp32
+ * layers; MLAGG_DTYPE_BF16 / _F16: the 16-bit modes, see mlagg_conv1x1_fwd_lp).  w is the layer's (I, O, 3, 3) weight.
+ *   forward: y (B, O, 2H - 1, 2W - 1) = conv_transpose2d(x (B, I, H, W), w), what the library returns (PatchExpand's pad stays);
+ *   data gradient: dx (B, I, H, W) = conv2d(dy, w, stride 2, padding 1), dy (B, O, 2H - 1, 2W - 1) at any channel / row stride (the
+ *   interior of the padded gradient qualifies); weight gradient: dW (I, O, 3, 3), overwritten.
+ *   workspace: mlagg_conv3x3_s2t_workspace_bytes(O, I) bytes, 16-byte aligned (the pre-split weight image) for the forward / data
+ *   gradient; mlagg_conv3x3_s2t_wgrad_workspace_floats floats for the weight gradient.
+ * Supported (mlagg_conv3x3_s2t_supported): O % 16 == 0 and I % 16 == 0, every sample of x, dy and dx under 2 GB.
+ * ------------------------------------------------------------------------------------------ */
+int mlagg_conv3x3_s2t_supported(int O, int I, int H, int W);
+size_t mlagg_conv3x3_s2t_workspace_bytes(int O, int I);
+int mlagg_conv3x3_s2t_fwd(const float *x, long x_batch, const float *w, float *y, long y_batch, void *workspace, int B, int O, int I,
+                          int H, int W, int dtype, void *stream);
+int mlagg_conv3x3_s2_dgrad(const float *dy, long dy_batch, long dy_chan_stride, long dy_row_stride, const float *w, float *dx,
+                           long dx_batch, void *workspace, int B, int O, int I, int H, int W, int dtype, void *stream);
+size_t mlagg_conv3x3_s2t_wgrad_workspace_floats(int B, int O, int I, int H, int W);
+int mlagg_conv3x3_s2t_wgrad(const float *x, long x_batch, const float *dy, long dy_batch, long dy_chan_stride, long dy_row_stride,
+                            float *dW, float *workspace, int B, int O, int I, int H, int W, int dtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K17: key / value reduction of the pooled attention branch, pooled (B, (H/r)(W/r), d) = r x r window mean of GELU(s), s (B, H W, d)
  * token-major at row stride s_stride (a column block of the stacked q | v | sr projection).  Replaces nn.GELU + nn.AdaptiveAvgPool2d
  * at nnUNetTrainer_MLAgg_2D_dt_MS.py:722 (modules at :668, :671) for H % r == W % r == 0 (other sizes: MLAGG_E_UNSUPPORTED, the

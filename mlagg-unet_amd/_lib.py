@@ -107,6 +107,12 @@ SIGNATURES = {
     "mlagg_conv3x3_wgrad": (_I, [_F, ctypes.c_long, _F, ctypes.c_long, _F, _F, _I, _I, _I, _I, _I, _S]),
     "mlagg_conv3x3_fwd_lp": (_I, [_F, ctypes.c_long, _F, _I, _F, _F, ctypes.c_long, _F, _I, _I, _I, _I, _I, _I, _S]),
     "mlagg_conv3x3_wgrad_lp": (_I, [_F, ctypes.c_long, _F, ctypes.c_long, _F, _F, _I, _I, _I, _I, _I, _I, _S]),
+    "mlagg_conv3x3_s2t_supported": (_I, [_I, _I, _I, _I]),
+    "mlagg_conv3x3_s2t_workspace_bytes": (_SZ, [_I, _I]),
+    "mlagg_conv3x3_s2t_fwd": (_I, [_F, ctypes.c_long, _F, _F, ctypes.c_long, _F, _I, _I, _I, _I, _I, _I, _S]),
+    "mlagg_conv3x3_s2_dgrad": (_I, [_F, ctypes.c_long, ctypes.c_long, ctypes.c_long, _F, _F, ctypes.c_long, _F, _I, _I, _I, _I, _I, _I, _S]),
+    "mlagg_conv3x3_s2t_wgrad_workspace_floats": (_SZ, [_I, _I, _I, _I, _I]),
+    "mlagg_conv3x3_s2t_wgrad": (_I, [_F, ctypes.c_long, _F, ctypes.c_long, ctypes.c_long, ctypes.c_long, _F, _F, _I, _I, _I, _I, _I, _I, _S]),
     "mlagg_pixel_unshuffle2_strided": (_I, [_F, ctypes.c_long, _F, _I, _I, _I, _I, _S]),
     "mlagg_pixel_shuffle2": (_I, [_F, _F, _I, _I, _I, _I, _I, _S]),
     "mlagg_conv1x1_fwd_acc": (_I, [_F, ctypes.c_long, _F, _F, _F, ctypes.c_long, _I, _I, _I, _I, ctypes.c_long, _I, _I, _S]),

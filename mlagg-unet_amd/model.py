@@ -224,11 +224,16 @@ class ConvTranspose2d(_ConvMixin, nn.ConvTranspose2d):
     def _t2(self, x, form):
         return ops.conv_t2x2_supported(x, self.weight, self.stride, self.padding, self.output_padding, self.dilation, self.groups, form)
 
+    def _s2t(self, x, form):
+        return ops.conv3x3_s2t_supported(x, self.weight, self.stride, self.padding, self.output_padding, self.dilation, self.groups, form)
+
     def _fp32_conv(self, x):
         if self._k18(x, ops._DTYPE_BF16X3):
             return ops.conv1x1(x, self.weight.permute(1, 0, 2, 3))
         if self._t2(x, ops._DTYPE_BF16X3):
             return ops.conv_t2x2(x, self.weight)                     # K18 + pixel shuffle
+        if self._s2t(x, ops._DTYPE_BF16X3):
+            return ops.conv3x3_s2t(x, self.weight)                   # K19t (PatchExpand)
         return self._lib_conv(x, self.weight)
 
     def _lp_conv(self, x, form):
@@ -236,6 +241,8 @@ class ConvTranspose2d(_ConvMixin, nn.ConvTranspose2d):
             return ops.conv1x1(x, self.weight.permute(1, 0, 2, 3), form)
         if self._t2(x, form):
             return ops.conv_t2x2(x, self.weight, form)
+        if self._s2t(x, form):
+            return ops.conv3x3_s2t(x, self.weight, form)
         return None
 
     def _eager(self, x):

@@ -2336,6 +2336,118 @@ def conv3x3(x, weight, form=_DTYPE_BF16X3):
     return Conv3x3Fn.apply(x, weight, form, _claim(x))
 
 
+# K19t: the 3 x 3, stride-2, padding-1 transposed convolution of PatchExpand (T:506-513) -- forward, data gradient and weight gradient
+# (csrc/conv3x3_s2t.hip).  MLAGG_K19T=0: the library's transposed-convolution solvers, today's dispatch.
+K19T = _os.environ.get("MLAGG_K19T", "1") == "1"
+# The weight gradient on the kernel: off by default -- the per-lane loads of its 32 channel rows bind it on the texture addresser at 29-34
+# TF/s, 2.6x MIOpen's time on the three PatchExpand shapes (profiles/round5_a_conv3x3_s2t_vs_miopen.log); forward and data gradient
+# win (fp32: 442 vs 554 and 367 vs 485 us over the three layers at batch 10).  Per-product choice, as Conv3x3Fn makes it.
+K19T_WGRAD = _os.environ.get("MLAGG_K19T_WGRAD", "0") == "1"
+
+
+def _k19t_shape(O, I, H, W, form=_DTYPE_BF16X3):
+    floor = K19_MIN_PIXELS if form == _DTYPE_BF16X3 else LP_K_MIN_PIXELS
+    return K19T and H * W >= floor and bool(_lib.lib().mlagg_conv3x3_s2t_supported(O, I, H, W))
+
+
+def _k19t_fwd(x, xb, w, O, I, H, W, form):
+    lib = _lib.lib()
+    B = x.shape[0]
+    y = torch.empty(B, O, 2 * H - 1, 2 * W - 1, device=x.device, dtype=torch.float32)
+    ws = torch.empty(lib.mlagg_conv3x3_s2t_workspace_bytes(O, I), device=x.device, dtype=torch.uint8)
+    _flop("K19", 2 * 9 * B * O * I * H * W)
+    _lib.check(lib.mlagg_conv3x3_s2t_fwd(_ptr(x), xb, _ptr(w), _ptr(y), y.stride(0), _ptr(ws), B, O, I, H, W, form, _stream()),
+               "mlagg_conv3x3_s2t_fwd")
+    return y
+
+
+def _k19t_dgrad(dy, w, O, I, H, W, form):
+    lib = _lib.lib()
+    B = dy.shape[0]
+    dx = torch.empty(B, I, H, W, device=dy.device, dtype=torch.float32)
+    ws = torch.empty(lib.mlagg_conv3x3_s2t_workspace_bytes(O, I), device=dy.device, dtype=torch.uint8)
+    _flop("K19", 2 * 9 * B * O * I * H * W)
+    _lib.check(lib.mlagg_conv3x3_s2_dgrad(_ptr(dy), dy.stride(0), dy.stride(1), dy.stride(2), _ptr(w), _ptr(dx), dx.stride(0), _ptr(ws),
+                                          B, O, I, H, W, form, _stream()), "mlagg_conv3x3_s2_dgrad")
+    return dx
+
+
+def _k19t_wgrad(x, xb, dy, O, I, H, W, form):
+    lib = _lib.lib()
+    B = x.shape[0]
+    dW = torch.empty(I, O, 3, 3, device=x.device, dtype=torch.float32)
+    ws = torch.empty(lib.mlagg_conv3x3_s2t_wgrad_workspace_floats(B, O, I, H, W), device=x.device, dtype=torch.float32)
+    _flop("K19", 2 * 9 * B * O * I * H * W)
+    _lib.check(lib.mlagg_conv3x3_s2t_wgrad(_ptr(x), xb, _ptr(dy), dy.stride(0), dy.stride(1), dy.stride(2), _ptr(dW), _ptr(ws), B, O, I,
+                                           H, W, form, _stream()), "mlagg_conv3x3_s2t_wgrad")
+    return dW
+
+
+def _lib_convt_s2(x, w, form):
+    if form == _DTYPE_BF16X3:
+        return torch.nn.functional.conv_transpose2d(x, w, None, 2, 1)
+    t = _FORM_TORCH[form]
+    return torch.nn.functional.conv_transpose2d(x.to(t), w.to(t), None, 2, 1).float()
+
+
+def _lib_convt_s2_bwd(dy, x, w, mask, form):
+    if form != _DTYPE_BF16X3:
+        t = _FORM_TORCH[form]
+        dy, x, w = dy.to(t), x.to(t), w.to(t)
+    out = torch.ops.aten.convolution_backward(dy.contiguous(), x, w, None, (2, 2), (1, 1), (1, 1), True, (0, 0), 1, mask)
+    return [None if o is None else o.float() for o in out]
+
+
+class ConvT3x3S2Fn(torch.autograd.Function):
+    """y = conv_transpose2d(x, W, stride=2, padding=1) for a dense 3 x 3 kernel (no bias), y (B, O, 2H - 1, 2W - 1): the three products
+    on K19t in operand form `form`, each one on the library where the kernel does not take it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, form=_DTYPE_BF16X3):
+        x, xb, _ = _planes(x, "x")
+        B, I, H, W = x.shape
+        O = int(weight.shape[1])
+        w = _require(weight.contiguous(), "weight")
+        y = _k19t_fwd(x, xb, w, O, I, H, W, form) if _k19t_shape(O, I, H, W, form) else _lib_convt_s2(x, w, form)
+        ctx.save_for_backward(x, w)
+        ctx.form = form
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        B, I, H, W = x.shape
+        O = int(w.shape[1])
+        form = ctx.form
+        on = _k19t_shape(O, I, H, W, form)
+        if on and (dy.stride(3) != 1 or dy.data_ptr() % 4):
+            dy = dy.contiguous()                                  # any channel / row stride is fine, a strided row is not
+        dx = dW = None
+        if ctx.needs_input_grad[0]:
+            dx = _k19t_dgrad(dy, w, O, I, H, W, form) if on else _lib_convt_s2_bwd(dy, x, w, (True, False, False), form)[0]
+        if ctx.needs_input_grad[1]:
+            if on and K19T_WGRAD:
+                dW = _k19t_wgrad(x, x.stride(0), dy, O, I, H, W, form)
+            else:
+                dW = _lib_convt_s2_bwd(dy, x, w, (False, True, False), form)[1]
+        return dx, dW, None
+
+
+def conv3x3_s2t_supported(x, weight, stride, padding, output_padding, dilation, groups, form=_DTYPE_BF16X3):
+    """A dense 3 x 3 transposed convolution with stride 2, padding 1, no output padding, on an fp32 device map that K19t takes."""
+    if not (K19T and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and groups == 1):
+        return False
+    if tuple(weight.shape[2:]) != (3, 3) or any(int(v) != 2 for v in stride) or any(int(v) != 1 for v in padding) or \
+            any(int(v) != 0 for v in output_padding) or any(int(v) != 1 for v in dilation):
+        return False
+    I, O = int(weight.shape[0]), int(weight.shape[1])
+    return _k19t_shape(O, I, int(x.shape[2]), int(x.shape[3]), form)
+
+
+def conv3x3_s2t(x, weight, form=_DTYPE_BF16X3):
+    return ConvT3x3S2Fn.apply(x, weight, form)
+
+
 K19_3D = _os.environ.get("MLAGG_K19_3D", "1") == "1"
 K19_3D_WGRAD = _os.environ.get("MLAGG_K19_3D_WGRAD", "1") == "1"
 
