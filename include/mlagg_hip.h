@@ -668,6 +668,29 @@ int mlagg_adamw_clip_step(const void *tensor_table, const void *work_list, int n
 int mlagg_adamw_clip_step_dev(const void *tensor_table, const void *work_list, int n_work, double *sumsq, const float *lr_dev,
                               int *step_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K20: 3-D sliding-window inference (reference nnunetv2/inference/sliding_window_prediction.py:60-210 for a 3-D tile_size).
+ * fp32 throughout, Z the contiguous axis, 64-bit volume offsets.  flips: HOST array of the V mirror variants (V in {1, 2, 4, 8}),
+ * each a bitmask of flipped tile axes (bit a = axis a), in the reference's order none, 0, 1, 2, (0,1), (0,2), (1,2), (0,1,2)
+ * restricted to the requested axes (maybe_mirror_and_predict :87-115).
+ *   gather:   vol (C, X, Y, Z) padded input -> out (V * n, C, tx, ty, tz), variant-major then tile, variant v flipped along its axes.
+ *             origins: HOST array of n (x, y, z) tile origins; every tile must lie inside the volume.  Replaces `data[sl][None]`
+ *             (:193) and the torch.flip input copies of :97-114.
+ *   fold:     for tile `tile` of a chunk output out (V * n, K, tx, ty, tz) at origin (ox, oy, oz): s = out_0 + flip_1(out_1) + ...
+ *             in variant order, s /= V, acc[k, o + p] += s * gauss[p], w[o + p] += gauss[p]; acc (K, X, Y, Z), w (X, Y, Z).  Replaces
+ *             the flipped output copies and their sum (:97-115) and the accumulation (:200-201).  One call per tile, in tile order:
+ *             the overlapping tiles accumulate in the reference's order, whatever the chunking.
+ *   finalize: logits (K, X0, Y0, Z0) = acc / w on the region starting at (lx, ly, lz), contiguous (:203, :206); labels
+ *             (X0, Y0, Z0) int64 = argmax over K with torch.argmax's first-maximum rule, or NULL.
+ * No atomics: bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int mlagg_sw_gather(const float *vol, int C, int X, int Y, int Z, const int *origins, int n, const int *flips, int V, float *out,
+                    int tx, int ty, int tz, void *stream);
+int mlagg_sw_fold(const float *out, int tile, int n, const int *flips, int V, int K, const float *gauss, int tx, int ty, int tz,
+                  int ox, int oy, int oz, float *acc, float *w, int X, int Y, int Z, void *stream);
+int mlagg_sw_finalize(const float *acc, const float *w, int K, int X, int Y, int Z, int lx, int ly, int lz, int X0, int Y0, int Z0,
+                      float *logits, long long *labels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
-"""Sliding-window inference for the 2-D MLAgg-UNet on MI355X, the device side of
-the reference's mlagg/nnunetv2/inference/sliding_window_prediction.py:118-210 and the network restore of
+"""Sliding-window inference for the 2-D MLAgg-UNet and the 3-D UMambaEnc on MI355X, the device side
+of the reference's mlagg/nnunetv2/inference/sliding_window_prediction.py:60-210 and the network restore of
 predict_from_raw_data.py:96-99.
 
 Same tiling, Gaussian importance map and mirror test-time augmentation as the reference, but
@@ -9,6 +9,11 @@ Same tiling, Gaussian importance map and mirror test-time augmentation as the re
   * logits and weights accumulate in fp32 on the device (the reference accumulates in half),
   * a training checkpoint (which holds the deep-supervision heads out_1..out_4) loads into the inference
     network built with enable_deep_supervision=False (the reference's strict load fails: SURVEY finding 7d).
+
+3-D tiles on a (c, x, y, z) volume (every 3d_fullres model) take the K20 kernels of csrc/sliding_window.hip on the device: one
+gather builds a chunk's network input with every mirror variant, one fold per tile sums the variants, scales by the Gaussian and
+accumulates in the reference's order, and one finalize divides, crops and (optionally) takes the argmax -- no flipped copy of an
+output, no transient, a contiguous result.  On a CPU device the same order runs as a torch composition (_sliding_window_3d_torch).
 """
 import numpy as np
 import torch
@@ -64,11 +69,104 @@ def load_inference_weights(network, state_dict):
     return dropped
 
 
+def mirror_variants(mirror_axes):
+    """Mirror variants of a 3-D tile as bitmasks of flipped axes (bit a = axis a), in maybe_mirror_and_predict's order
+    (reference :87-115): none, 0, 1, 2, (0, 1), (0, 2), (1, 2), (0, 1, 2), restricted to the requested axes."""
+    if mirror_axes is None:
+        return [0]
+    axes = set(int(a) for a in mirror_axes)
+    if not axes or min(axes) < 0 or max(axes) > 2:
+        raise RuntimeError("mirror_axes does not match the dimension of the input")
+    order = [(), (0,), (1,), (2,), (0, 1), (0, 2), (1, 2), (0, 1, 2)]
+    return [sum(1 << a for a in f) for f in order if set(f) <= axes]
+
+
+def _flip_dims(mask, first):
+    return tuple(first + a for a in range(3) if mask >> a & 1)
+
+
+def _sliding_window_3d_torch(network, data, gaussian, places, flips, tile_size, tile_batch, num_heads):
+    """Torch composition of the 3-D sliding window in the reference's order, on data's device: returns the padded accumulators
+    (logits sum (K, X, Y, Z), weight sum (X, Y, Z)) in fp32.  The host path of the 3-D branch, and the A/B side of
+    tools/bench_inference_3d.py."""
+    tx, ty, tz = tile_size
+    logits = torch.zeros((num_heads,) + tuple(data.shape[1:]), dtype=torch.float32, device=data.device)
+    weight = torch.zeros(tuple(data.shape[1:]), dtype=torch.float32, device=data.device)
+    for i in range(0, len(places), tile_batch):
+        chunk = places[i:i + tile_batch]
+        tiles = torch.stack([data[:, sx:sx + tx, sy:sy + ty, sz:sz + tz] for sx, sy, sz in chunk])   # (n, c, tx, ty, tz)
+        batch = torch.cat([torch.flip(tiles, _flip_dims(m, 2)) if m else tiles for m in flips])
+        out = network(batch)
+        if isinstance(out, (list, tuple)):
+            raise RuntimeError("the inference network must be built with enable_deep_supervision=False")
+        n = len(chunk)
+        for j, (sx, sy, sz) in enumerate(chunk):
+            pred = out[j].clone()
+            for v, m in enumerate(flips[1:], start=1):
+                pred += torch.flip(out[v * n + j], _flip_dims(m, 1))
+            pred = pred / len(flips) * gaussian
+            logits[:, sx:sx + tx, sy:sy + ty, sz:sz + tz] += pred
+            weight[sx:sx + tx, sy:sy + ty, sz:sz + tz] += gaussian
+    return logits, weight
+
+
+def _predict_3d(network, input_image, num_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch, device,
+                want_labels):
+    """(c, x, y, z) volume, 3-D tile -> (logits (K, x, y, z), labels (x, y, z) int64 or None), contiguous fp32 on `device`."""
+    tile_size = tuple(int(t) for t in tile_size)
+    flips = mirror_variants(mirror_axes)
+    data, revert = _pad_to_tile(torch.as_tensor(input_image, dtype=torch.float32), tile_size)
+    data = data.to(device).contiguous()
+    gaussian = compute_gaussian(tile_size).to(device) if use_gaussian else torch.ones(tile_size, device=device)
+    steps = compute_steps_for_sliding_window(tuple(data.shape[1:]), tile_size, tile_step_size)
+    places = [(sx, sy, sz) for sx in steps[0] for sy in steps[1] for sz in steps[2]]
+    if device.type != "cuda":
+        logits, weight = _sliding_window_3d_torch(network, data, gaussian, places, flips, tile_size, tile_batch, num_heads)
+        logits /= weight
+        logits = logits[(slice(None), *revert)].contiguous()
+        return logits, (logits.argmax(0) if want_labels else None)
+    from . import ops
+    X, Y, Z = data.shape[1:]
+    acc = torch.zeros((num_heads, X, Y, Z), dtype=torch.float32, device=device)
+    weight = torch.zeros((X, Y, Z), dtype=torch.float32, device=device)
+    for i in range(0, len(places), tile_batch):
+        chunk = places[i:i + tile_batch]
+        out = network(ops.sliding_window_gather(data, chunk, flips, tile_size))
+        if isinstance(out, (list, tuple)):
+            raise RuntimeError("the inference network must be built with enable_deep_supervision=False")
+        if tuple(out.shape) != (len(flips) * len(chunk), num_heads) + tile_size:
+            raise RuntimeError(f"network output {tuple(out.shape)}: expected {(len(flips) * len(chunk), num_heads) + tile_size}")
+        out = out.contiguous()
+        for j, origin in enumerate(chunk):
+            ops.sliding_window_fold(out, j, len(chunk), flips, gaussian, origin, acc, weight)
+    return ops.sliding_window_finalize(acc, weight, revert, return_labels=want_labels)
+
+
+def _run_3d(network, input_image, num_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch, device,
+            want_labels):
+    """Argument handling of the two public functions for a 3-D tile_size."""
+    if input_image.dim() != 4:
+        raise RuntimeError("input_image must be (c, x, y, z) for a 3-D tile_size")
+    tile_batch = 1 if tile_batch is None else int(tile_batch)
+    if tile_batch < 1:
+        raise RuntimeError("tile_batch must be at least 1")
+    device = torch.device(device) if device is not None else next(network.parameters()).device
+    network.eval()
+    return _predict_3d(network, input_image, num_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch, device,
+                       want_labels)
+
+
 @torch.no_grad()
 def predict_sliding_window_return_logits(network, input_image, num_segmentation_heads, tile_size, mirror_axes=None,
-                                         tile_step_size=0.5, use_gaussian=True, tile_batch=8, device=None):
-    """input_image (c, D, X, Y) with a 2-D tile_size -> fp32 logits (num_segmentation_heads, D, X, Y) on `device`.
-    `network(x)` must return a tensor (deep supervision disabled)."""
+                                         tile_step_size=0.5, use_gaussian=True, tile_batch=None, device=None):
+    """input_image (c, D, X, Y) with a 2-D tile_size, or (c, x, y, z) with a 3-D tile_size -> fp32 logits
+    (num_segmentation_heads, ...) on `device`.  `network(x)` must return a tensor (deep supervision disabled).  tile_batch: tiles per
+    network call (the batch is tile_batch * 2^|mirror_axes|); default 8 for 2-D tiles, 1 for 3-D tiles."""
+    if len(tile_size) == 3:
+        return _run_3d(network, input_image, num_segmentation_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch,
+                       device, False)[0]
+    if tile_batch is None:
+        tile_batch = 8
     if input_image.dim() != 4 or len(tile_size) != 2:
         raise RuntimeError("input_image must be (c, D, X, Y) and tile_size 2-D")
     device = torch.device(device) if device is not None else next(network.parameters()).device
@@ -108,3 +206,15 @@ def predict_sliding_window_return_logits(network, input_image, num_segmentation_
             weight[d, sx:sx + tx, sy:sy + ty] += gaussian
     logits /= weight
     return logits[(slice(None), slice(None), *revert)]
+
+
+@torch.no_grad()
+def predict_sliding_window_return_segmentation(network, input_image, num_segmentation_heads, tile_size, mirror_axes=None,
+                                               tile_step_size=0.5, use_gaussian=True, tile_batch=None, device=None):
+    """The int64 label map argmax_k(logits) of predict_sliding_window_return_logits (torch.argmax's first-maximum rule).  3-D tiles
+    on the device take it from the finalize kernel, which writes it next to the logits without a second pass over them."""
+    if len(tile_size) == 3:
+        return _run_3d(network, input_image, num_segmentation_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch,
+                       device, True)[1]
+    return predict_sliding_window_return_logits(network, input_image, num_segmentation_heads, tile_size, mirror_axes,
+                                                tile_step_size, use_gaussian, tile_batch, device).argmax(0)

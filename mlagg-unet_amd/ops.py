@@ -2699,3 +2699,92 @@ def conv_nd(x, weight, stride, padding):
         return ConvNdFn.apply(x, weight, tuple(stride), tuple(padding))
     conv = torch.nn.functional.conv3d if x.dim() == 5 else torch.nn.functional.conv2d
     return conv(x, weight, None, stride, padding)
+
+
+# ------------------------------------------------------------------------------------------------
+# K20: 3-D sliding-window inference (csrc/sliding_window.hip).  Mirror variants are bitmasks of flipped tile axes (bit a = axis a),
+# in the reference's order (inference.mirror_variants).  No autograd: inference only.
+# ------------------------------------------------------------------------------------------------
+def _sw_volume(t, name, nd):
+    _require(t, name)
+    if t.dim() != nd or not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous {nd}-D tensor, got shape {tuple(t.shape)}"
+                           f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+    return t
+
+
+def _sw_flips(flips):
+    flips = [int(m) for m in flips]
+    if len(flips) not in (1, 2, 4, 8) or any(m < 0 or m > 7 for m in flips) or len(set(flips)) != len(flips):
+        raise RuntimeError(f"mirror variants {flips}: 1, 2, 4 or 8 distinct masks in [0, 7]")
+    return flips
+
+
+def _sw_box(origin, tile, shape, what):
+    o = tuple(int(v) for v in origin)
+    if len(o) != 3 or any(v < 0 or v + t > s for v, t, s in zip(o, tile, shape)):
+        raise RuntimeError(f"{what}: tile at {o} of size {tuple(tile)} is not inside the volume {tuple(shape)}")
+    return o
+
+
+def sliding_window_gather(volume, origins, flips, tile_size):
+    """volume (C, X, Y, Z) -> network input (V * n, C, tx, ty, tz): the n tiles at `origins`, variant-major, variant v flipped
+    along the axes of mask flips[v]."""
+    _sw_volume(volume, "volume", 4)
+    flips = _sw_flips(flips)
+    tile = tuple(int(t) for t in tile_size)
+    if len(tile) != 3 or min(tile) < 1:
+        raise RuntimeError(f"tile_size {tile_size}: three positive sides")
+    C, X, Y, Z = volume.shape
+    boxes = [_sw_box(o, tile, (X, Y, Z), "sliding_window_gather") for o in origins]
+    if not boxes:
+        raise RuntimeError("sliding_window_gather: no tiles")
+    out = torch.empty((len(flips) * len(boxes), C) + tile, device=volume.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mlagg_sw_gather(_ptr(volume), C, X, Y, Z, _int_array([v for o in boxes for v in o]), len(boxes),
+                                          _int_array(flips), len(flips), _ptr(out), *tile, _stream()), "mlagg_sw_gather")
+    return out
+
+
+def sliding_window_fold(out, tile, n, flips, gaussian, origin, acc, weight):
+    """Fold tile `tile` of the chunk output out (V * n, K, tx, ty, tz) into acc (K, X, Y, Z) and weight (X, Y, Z) at `origin`:
+    acc += mean over the variants of the flipped-back outputs * gaussian, weight += gaussian (in place)."""
+    _sw_volume(out, "out", 5)
+    _sw_volume(acc, "acc", 4)
+    _sw_volume(weight, "weight", 3)
+    flips = _sw_flips(flips)
+    V, n, tile = len(flips), int(n), int(tile)
+    K, tx, ty, tz = (int(v) for v in out.shape[1:])
+    gaussian = _require(gaussian.contiguous(), "gaussian", (tx, ty, tz))
+    if out.shape[0] != V * n or not 0 <= tile < n:
+        raise RuntimeError(f"sliding_window_fold: out has {out.shape[0]} rows, expected {V} variants x {n} tiles; tile {tile}")
+    if acc.shape[0] != K or acc.shape[1:] != weight.shape:
+        raise RuntimeError(f"sliding_window_fold: acc {tuple(acc.shape)} / weight {tuple(weight.shape)} for {K} classes")
+    X, Y, Z = weight.shape
+    o = _sw_box(origin, (tx, ty, tz), (X, Y, Z), "sliding_window_fold")
+    _lib.check(_lib.lib().mlagg_sw_fold(_ptr(out), tile, n, _int_array(flips), V, K, _ptr(gaussian), tx, ty, tz, *o,
+                                        _ptr(acc), _ptr(weight), X, Y, Z, _stream()), "mlagg_sw_fold")
+
+
+def sliding_window_finalize(acc, weight, region, return_labels=False):
+    """logits (K, X0, Y0, Z0) = acc / weight on `region` (three slices with explicit bounds), a new contiguous tensor; with
+    return_labels also the int64 argmax over K (torch.argmax's first-maximum rule).  Returns (logits, labels or None)."""
+    _sw_volume(acc, "acc", 4)
+    _sw_volume(weight, "weight", 3)
+    if acc.shape[1:] != weight.shape:
+        raise RuntimeError(f"sliding_window_finalize: acc {tuple(acc.shape)} / weight {tuple(weight.shape)}")
+    K = int(acc.shape[0])
+    shape = tuple(int(s) for s in weight.shape)
+    lo, size = [], []
+    for sl, s in zip(region, shape):
+        a, b = (0 if sl.start is None else int(sl.start)), (s if sl.stop is None else int(sl.stop))
+        if sl.step not in (None, 1) or not 0 <= a < b <= s:
+            raise RuntimeError(f"sliding_window_finalize: region {region} is not inside {shape}")
+        lo.append(a)
+        size.append(b - a)
+    if len(lo) != 3:
+        raise RuntimeError("sliding_window_finalize: region must hold three slices")
+    logits = torch.empty((K,) + tuple(size), device=acc.device, dtype=torch.float32)
+    labels = torch.empty(tuple(size), device=acc.device, dtype=torch.int64) if return_labels else None
+    _lib.check(_lib.lib().mlagg_sw_finalize(_ptr(acc), _ptr(weight), K, *shape, *lo, *size, _ptr(logits), _ptr(labels), _stream()),
+               "mlagg_sw_finalize")
+    return logits, labels
