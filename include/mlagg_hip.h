@@ -691,6 +691,28 @@ int mlagg_sw_fold(const float *out, int tile, int n, const int *flips, int V, in
 int mlagg_sw_finalize(const float *acc, const float *w, int K, int X, int Y, int Z, int lx, int ly, int lz, int X0, int Y0, int Z0,
                       float *logits, long long *labels, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K21: prediction export on the device (reference nnunetv2/inference/export_prediction.py:10-69 with the default
+ * resample_data_or_seg_to_shape(is_seg=False, order=1, order_z=0), preprocessing/resampling/default_resampling.py:76-200).
+ * Logits (C|K, X, Y, Z) fp32 with element strides (sc, sx, sy, sz) >= 0: any view.  tap_idx (X' + Y' + Z', 2) int32 and
+ * tap_w (X' + Y' + Z', 2) fp64 are DEVICE tables built by export._axis_taps: for output index o of an axis, the two source
+ * indices (inside the input's extent along that axis) and their weights; x entries first, then y, then z.  The kernels blend the
+ * eight taps separably (z, then y, then x) in fp64 and round once to fp32.
+ *   resample_linear:     out (C, X', Y', Z') contiguous fp32 (16-byte aligned).  Replaces resample_data_or_seg_to_shape (:76-200).
+ *   export_segmentation: K <= 32 classes; box_lo, shape, perm are HOST arrays of 3: the bbox's lower corner and
+ *                        shape_before_cropping in the preprocessed axis order, and transpose_backward.  The box has extent
+ *                        (X', Y', Z').  labels (shape[perm[0]], shape[perm[1]], shape[perm[2]]) uint8 (4-byte aligned) = argmax
+ *                        of the fp32 softmax of the resampled logits inside the box, 0 outside; probs (K, same) fp32 or NULL,
+ *                        0 outside the box.  Replaces the resampling, convert_logits_to_segmentation, the paste, revert_cropping
+ *                        and the transposes of export_prediction.py:36-63.
+ * No atomics: bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int mlagg_resample_linear(const float *in, int C, int X, int Y, int Z, long long sc, long long sx, long long sy, long long sz,
+                          const int *tap_idx, const double *tap_w, float *out, int Xo, int Yo, int Zo, void *stream);
+int mlagg_export_segmentation(const float *logits, int K, int X, int Y, int Z, long long sc, long long sx, long long sy, long long sz,
+                              const int *tap_idx, const double *tap_w, int Xc, int Yc, int Zc, const int *box_lo, const int *shape,
+                              const int *perm, unsigned char *labels, float *probs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

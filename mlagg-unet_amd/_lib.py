@@ -157,6 +157,9 @@ SIGNATURES = {
     "mlagg_sw_gather": (_I, [_F, _I, _I, _I, _I, ctypes.POINTER(_I), _I, ctypes.POINTER(_I), _I, _F, _I, _I, _I, _S]),
     "mlagg_sw_fold": (_I, [_F, _I, _I, ctypes.POINTER(_I), _I, _I, _F] + [_I] * 6 + [_F, _F, _I, _I, _I, _S]),
     "mlagg_sw_finalize": (_I, [_F, _F] + [_I] * 10 + [_F, _F, _S]),
+    "mlagg_resample_linear": (_I, [_F] + [_I] * 4 + [ctypes.c_longlong] * 4 + [_F, _F, _F] + [_I] * 3 + [_S]),
+    "mlagg_export_segmentation": (_I, [_F] + [_I] * 4 + [ctypes.c_longlong] * 4 + [_F, _F] + [_I] * 3
+                                  + [ctypes.POINTER(_I)] * 3 + [_F, _F, _S]),
     "mlagg_selscan1_chunk": (_I, [_I, _I, _I]),
     "mlagg_selscan1_state_floats": (_SZ, [_I, _I, _I, _I]),
     "mlagg_selscan1_fwd": (_I, [_F, ctypes.c_long] + [_F] * 5 + [_I] + [_F] * 5 + [_I] * 4 + [_S]),

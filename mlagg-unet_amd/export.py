@@ -1,0 +1,273 @@
+"""Prediction export to the original image geometry: the reference's
+mlagg/nnunetv2/inference/export_prediction.py:10-69 with its default probability resampler, resample_data_or_seg_to_shape(is_seg=False,
+order=1, order_z=0, force_separate_z=None) of preprocessing/resampling/default_resampling.py:76-200.
+
+From fp32 logits in the preprocessed geometry (cropped to the non-zero box, resampled to the plan's spacing, transposed by
+transpose_forward) to a uint8 label volume in the original geometry:
+  1. resample the logits to shape_after_cropping_and_before_resampling (order-1 in-plane; order 0 or 1 along a low-resolution axis
+     when the spacing is anisotropic);
+  2. fp32 softmax over the classes and the first-maximum argmax of the probabilities;
+  3. paste the labels (and probabilities) into shape_before_cropping at bbox_used_for_cropping, zeros outside;
+  4. transpose by transpose_backward.
+
+Every coordinate comes from one table per output axis (_axis_taps), built in float64 with the reference's expressions: two source
+indices and their two weights.  A device tensor takes K21 (csrc/export.hip): one fused kernel for up to 32 classes that never
+materialises the resampled logits, or the resampling kernel followed by torch's softmax / argmax for more.  A CPU tensor or numpy
+array takes the host path: the same separable blend in torch float64, then the same fp32 softmax, argmax and paste.  Both give the
+same fp32 resampled logits bit for bit.  Region-based label managers are not supported.
+"""
+import json
+import os
+import pickle
+
+import numpy as np
+import torch
+
+ANISO_THRESHOLD = 3                  # nnunetv2/configuration.py:7
+
+
+# ------------------------------------------------------------------------------------------------
+# the reference's decisions (default_resampling.py:13-20, 76-119)
+# ------------------------------------------------------------------------------------------------
+def get_do_separate_z(spacing, anisotropy_threshold=ANISO_THRESHOLD):
+    return (np.max(spacing) / np.min(spacing)) > anisotropy_threshold
+
+
+def get_lowres_axis(spacing):
+    return np.where(max(spacing) / np.array(spacing) == 1)[0]
+
+
+def separate_z_decision(current_spacing, new_spacing, force_separate_z=None, separate_z_anisotropy_threshold=ANISO_THRESHOLD):
+    """-> (do_separate_z, low-resolution axis or None), as resample_data_or_seg_to_shape decides them (:86-112)."""
+    if force_separate_z is not None:
+        do_separate_z = bool(force_separate_z)
+        axis = get_lowres_axis(current_spacing) if force_separate_z else None
+    elif get_do_separate_z(current_spacing, separate_z_anisotropy_threshold):
+        do_separate_z, axis = True, get_lowres_axis(current_spacing)
+    elif get_do_separate_z(new_spacing, separate_z_anisotropy_threshold):
+        do_separate_z, axis = True, get_lowres_axis(new_spacing)
+    else:
+        do_separate_z, axis = False, None
+    if axis is not None and len(axis) in (2, 3):   # e.g. spacing (0.24, 1.25, 1.25): no separate z
+        do_separate_z = False
+    if not do_separate_z:
+        return False, None
+    return True, int(axis[0])
+
+
+def _axis_taps(n_in, n_out, kind):
+    """Table of one output axis: idx (n_out, 2) int32 and w (n_out, 2) float64, out[o] = in[idx[o, 0]] * w[o, 0] + in[idx[o, 1]] * w[o, 1].
+    kind 'linear': ndi.zoom(order=1, mode='nearest', grid_mode=True), i.e. skimage resize(order=1, mode='edge', anti_aliasing=False):
+    c = (o + 0.5) * n_in / n_out - 0.5 clamped to [0, n_in - 1], taps floor(c) and floor(c) + 1 (clamped), weights 1 - f and f.
+    kind 'nearest': map_coordinates(order=0, mode='nearest') along the low-resolution axis (:172-184): floor(c + 0.5), clamped.
+    kind 'identity': the axis is unchanged."""
+    o = np.arange(n_out, dtype=np.float64)
+    if kind == "identity":
+        if n_in != n_out:
+            raise RuntimeError(f"identity axis of {n_in} -> {n_out}")
+        i0 = o.astype(np.int64)
+        i1, w1 = i0, np.zeros(n_out)
+    else:
+        c = float(n_in) / n_out * (o + 0.5) - 0.5
+        if kind == "nearest":
+            i0 = np.clip(np.floor(c + 0.5), 0, n_in - 1).astype(np.int64)
+            i1, w1 = i0, np.zeros(n_out)
+        elif kind == "linear":
+            c = np.clip(c, 0, n_in - 1)
+            fl = np.floor(c)
+            i0 = fl.astype(np.int64)
+            i1 = np.minimum(i0 + 1, n_in - 1)
+            w1 = c - fl
+        else:
+            raise RuntimeError(f"unknown tap kind {kind!r}")
+    idx = np.stack([i0, i1], 1).astype(np.int32)
+    w = np.stack([1.0 - w1, w1], 1)
+    return idx, w
+
+
+def _check_orders(order, order_z):
+    if order != 1 or order_z not in (0, 1):
+        raise NotImplementedError(f"probability resampling of order {order} / order_z {order_z}: only order 1 with order_z 0 or 1 "
+                                  "(the export default) is implemented")
+
+
+def resampling_plan(in_shape, new_shape, current_spacing, new_spacing, order=1, order_z=0, force_separate_z=None,
+                    separate_z_anisotropy_threshold=ANISO_THRESHOLD):
+    """-> (tap kinds of the three axes, or None when no resampling is needed (the reference returns the data unchanged))."""
+    _check_orders(order, order_z)
+    in_shape, new_shape = tuple(int(s) for s in in_shape), tuple(int(s) for s in new_shape)
+    if len(in_shape) != 3 or len(new_shape) != 3:
+        raise RuntimeError(f"resampling needs three spatial axes, got {in_shape} -> {new_shape}")
+    if in_shape == new_shape:
+        return None
+    sep, axis = separate_z_decision(current_spacing, new_spacing, force_separate_z, separate_z_anisotropy_threshold)
+    kinds = []
+    for a, (n_in, n_out) in enumerate(zip(in_shape, new_shape)):
+        if n_in == n_out:
+            kinds.append("identity")
+        elif sep and a == axis:
+            kinds.append("nearest" if order_z == 0 else "linear")
+        else:
+            kinds.append("linear")
+    return tuple(kinds)
+
+
+def build_taps(in_shape, new_shape, kinds):
+    """The three axis tables of a plan, concatenated x, y, z (identity tables when kinds is None)."""
+    kinds = kinds or ("identity",) * 3
+    parts = [_axis_taps(int(a), int(b), k) for a, b, k in zip(in_shape, new_shape, kinds)]
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+# ------------------------------------------------------------------------------------------------
+# host path: the kernels' arithmetic in torch float64
+# ------------------------------------------------------------------------------------------------
+def _resample_host(logits, taps, new_shape):
+    """(C, X, Y, Z) fp32 CPU -> (C, *new_shape) fp32: blend along z, then y, then x in float64 per channel, rounded once -- the
+    products and sums of csrc/export.hip's interp, in the same order."""
+    idx, w = (torch.from_numpy(a) for a in taps)
+    Xo, Yo, Zo = new_shape
+    ix, iy, iz = idx[:Xo].long(), idx[Xo:Xo + Yo].long(), idx[Xo + Yo:].long()
+    wx, wy, wz = w[:Xo], w[Xo:Xo + Yo], w[Xo + Yo:]
+    out = torch.empty((logits.shape[0],) + tuple(new_shape), dtype=torch.float32)
+    for c in range(logits.shape[0]):
+        v = logits[c].double()
+        v = v[:, :, iz[:, 0]] * wz[:, 0] + v[:, :, iz[:, 1]] * wz[:, 1]
+        v = v[:, iy[:, 0], :] * wy[:, 0, None] + v[:, iy[:, 1], :] * wy[:, 1, None]
+        v = v[ix[:, 0]] * wx[:, 0, None, None] + v[ix[:, 1]] * wx[:, 1, None, None]
+        out[c] = v.float()
+    return out
+
+
+def _as_logits(logits):
+    if isinstance(logits, np.ndarray):
+        logits = torch.from_numpy(logits)
+    if not isinstance(logits, torch.Tensor):
+        raise RuntimeError(f"logits: expected a torch tensor or numpy array, got {type(logits)}")
+    if not logits.is_floating_point():
+        raise RuntimeError(f"logits: expected floating point values, got {logits.dtype}")
+    if logits.dim() != 4 or min(logits.shape) < 1:
+        raise RuntimeError(f"logits: expected a non-empty (C, x, y, z) array, got shape {tuple(logits.shape)}")
+    return logits.float()
+
+
+def resample_logits_to_shape(logits, new_shape, current_spacing, new_spacing, order=1, order_z=0, force_separate_z=None,
+                             separate_z_anisotropy_threshold=ANISO_THRESHOLD):
+    """resample_data_or_seg_to_shape(is_seg=False) (default_resampling.py:76-200) for order 1: logits (C, x, y, z) fp32 ->
+    (C, *new_shape) fp32 on the input's device (K21's resampling kernel on the GPU, the float64 host blend on the CPU).  As in
+    the reference, logits that already have new_shape are returned unchanged."""
+    logits = _as_logits(logits)
+    new_shape = tuple(int(s) for s in new_shape)
+    kinds = resampling_plan(logits.shape[1:], new_shape, current_spacing, new_spacing, order, order_z, force_separate_z,
+                            separate_z_anisotropy_threshold)
+    if kinds is None:
+        return logits
+    taps = build_taps(logits.shape[1:], new_shape, kinds)
+    if logits.is_cuda:
+        from . import ops
+        return ops.resample_linear(logits, taps, new_shape)
+    return _resample_host(logits, taps, new_shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# export
+# ------------------------------------------------------------------------------------------------
+def current_spacing_for(configuration_spacing, properties):
+    """export_prediction.py:29-32: a 2-D configuration (two spacing values) keeps the original spacing of the first axis."""
+    spacing = [float(s) for s in configuration_spacing]
+    if len(spacing) == len(properties["shape_after_cropping_and_before_resampling"]):
+        return spacing
+    return [float(properties["spacing"][0]), *spacing]
+
+
+def _geometry(logits, properties, transpose_backward):
+    crop = tuple(int(s) for s in properties["shape_after_cropping_and_before_resampling"])
+    full = tuple(int(s) for s in properties["shape_before_cropping"])
+    bbox = [tuple(int(v) for v in b) for b in properties["bbox_used_for_cropping"]]
+    perm = tuple(int(p) for p in transpose_backward)
+    if len(crop) != 3 or len(full) != 3 or len(bbox) != 3:
+        raise RuntimeError(f"export: expected 3-D geometry, got crop {crop}, shape {full}, bbox {bbox}")
+    if logits.dim() != 1 + len(crop):
+        raise RuntimeError(f"export: logits of shape {tuple(logits.shape)} do not match the preprocessed (c, x, y, z) layout")
+    if any(len(b) != 2 or not 0 <= b[0] < b[1] <= s for b, s in zip(bbox, full)):
+        raise RuntimeError(f"export: bbox_used_for_cropping {bbox} is not inside shape_before_cropping {full}")
+    if tuple(b[1] - b[0] for b in bbox) != crop:
+        raise RuntimeError(f"export: shape_after_cropping_and_before_resampling {crop} differs from the extent of the bbox {bbox}")
+    if sorted(perm) != [0, 1, 2]:
+        raise RuntimeError(f"export: transpose_backward {perm} is not a permutation of (0, 1, 2)")
+    if logits.shape[0] > 256:
+        raise RuntimeError(f"export: {logits.shape[0]} classes do not fit the uint8 segmentation")
+    return crop, full, tuple(b[0] for b in bbox), perm
+
+
+def _finish(resampled, crop, full, lo, perm, return_probabilities):
+    """Softmax, argmax, paste and transpose of resampled logits (K, *crop), on their device (host path and K > 32)."""
+    probs = torch.softmax(resampled, 0)
+    sl = tuple(slice(a, a + c) for a, c in zip(lo, crop))
+    seg = torch.zeros(full, dtype=torch.uint8, device=resampled.device)
+    seg[sl] = probs.argmax(0).to(torch.uint8)
+    seg = seg.permute(perm).contiguous()
+    if not return_probabilities:
+        return seg, None
+    out = torch.zeros((probs.shape[0],) + full, dtype=torch.float32, device=resampled.device)
+    out[(slice(None),) + sl] = probs
+    return seg, out.permute((0,) + tuple(p + 1 for p in perm)).contiguous()
+
+
+def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties, configuration_spacing, transpose_backward=(0, 1, 2),
+                                                                 return_probabilities=False, order=1, order_z=0, force_separate_z=None):
+    """logits (K, x, y, z) in the preprocessed geometry (any strides) -> (segmentation uint8 in the original geometry, probabilities
+    (K, *original) fp32 or None), on the logits' device: export_prediction.py:28-63 with the default probability resampler.
+    properties: the preprocessing's dict (spacing, shape_before_cropping, bbox_used_for_cropping,
+    shape_after_cropping_and_before_resampling); configuration_spacing: the plan configuration's spacing (2 or 3 values)."""
+    logits = _as_logits(logits)
+    crop, full, lo, perm = _geometry(logits, properties, transpose_backward)
+    cur = current_spacing_for(configuration_spacing, properties)
+    kinds = resampling_plan(logits.shape[1:], crop, cur, [float(s) for s in properties["spacing"]], order, order_z, force_separate_z)
+    taps = build_taps(logits.shape[1:], crop, kinds)
+    if logits.is_cuda:
+        from . import ops
+        if logits.shape[0] <= ops.EXPORT_MAX_CLASSES:
+            return ops.export_segmentation(logits, taps, crop, lo, full, perm, return_probabilities)
+        resampled = logits if kinds is None else ops.resample_linear(logits, taps, crop)
+    else:
+        resampled = logits if kinds is None else _resample_host(logits, taps, crop)
+    return _finish(resampled, crop, full, lo, perm, return_probabilities)
+
+
+def export_prediction_from_softmax(predicted_array_or_file, properties_dict, configuration_manager, plans_manager,
+                                   dataset_json_dict_or_file, output_file_truncated, save_probabilities=False):
+    """Drop-in for the reference's export_prediction_from_softmax (export_prediction.py:10-69), same arguments and files.  The logits
+    are exported where they live: a device tensor through K21, a CPU tensor or numpy array (or a .npy / .npz file, removed after
+    loading) through the host path.  Duck-typed: configuration_manager.spacing, plans_manager.transpose_backward,
+    plans_manager.get_label_manager(dataset_json) (region-based managers raise NotImplementedError) and
+    plans_manager.image_reader_writer_class().write_seg(seg, file, properties)."""
+    if isinstance(predicted_array_or_file, str):
+        path = predicted_array_or_file
+        if path.endswith(".npy"):
+            predicted_array_or_file = np.load(path)
+        elif path.endswith(".npz"):
+            predicted_array_or_file = np.load(path)["softmax"]
+        else:
+            raise RuntimeError(f"export: {path} is neither a .npy nor a .npz file")
+        os.remove(path)
+    if isinstance(dataset_json_dict_or_file, str):
+        with open(dataset_json_dict_or_file) as f:
+            dataset_json_dict_or_file = json.load(f)
+    label_manager = plans_manager.get_label_manager(dataset_json_dict_or_file)
+    if getattr(label_manager, "has_regions", False):
+        raise NotImplementedError("region-based label managers (sigmoid / regions_class_order) are not supported by the export")
+    kwargs = dict(getattr(configuration_manager, "configuration", {}).get("resampling_fn_probabilities_kwargs", {}) or {})
+    if kwargs.pop("is_seg", False):
+        raise NotImplementedError("the probability resampler must not be a segmentation resampler")
+    kwargs = {k: kwargs[k] for k in ("order", "order_z", "force_separate_z") if k in kwargs}
+    seg, probs = convert_predicted_logits_to_segmentation_with_correct_shape(
+        predicted_array_or_file, properties_dict, configuration_manager.spacing, plans_manager.transpose_backward,
+        return_probabilities=save_probabilities, **kwargs)
+    if save_probabilities:
+        np.savez_compressed(output_file_truncated + ".npz", probabilities=probs.cpu().numpy())
+        with open(output_file_truncated + ".pkl", "wb") as f:
+            pickle.dump(properties_dict, f)
+        del probs
+    rw = plans_manager.image_reader_writer_class()
+    rw.write_seg(seg.cpu().numpy(), output_file_truncated + dataset_json_dict_or_file["file_ending"], properties_dict)

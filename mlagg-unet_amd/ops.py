@@ -3,6 +3,7 @@
 PyTorch is plumbing here: device memory, the current HIP stream and autograd bookkeeping.  Every
 op requires CUDA(HIP) fp32 tensors and raises RuntimeError otherwise -- there is no eager path.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -2788,3 +2789,74 @@ def sliding_window_finalize(acc, weight, region, return_labels=False):
     _lib.check(_lib.lib().mlagg_sw_finalize(_ptr(acc), _ptr(weight), K, *shape, *lo, *size, _ptr(logits), _ptr(labels), _stream()),
                "mlagg_sw_finalize")
     return logits, labels
+
+
+# ------------------------------------------------------------------------------------------------
+# K21: prediction export (csrc/export.hip).  The per-axis tap tables come from export._axis_taps as host numpy arrays
+# (idx (X' + Y' + Z', 2) int32, w (X' + Y' + Z', 2) float64); they are checked against the logits' extent here, on the host, before
+# the single upload of the call, so the kernels never read outside the logits.  No autograd: inference only.
+# ------------------------------------------------------------------------------------------------
+def _export_source(logits):
+    _require(logits, "logits")
+    if logits.dim() != 4 or min(logits.shape) < 1:
+        raise RuntimeError(f"logits: expected a non-empty (C, X, Y, Z) tensor, got shape {tuple(logits.shape)}")
+    if min(logits.stride()) < 0:
+        raise RuntimeError("logits: negative strides are not supported")
+    return tuple(int(s) for s in logits.shape), tuple(int(s) for s in logits.stride())
+
+
+def _export_taps(taps, in_shape, out_shape, device):
+    idx, w = (np.ascontiguousarray(a) for a in taps)
+    n = sum(out_shape)
+    if idx.dtype != np.int32 or w.dtype != np.float64 or idx.shape != (n, 2) or w.shape != (n, 2):
+        raise RuntimeError(f"tap tables: expected int32 / float64 ({n}, 2) arrays for output shape {tuple(out_shape)}")
+    lo = 0
+    for n_in, n_out in zip(in_shape, out_shape):
+        part = idx[lo:lo + n_out]
+        if part.min() < 0 or part.max() >= n_in:
+            raise RuntimeError(f"tap tables: an index outside [0, {n_in}) for an axis of {n_in} -> {n_out}")
+        lo += n_out
+    return torch.from_numpy(idx).to(device), torch.from_numpy(w).to(device)
+
+
+def resample_linear(logits, taps, out_shape):
+    """logits (C, X, Y, Z) fp32, any non-negative strides -> (C, *out_shape) contiguous fp32: out[c, o] = the separable blend of the
+    two taps of every axis at o (taps = export._axis_taps tables), in fp64, rounded once."""
+    shape, st = _export_source(logits)
+    out_shape = tuple(int(s) for s in out_shape)
+    if len(out_shape) != 3 or min(out_shape) < 1:
+        raise RuntimeError(f"resample_linear: output shape {out_shape}")
+    idx, w = _export_taps(taps, shape[1:], out_shape, logits.device)
+    out = torch.empty((shape[0],) + out_shape, device=logits.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mlagg_resample_linear(_ptr(logits), *shape, *st, _ptr(idx), _ptr(w), _ptr(out), *out_shape, _stream()),
+               "mlagg_resample_linear")
+    return out
+
+
+EXPORT_MAX_CLASSES = 32        # classes held in registers by the fused export kernel
+
+
+def export_segmentation(logits, taps, crop_shape, box_lo, shape_before_cropping, transpose_backward, return_probabilities=False):
+    """The fused export of K <= 32 classes: resample logits (K, X, Y, Z) to crop_shape with the tap tables, fp32 softmax over K,
+    first-maximum argmax, pasted at box_lo into shape_before_cropping (zeros outside) and transposed by transpose_backward.
+    Returns (labels uint8, probabilities (K, ...) fp32 or None), contiguous."""
+    shape, st = _export_source(logits)
+    K = shape[0]
+    if K > EXPORT_MAX_CLASSES:
+        raise RuntimeError(f"export_segmentation: {K} classes, the fused kernel holds at most {EXPORT_MAX_CLASSES}")
+    crop = tuple(int(s) for s in crop_shape)
+    lo = tuple(int(v) for v in box_lo)
+    full = tuple(int(s) for s in shape_before_cropping)
+    perm = tuple(int(p) for p in transpose_backward)
+    if len(crop) != 3 or len(lo) != 3 or len(full) != 3 or sorted(perm) != [0, 1, 2]:
+        raise RuntimeError(f"export_segmentation: crop {crop}, box {lo}, shape {full}, transpose {perm}")
+    if any(c < 1 or a < 0 or a + c > s for c, a, s in zip(crop, lo, full)):
+        raise RuntimeError(f"export_segmentation: a box of {crop} at {lo} is not inside {full}")
+    idx, w = _export_taps(taps, shape[1:], crop, logits.device)
+    out_shape = tuple(full[p] for p in perm)
+    labels = torch.empty(out_shape, device=logits.device, dtype=torch.uint8)
+    probs = torch.empty((K,) + out_shape, device=logits.device, dtype=torch.float32) if return_probabilities else None
+    _lib.check(_lib.lib().mlagg_export_segmentation(_ptr(logits), *shape, *st, _ptr(idx), _ptr(w), *crop, _int_array(lo),
+                                                    _int_array(full), _int_array(perm), _ptr(labels), _ptr(probs), _stream()),
+               "mlagg_export_segmentation")
+    return labels, probs
