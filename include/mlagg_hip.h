@@ -713,6 +713,57 @@ int mlagg_export_segmentation(const float *logits, int K, int X, int Y, int Z, l
                               const int *tap_idx, const double *tap_w, int Xc, int Yc, int Zc, const int *box_lo, const int *shape,
                               const int *perm, unsigned char *labels, float *probs, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K22: case preprocessing on the device (reference nnunetv2/preprocessing/preprocessors/default_preprocessor.py:38-124 for a
+ * test case: crop to non-zero (preprocessing/cropping/cropping.py), normalise (normalization/default_normalization_schemes.py),
+ * resample_data_or_seg_to_shape(order=3, order_z=0 | 1) (resampling/default_resampling.py:76-200)).  The raw input is
+ * (C, X, Y, Z) fp32 with element strides (sc, sx, sy, sz) >= 0 (the transpose_forward view); lo / ext are HOST arrays of 3:
+ * the crop window's lower corner and extent.
+ *   nonzero_box:     box (6 ints, DEVICE) = min x, y, z and max x, y, z of the voxels != 0 in any channel ((INT_MAX, -1) when
+ *                    there are none).  Integer atomics: deterministic.
+ *   channel_stats:   channel c of the window (voxels with mask != 0 for MLAGG_PP_ZSCORE_MASKED; mask (ext) uint8, contiguous):
+ *                    stats[c * 4 .. + 3] = fp64 mean, std, min, max; for ZScore params[c * 4 + 2 | 3] = fp32 mean and
+ *                    max(std, 1e-8), for RescaleTo01 params[c * 4 + 0 | 3] = min and max(max - min, 1e-8).  partials:
+ *                    C * MLAGG_PP_STATS_PARTIALS * 5 doubles of workspace.  Fixed summation order: bit-reproducible.
+ *   normalize:       out (C, ext) contiguous fp32 = scheme schemes[c] (DEVICE int array of C) of the window in fp32, with
+ *                    params[c * 4 ..] (DEVICE): CT (lo, hi, mean, den) = (clip(x, lo, hi) - mean) / den; ZScore (.., .., mean, den);
+ *                    masked ZScore the same where mask != 0, x elsewhere; RescaleTo01 (min, .., .., den); RGBTo01 x / 255.
+ *   clip_ranges:     lo / hi (C * D ordered-int encoded fp32) = min / max of x (C, X, Y, Z) contiguous per channel (axis -1,
+ *                    D = 1) or per channel and slice along axis (D = its extent): the ranges skimage's resize clips to.
+ *   cubic_axis:      one axis of ndi.zoom(order=3, mode='nearest', grid_mode=True) in fp64 on (outer, n_in, inner) contiguous
+ *                    fp32 | fp64 -> (outer, n_out, inner) fp32 | fp64: out[o] = sum_k w[4 o + k] * coef[start[o] + k], where coef
+ *                    is the line edge-padded by 12, prefiltered by the HOST array fir[0..30] (h[|k|]) with the reflect boundary; start / w are
+ *                    DEVICE tables, every start[o] in [P0, P0 + M - 4], P0 + M <= n_in + 24; clip_lo / clip_hi (clip_ranges
+ *                    output or NULL) clip the output element f to domain (f / clip_cstride) * clip_D + (f / clip_dstride) % clip_D.
+ *                    Lines longer than the LDS plan allows (mlagg_pp_cubic_lines_per_block == 0) are MLAGG_E_UNSUPPORTED.
+ *   gather_axis:     (outer, n_in, inner) fp64 -> (outer, n_out, inner) fp32: in[idx[2 o]] * w[2 o] + in[idx[2 o + 1]] * w[2 o + 1]
+ *                    (export._axis_taps tables, DEVICE): map_coordinates(order=0 | 1, mode='nearest') along the low-resolution
+ *                    axis of separate-z resampling (:172-184).
+ * All volume offsets are 64-bit.
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_PP_NONE          0
+#define MLAGG_PP_CT            1
+#define MLAGG_PP_ZSCORE        2
+#define MLAGG_PP_ZSCORE_MASKED 3
+#define MLAGG_PP_RESCALE01     4
+#define MLAGG_PP_RGB01         5
+#define MLAGG_PP_STATS_PARTIALS 256
+int mlagg_pp_nonzero_box(const float *in, int C, int X, int Y, int Z, long long sc, long long sx, long long sy, long long sz, int *box,
+                         void *stream);
+int mlagg_pp_channel_stats(const float *in, int C, int X, int Y, int Z, long long sc, long long sx, long long sy, long long sz,
+                           const int *lo, const int *ext, int c, int scheme, const unsigned char *mask, double *partials,
+                           float *params, double *stats, void *stream);
+int mlagg_pp_normalize(const float *in, int C, int X, int Y, int Z, long long sc, long long sx, long long sy, long long sz,
+                       const int *lo, const int *ext, const int *schemes, const float *params, const unsigned char *mask, float *out,
+                       void *stream);
+int mlagg_pp_clip_ranges(const float *x, int C, int X, int Y, int Z, int axis, unsigned *lo, unsigned *hi, void *stream);
+int mlagg_pp_cubic_lines_per_block(int n_in, int M);
+int mlagg_pp_cubic_axis(const void *in, int in_f64, void *out, int out_f64, long long outer, int n_in, long long inner, int n_out,
+                        const int *start, const double *w, int P0, int M, const double *fir, const unsigned *clip_lo,
+                        const unsigned *clip_hi, long long clip_cstride, long long clip_dstride, int clip_D, void *stream);
+int mlagg_pp_gather_axis(const double *in, float *out, long long outer, int n_in, long long inner, int n_out, const int *idx,
+                         const double *w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,14 @@ SIGNATURES = {
     "mlagg_resample_linear": (_I, [_F] + [_I] * 4 + [ctypes.c_longlong] * 4 + [_F, _F, _F] + [_I] * 3 + [_S]),
     "mlagg_export_segmentation": (_I, [_F] + [_I] * 4 + [ctypes.c_longlong] * 4 + [_F, _F] + [_I] * 3
                                   + [ctypes.POINTER(_I)] * 3 + [_F, _F, _S]),
+    "mlagg_pp_nonzero_box": (_I, [_F] + [_I] * 4 + [ctypes.c_longlong] * 4 + [_F, _S]),
+    "mlagg_pp_channel_stats": (_I, [_F] + [_I] * 4 + [ctypes.c_longlong] * 4 + [ctypes.POINTER(_I)] * 2 + [_I, _I, _F, _F, _F, _F, _S]),
+    "mlagg_pp_normalize": (_I, [_F] + [_I] * 4 + [ctypes.c_longlong] * 4 + [ctypes.POINTER(_I)] * 2 + [_F, _F, _F, _F, _S]),
+    "mlagg_pp_clip_ranges": (_I, [_F] + [_I] * 5 + [_F, _F, _S]),
+    "mlagg_pp_cubic_lines_per_block": (_I, [_I, _I]),
+    "mlagg_pp_cubic_axis": (_I, [_F, _I, _F, _I, ctypes.c_longlong, _I, ctypes.c_longlong, _I, _F, _F, _I, _I, _F, _F, _F,
+                                 ctypes.c_longlong, ctypes.c_longlong, _I, _S]),
+    "mlagg_pp_gather_axis": (_I, [_F, _F, ctypes.c_longlong, _I, ctypes.c_longlong, _I, _F, _F, _S]),
     "mlagg_selscan1_chunk": (_I, [_I, _I, _I]),
     "mlagg_selscan1_state_floats": (_SZ, [_I, _I, _I, _I]),
     "mlagg_selscan1_fwd": (_I, [_F, ctypes.c_long] + [_F] * 5 + [_I] + [_F] * 5 + [_I] * 4 + [_S]),

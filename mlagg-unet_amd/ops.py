@@ -2860,3 +2860,154 @@ def export_segmentation(logits, taps, crop_shape, box_lo, shape_before_cropping,
                                                     _int_array(full), _int_array(perm), _ptr(labels), _ptr(probs), _stream()),
                "mlagg_export_segmentation")
     return labels, probs
+
+
+# ------------------------------------------------------------------------------------------------
+# K22: case preprocessing (csrc/preprocess.hip).  The cubic tap tables come from preprocessing._cubic_taps and the order-0 / order-1
+# tables from export._axis_taps, as host numpy arrays; they are checked here, on the host, before their upload, so the kernels never
+# read outside a line.  No autograd: inference only.
+# ------------------------------------------------------------------------------------------------
+PP_SCHEMES = {"NoNormalization": 0, "CTNormalization": 1, "ZScoreNormalization": 2, "ZScoreNormalization+mask": 3,
+              "RescaleTo01Normalization": 4, "RGBTo01Normalization": 5}
+PP_STATS_PARTIALS = 256        # MLAGG_PP_STATS_PARTIALS
+
+
+def _pp_source(x):
+    _require(x, "image")
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise RuntimeError(f"image: expected a non-empty (C, X, Y, Z) tensor, got shape {tuple(x.shape)}")
+    if min(x.stride()) < 0:
+        raise RuntimeError("image: negative strides are not supported")
+    return tuple(int(s) for s in x.shape), tuple(int(s) for s in x.stride())
+
+
+def _pp_window(shape, lo, ext):
+    lo, ext = tuple(int(v) for v in lo), tuple(int(v) for v in ext)
+    if len(lo) != 3 or len(ext) != 3 or any(a < 0 or e < 1 or a + e > s for a, e, s in zip(lo, ext, shape[1:])):
+        raise RuntimeError(f"crop window of {ext} at {lo} is not inside {tuple(shape[1:])}")
+    return lo, ext
+
+
+def pp_nonzero_box(x):
+    """x (C, X, Y, Z) fp32, any non-negative strides -> int32 device tensor (6,): min x, y, z and max x, y, z of the voxels that are
+    non-zero in any channel; (2^31 - 1, -1) per axis when there are none."""
+    shape, st = _pp_source(x)
+    box = torch.empty(6, dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().mlagg_pp_nonzero_box(_ptr(x), *shape, *st, _ptr(box), _stream()), "mlagg_pp_nonzero_box")
+    return box
+
+
+def pp_channel_stats(x, lo, ext, c, scheme, params, stats, mask=None):
+    """Channel c of x's crop window (under mask, (ext) uint8, for the masked ZScore): fills stats[c] = fp64 (mean, std, min, max) and
+    the scheme's fp32 constants in params[c] (see mlagg_pp_channel_stats)."""
+    shape, st = _pp_source(x)
+    lo, ext = _pp_window(shape, lo, ext)
+    if not 0 <= c < shape[0] or scheme not in PP_SCHEMES.values():
+        raise RuntimeError(f"pp_channel_stats: channel {c} of {shape[0]}, scheme {scheme}")
+    if params.dtype != torch.float32 or params.shape != (shape[0], 4) or not params.is_contiguous():
+        raise RuntimeError("pp_channel_stats: params must be a contiguous (C, 4) fp32 tensor")
+    if stats.dtype != torch.float64 or stats.shape != (shape[0], 4) or not stats.is_contiguous():
+        raise RuntimeError("pp_channel_stats: stats must be a contiguous (C, 4) fp64 tensor")
+    if scheme == PP_SCHEMES["ZScoreNormalization+mask"]:
+        if mask is None or mask.dtype != torch.uint8 or tuple(mask.shape) != ext or not mask.is_contiguous():
+            raise RuntimeError(f"pp_channel_stats: the masked ZScore needs a contiguous uint8 mask of shape {ext}")
+    partials = torch.empty(shape[0] * PP_STATS_PARTIALS * 5, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().mlagg_pp_channel_stats(_ptr(x), *shape, *st, _int_array(lo), _int_array(ext), int(c), int(scheme), _ptr(mask),
+                                                 _ptr(partials), _ptr(params), _ptr(stats), _stream()), "mlagg_pp_channel_stats")
+
+
+def pp_normalize(x, lo, ext, schemes, params, mask=None):
+    """Crop x to the window and normalise every channel with its scheme code (PP_SCHEMES) in fp32 -> (C, *ext) contiguous fp32.
+    schemes: int32 device tensor (C,); params: fp32 device tensor (C, 4); mask: (ext) uint8 for the masked ZScore."""
+    shape, st = _pp_source(x)
+    lo, ext = _pp_window(shape, lo, ext)
+    if schemes.dtype != torch.int32 or tuple(schemes.shape) != (shape[0],) or params.dtype != torch.float32 \
+            or tuple(params.shape) != (shape[0], 4) or not params.is_contiguous():
+        raise RuntimeError("pp_normalize: schemes (C,) int32 and params (C, 4) fp32 device tensors")
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != ext or not mask.is_contiguous()):
+        raise RuntimeError(f"pp_normalize: mask must be a contiguous uint8 tensor of shape {ext}")
+    if mask is None and bool((schemes == PP_SCHEMES["ZScoreNormalization+mask"]).any()):
+        raise RuntimeError("pp_normalize: the masked ZScore needs a mask")
+    out = torch.empty((shape[0],) + ext, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().mlagg_pp_normalize(_ptr(x), *shape, *st, _int_array(lo), _int_array(ext), _ptr(schemes), _ptr(params),
+                                             _ptr(mask), _ptr(out), _stream()), "mlagg_pp_normalize")
+    return out
+
+
+def pp_clip_ranges(x, axis=None):
+    """x (C, X, Y, Z) contiguous fp32 -> (lo, hi) int32 device tensors (C * D,) of ordered-int encoded min / max: per channel
+    (axis None, D = 1) or per channel and slice along spatial axis `axis` (D = its extent)."""
+    shape, _ = _pp_source(x)
+    if not x.is_contiguous():
+        raise RuntimeError("pp_clip_ranges: x must be contiguous")
+    D = 1 if axis is None else shape[1 + int(axis)]
+    lo = torch.empty(shape[0] * D, dtype=torch.int32, device=x.device)
+    hi = torch.empty_like(lo)
+    _lib.check(_lib.lib().mlagg_pp_clip_ranges(_ptr(x), *shape, -1 if axis is None else int(axis), _ptr(lo), _ptr(hi), _stream()),
+               "mlagg_pp_clip_ranges")
+    return lo, hi
+
+
+def _line_geometry(x, axis):
+    if x.dim() != 4 or not x.is_contiguous() or not x.is_cuda or not 0 <= axis <= 2:
+        raise RuntimeError(f"expected a contiguous (C, X, Y, Z) device tensor and a spatial axis, got {tuple(x.shape)}, axis {axis}")
+    shape = tuple(int(s) for s in x.shape)
+    outer = int(np.prod(shape[:1 + axis]))
+    inner = int(np.prod(shape[2 + axis:]))
+    return shape, outer, shape[1 + axis], inner
+
+
+def pp_cubic_axis(x, axis, taps, fir, out_dtype=torch.float64, clip=None):
+    """One axis of the cubic zoom: x (C, X, Y, Z) contiguous fp32 | fp64 -> the same with `axis` resampled by taps =
+    preprocessing._cubic_taps(n_in, n_out) (start, w, P0, M), fir: the 31 prefilter taps.  clip = (lo, hi, D, domain axis or None):
+    pp_clip_ranges output for the output's domains."""
+    if x.dtype not in (torch.float32, torch.float64) or out_dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"pp_cubic_axis: fp32 / fp64 only, got {x.dtype} -> {out_dtype}")
+    shape, outer, n_in, inner = _line_geometry(x, axis)
+    start, w, P0, M = taps
+    start, w = np.ascontiguousarray(start, dtype=np.int32), np.ascontiguousarray(w, dtype=np.float64)
+    n_out = start.shape[0]
+    if n_out < 1 or w.shape != (n_out, 4) or start.min() < P0 or start.max() + 4 > P0 + M or P0 < 0 or P0 + M > n_in + 24:
+        raise RuntimeError(f"pp_cubic_axis: tap table does not fit a line of {n_in}")
+    if _lib.lib().mlagg_pp_cubic_lines_per_block(n_in, int(M)) < 1:
+        raise RuntimeError(f"pp_cubic_axis: a line of {n_in} -> {n_out} samples does not fit the kernel's LDS plan")
+    fir = torch.as_tensor(np.ascontiguousarray(fir, dtype=np.float64))
+    if fir.shape != (31,):
+        raise RuntimeError("pp_cubic_axis: 31 prefilter taps expected")
+    out_shape = list(shape)
+    out_shape[1 + axis] = n_out
+    out = torch.empty(out_shape, dtype=out_dtype, device=x.device)
+    d_start, d_w = torch.from_numpy(start).to(x.device), torch.from_numpy(w).to(x.device)
+    clo = chi = None
+    cstride = dstride = D = 1
+    if clip is not None:
+        clo, chi, D, dax = clip
+        V = int(np.prod(out_shape[1:]))
+        cstride = V
+        dstride = V if dax is None else int(np.prod(out_shape[2 + dax:]))
+        if D != (1 if dax is None else out_shape[1 + dax]) or clo.numel() != shape[0] * D or chi.numel() != shape[0] * D:
+            raise RuntimeError("pp_cubic_axis: clip ranges do not match the output's domains")
+    _lib.check(_lib.lib().mlagg_pp_cubic_axis(_ptr(x), int(x.dtype == torch.float64), _ptr(out), int(out_dtype == torch.float64),
+                                              outer, n_in, inner, n_out, _ptr(d_start), _ptr(d_w), int(P0), int(M), fir.data_ptr(),
+                                              _ptr(clo), _ptr(chi), cstride, dstride, int(D), _stream()), "mlagg_pp_cubic_axis")
+    return out
+
+
+def pp_gather_axis(x, axis, taps):
+    """x (C, X, Y, Z) contiguous fp64 -> fp32 with `axis` resampled by an export._axis_taps table (order 0 or 1)."""
+    if x.dtype != torch.float64:
+        raise RuntimeError(f"pp_gather_axis: fp64 input expected, got {x.dtype}")
+    shape, outer, n_in, inner = _line_geometry(x, axis)
+    idx, w = (np.ascontiguousarray(a) for a in taps)
+    n_out = idx.shape[0]
+    if idx.dtype != np.int32 or w.dtype != np.float64 or idx.shape != (n_out, 2) or w.shape != (n_out, 2) or n_out < 1:
+        raise RuntimeError("pp_gather_axis: int32 / float64 (n_out, 2) tables expected")
+    if idx.min() < 0 or idx.max() >= n_in:
+        raise RuntimeError(f"pp_gather_axis: an index outside [0, {n_in})")
+    out_shape = list(shape)
+    out_shape[1 + axis] = n_out
+    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    d_idx, d_w = torch.from_numpy(idx).to(x.device), torch.from_numpy(w).to(x.device)
+    _lib.check(_lib.lib().mlagg_pp_gather_axis(_ptr(x), _ptr(out), outer, n_in, inner, n_out, _ptr(d_idx), _ptr(d_w), _stream()),
+               "mlagg_pp_gather_axis")
+    return out

@@ -1,0 +1,52 @@
+"""Prediction of one raw case: the reference's nnUNetPredictor per case
+(mlagg/nnunetv2/inference/predict_from_raw_data.py:30-67 preprocessing, :263-288 the fold ensemble, then export_prediction.py), as
+one chain of this package's functions:
+
+    preprocessing.preprocess_case -> inference.predict_sliding_window_return_logits (2-D or 3-D tiles, from the configuration's
+    patch_size) -> export.convert_predicted_logits_to_segmentation_with_correct_shape
+
+On a CUDA device every step runs on the device (K22, the sliding window with K20 for 3-D tiles, K21); the only read-back on the way
+is K22's crop box.  The result is a uint8 label volume in the original geometry, which evaluation.abdomen_case_dsc scores directly.
+"""
+import torch
+
+from . import export, inference, preprocessing
+
+
+def _num_segmentation_heads(dataset_json):
+    labels = dataset_json["labels"]
+    if "regions_class_order" in dataset_json or any(isinstance(v, (list, tuple)) and len(v) > 1 for v in labels.values()):
+        raise NotImplementedError("region-based label managers are not supported")
+    values = sorted({int(v[0] if isinstance(v, (list, tuple)) else v) for v in labels.values()})
+    if "ignore" in labels:                               # the ignore label is not a segmentation head (label_handling.py)
+        values.remove(int(labels["ignore"]))
+    return len(values)
+
+
+@torch.no_grad()
+def predict_case(network, image, properties, plans, configuration_name, dataset_json, *, parameters=None, mirror_axes=None,
+                 tile_step_size=0.5, use_gaussian=True, tile_batch=None, return_probabilities=False, device=None):
+    """image (c, x, y, z) raw intensities and the reader's properties -> (segmentation uint8 in the original geometry, probabilities
+    (K, ...) fp32 or None), on `device` (default: the network's).  parameters: optional list of state dicts (folds), each loaded
+    with inference.load_inference_weights; their logits are summed in fp32 and divided by their count.  mirror_axes: the
+    reference's inference_allowed_mirroring_axes (None: no test-time mirroring)."""
+    device = torch.device(device) if device is not None else next(network.parameters()).device
+    K = _num_segmentation_heads(dataset_json)
+    cfg = preprocessing.get_configuration(plans, configuration_name)
+    data, props = preprocessing.preprocess_case(image, properties, plans, configuration_name, device=device)
+    data = torch.as_tensor(data).to(device)
+    tile = tuple(int(s) for s in cfg["patch_size"])
+    if len(tile) not in (2, 3):
+        raise RuntimeError(f"patch_size {tile}: 2-D or 3-D tiles expected")
+    logits = None
+    for sd in (parameters if parameters is not None else [None]):
+        if sd is not None:
+            inference.load_inference_weights(network, sd)
+        out = inference.predict_sliding_window_return_logits(network, data, K, tile, mirror_axes=mirror_axes,
+                                                             tile_step_size=tile_step_size, use_gaussian=use_gaussian,
+                                                             tile_batch=tile_batch, device=device)
+        logits = out if logits is None else logits + out
+    if parameters is not None and len(parameters) > 1:
+        logits = logits / len(parameters)
+    return export.convert_predicted_logits_to_segmentation_with_correct_shape(
+        logits, props, cfg["spacing"], plans.get("transpose_backward", [0, 1, 2]), return_probabilities=return_probabilities)
