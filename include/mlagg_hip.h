@@ -764,6 +764,21 @@ int mlagg_pp_cubic_axis(const void *in, int in_f64, void *out, int out_f64, long
 int mlagg_pp_gather_axis(const double *in, float *out, long long outer, int n_in, long long inner, int n_out, const int *idx,
                          const double *w, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K23: keep the largest connected component (reference nnunetv2/postprocessing/remove_connected_components.py:22-34,
+ * remove_all_but_largest_component_from_segmentation, with acvl_utils' remove_all_but_largest_component: full connectivity, every
+ * component of the maximal size kept).  labels (X, Y, Z) contiguous uint8, X * Y * Z <= 2^31 - 1 (else MLAGG_E_UNSUPPORTED before
+ * any launch), 4-byte aligned; group (256) uint8 DEVICE table: group[label] = 0 outside every mask, else the voxel's group.  Two
+ * voxels are connected when they are 26-neighbours with the same non-zero group: all listed labels -> 1 is the reference's
+ * united mask (foreground or a region); label -> label labels every class at once.
+ *   out (X, Y, Z) uint8 (4-byte aligned) = background_label (0..255) where group != 0 and the voxel's component is smaller than
+ *   the largest of its group; labels elsewhere.  parent, size: X * Y * Z int32 each of workspace.  stats (3 * 256 int32, DEVICE)
+ *   = per group: voxel count, largest component size, voxels kept (slot 0 unused).
+ * Six launches, integer atomics only: the result does not depend on the schedule.
+ * ------------------------------------------------------------------------------------------ */
+int mlagg_keep_largest_component(const unsigned char *labels, int X, int Y, int Z, const unsigned char *group, int background_label,
+                                 int *parent, int *size, int *stats, unsigned char *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,7 @@ SIGNATURES = {
     "mlagg_pp_cubic_axis": (_I, [_F, _I, _F, _I, ctypes.c_longlong, _I, ctypes.c_longlong, _I, _F, _F, _I, _I, _F, _F, _F,
                                  ctypes.c_longlong, ctypes.c_longlong, _I, _S]),
     "mlagg_pp_gather_axis": (_I, [_F, _F, ctypes.c_longlong, _I, ctypes.c_longlong, _I, _F, _F, _S]),
+    "mlagg_keep_largest_component": (_I, [_F, _I, _I, _I, _F, _I, _F, _F, _F, _F, _S]),
     "mlagg_selscan1_chunk": (_I, [_I, _I, _I]),
     "mlagg_selscan1_state_floats": (_SZ, [_I, _I, _I, _I]),
     "mlagg_selscan1_fwd": (_I, [_F, ctypes.c_long] + [_F] * 5 + [_I] + [_F] * 5 + [_I] * 4 + [_S]),

@@ -3011,3 +3011,42 @@ def pp_gather_axis(x, axis, taps):
     _lib.check(_lib.lib().mlagg_pp_gather_axis(_ptr(x), _ptr(out), outer, n_in, inner, n_out, _ptr(d_idx), _ptr(d_w), _stream()),
                "mlagg_pp_gather_axis")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# K23: keep the largest connected component (csrc/components.hip).  The group table maps each label to its mask's group (0: not
+# in any mask); postprocessing.py builds it.  Inference only.
+# ------------------------------------------------------------------------------------------------
+CC_MAX_VOXELS = 2 ** 31 - 1
+
+
+def keep_largest_component(labels, group, background_label=0):
+    """labels (X, Y, Z) contiguous uint8 on the device, group (256,) uint8 on the same device -> (out (X, Y, Z) uint8, stats (3, 256)
+    int32 device tensor: per group the voxel count, the largest component's size and the voxels kept).  Voxels of a non-zero group
+    whose 26-connected same-group component is smaller than the group's largest become background_label; ties are all kept."""
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.uint8 and labels.dim() == 3):
+        raise RuntimeError(f"labels: expected a 3-D uint8 tensor on the MI355X device, got "
+                           f"{getattr(labels, 'dtype', type(labels))} {tuple(getattr(labels, 'shape', ()))} "
+                           f"on {getattr(labels, 'device', '?')}")
+    if labels.numel() > CC_MAX_VOXELS:
+        raise RuntimeError(f"keep_largest_component: {labels.numel()} voxels, at most {CC_MAX_VOXELS} are supported")
+    if min(labels.shape) < 1:
+        raise RuntimeError(f"keep_largest_component: empty volume {tuple(labels.shape)}")
+    if not labels.is_contiguous():
+        raise RuntimeError("labels: expected a contiguous tensor")
+    if not (isinstance(group, torch.Tensor) and group.dtype == torch.uint8 and tuple(group.shape) == (256,)
+            and group.device == labels.device and group.is_contiguous()):
+        raise RuntimeError("group: expected a contiguous (256,) uint8 tensor on the labels' device")
+    if not 0 <= int(background_label) <= 255:
+        raise RuntimeError(f"background_label {background_label}: a uint8 label expected")
+    if labels.data_ptr() % 4:
+        labels = labels.clone()                       # the kernels read four labels per dword
+    n = labels.numel()
+    parent = torch.empty(n, dtype=torch.int32, device=labels.device)
+    size = torch.empty(n, dtype=torch.int32, device=labels.device)
+    stats = torch.empty((3, 256), dtype=torch.int32, device=labels.device)
+    out = torch.empty_like(labels)
+    _lib.check(_lib.lib().mlagg_keep_largest_component(_ptr(labels), *labels.shape, _ptr(group), int(background_label), _ptr(parent),
+                                                       _ptr(size), _ptr(stats), _ptr(out), _stream()),
+               "mlagg_keep_largest_component")
+    return out, stats

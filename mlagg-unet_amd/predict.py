@@ -10,7 +10,7 @@ is K22's crop box.  The result is a uint8 label volume in the original geometry,
 """
 import torch
 
-from . import export, inference, preprocessing
+from . import export, inference, postprocessing as pp, preprocessing
 
 
 def _num_segmentation_heads(dataset_json):
@@ -25,11 +25,14 @@ def _num_segmentation_heads(dataset_json):
 
 @torch.no_grad()
 def predict_case(network, image, properties, plans, configuration_name, dataset_json, *, parameters=None, mirror_axes=None,
-                 tile_step_size=0.5, use_gaussian=True, tile_batch=None, return_probabilities=False, device=None):
+                 tile_step_size=0.5, use_gaussian=True, tile_batch=None, return_probabilities=False, device=None,
+                 postprocessing=None):
     """image (c, x, y, z) raw intensities and the reader's properties -> (segmentation uint8 in the original geometry, probabilities
     (K, ...) fp32 or None), on `device` (default: the network's).  parameters: optional list of state dicts (folds), each loaded
     with inference.load_inference_weights; their logits are summed in fp32 and divided by their count.  mirror_axes: the
-    reference's inference_allowed_mirroring_axes (None: no test-time mirroring)."""
+    reference's inference_allowed_mirroring_axes (None: no test-time mirroring).  postprocessing: (pp_fns, pp_fn_kwargs), e.g. from
+    postprocessing.determine_postprocessing or postprocessing_from_json, applied to the exported labels (K23 on the device); the
+    probabilities are returned as exported."""
     device = torch.device(device) if device is not None else next(network.parameters()).device
     K = _num_segmentation_heads(dataset_json)
     cfg = preprocessing.get_configuration(plans, configuration_name)
@@ -48,5 +51,8 @@ def predict_case(network, image, properties, plans, configuration_name, dataset_
         logits = out if logits is None else logits + out
     if parameters is not None and len(parameters) > 1:
         logits = logits / len(parameters)
-    return export.convert_predicted_logits_to_segmentation_with_correct_shape(
+    seg, probs = export.convert_predicted_logits_to_segmentation_with_correct_shape(
         logits, props, cfg["spacing"], plans.get("transpose_backward", [0, 1, 2]), return_probabilities=return_probabilities)
+    if postprocessing is not None:
+        seg = pp.apply_postprocessing(seg, *postprocessing)
+    return seg, probs
