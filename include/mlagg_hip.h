@@ -779,6 +779,44 @@ int mlagg_pp_gather_axis(const double *in, float *out, long long outer, int n_in
 int mlagg_keep_largest_component(const unsigned char *labels, int X, int Y, int Z, const unsigned char *group, int background_label,
                                  int *parent, int *size, int *stats, unsigned char *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K24: normalized surface Dice (reference evaluation/SurfaceDice.py:280-425 compute_surface_distances, :470-479
+ * compute_surface_dice_at_tolerance, and the per-organ loops of evaluation/{abdomen,BTCV,ACDC,endoscopy}_NSD_Eval.py :90-110).
+ * gt, pred (X, Y, Z) contiguous uint8 label volumes indexed [x, y, z].  Three calls per case, two small read-backs by the caller:
+ *
+ * mlagg_surface_stats: wanted (256) uint8 DEVICE table (1 for the labels to measure, label 0 never); stats (256 x 10 int32, DEVICE)
+ *   per label value l: stats[10 l + 0..9] = gt voxels, prediction voxels, union box x min / max, y min / max, z min / max (min
+ *   INT_MAX and max -1 when empty), gt z min / max.  One pass over both volumes (per-block LDS partials, one atomic per block).
+ *
+ * mlagg_surface_prepare: desc (n_labels x 16 int64, DEVICE), per label: label, crop origin o0..o2 in the volume, mask extents n0..n2
+ *   (the union box, a slab label's cut to the gt's [z_lower, z_upper) included), then the exclusive prefix offsets of the crop
+ *   voxels (D0 D1 D2, D = n + 1: the reference's zero plane on the high side), of the z lines (D0 D1), the y lines (D0 D2) and the
+ *   x lines (D1 D2), and of the (distance, area) pairs of the gt and the prediction surfels (used by mlagg_surface_reduce when it
+ *   compacts).  total / zlines / ylines: the sums; max_crop: the largest crop's voxel count.  Every crop <= 2^31 - 1 voxels and
+ *   every D <= MLAGG_SURFACE_MAX_LINE (nmax_y: the largest D1), else MLAGG_E_UNSUPPORTED before any launch.
+ *   codes (2 x total uint8) = the 2x2x2 neighbour codes of the gt, then of the prediction; ft (2 x total int32) = the exact
+ *   feature transform of each surfel set after the z and y passes (packed fy * D2 + fz of the nearest feature in the x plane, -1
+ *   where that plane has none); counts (n_labels x 2 int32) = surfels of the gt and the prediction.  s1, s2: spacing (mm).
+ *
+ * mlagg_surface_reduce: the x pass at the other mask's surfels.  tol (n_labels float64, DEVICE), area (256 float64, DEVICE: the
+ *   surfel area of every code at this spacing).  partial: 4 x xlines float64 of workspace.  sums (n_labels x 4 float64) = gt surfel
+ *   area, gt area within tol of the prediction's surface, prediction surfel area, prediction area within tol of the gt's surface,
+ *   each a fixed-order sum (bit-identical on a repeated call).  pairs (optional, NULL: off): (distance, area) float64 pairs of every
+ *   surfel at desc's pair offsets, in no particular order (pair_count: n_labels x 2 int32 of workspace).  Distance +inf where the
+ *   other mask has no surfel.  Inference only: no graph capture.
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_SURFACE_STATS_PER_LABEL 10
+#define MLAGG_SURFACE_DESC_FIELDS 16
+#define MLAGG_SURFACE_MAX_LINE 2560
+int mlagg_surface_stats(const unsigned char *gt, const unsigned char *pred, int X, int Y, int Z, const unsigned char *wanted,
+                        int *stats, void *stream);
+int mlagg_surface_prepare(const unsigned char *gt, const unsigned char *pred, int X, int Y, int Z, const long long *desc, int n_labels,
+                          long long total, long long max_crop, long long zlines, long long ylines, int nmax_y, double s1, double s2, unsigned char *codes,
+                          int *ft, int *counts, void *stream);
+int mlagg_surface_reduce(const unsigned char *codes, const int *ft, const long long *desc, int n_labels, long long total,
+                         long long xlines, int nmax_x, const double *tol, const double *area, double s0, double s1, double s2,
+                         double *partial, double *sums, double *pairs, int *pair_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,11 @@ SIGNATURES = {
                                  ctypes.c_longlong, ctypes.c_longlong, _I, _S]),
     "mlagg_pp_gather_axis": (_I, [_F, _F, ctypes.c_longlong, _I, ctypes.c_longlong, _I, _F, _F, _S]),
     "mlagg_keep_largest_component": (_I, [_F, _I, _I, _I, _F, _I, _F, _F, _F, _F, _S]),
+    "mlagg_surface_stats": (_I, [_F, _F, _I, _I, _I, _F, _F, _S]),
+    "mlagg_surface_prepare": (_I, [_F, _F, _I, _I, _I, _F, _I] + [ctypes.c_longlong] * 4 + [_I, ctypes.c_double, ctypes.c_double,
+                                                                                           _F, _F, _F, _S]),
+    "mlagg_surface_reduce": (_I, [_F, _F, _F, _I, ctypes.c_longlong, ctypes.c_longlong, _I, _F, _F] + [ctypes.c_double] * 3
+                             + [_F] * 4 + [_S]),
     "mlagg_selscan1_chunk": (_I, [_I, _I, _I]),
     "mlagg_selscan1_state_floats": (_SZ, [_I, _I, _I, _I]),
     "mlagg_selscan1_fwd": (_I, [_F, ctypes.c_long] + [_F] * 5 + [_I] + [_F] * 5 + [_I] * 4 + [_S]),

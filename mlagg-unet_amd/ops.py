@@ -3050,3 +3050,82 @@ def keep_largest_component(labels, group, background_label=0):
                                                        _ptr(size), _ptr(stats), _ptr(out), _stream()),
                "mlagg_keep_largest_component")
     return out, stats
+
+
+# ------------------------------------------------------------------------------------------------
+# K24: normalized surface Dice (csrc/surface.hip).  surface.py lays out the crops (desc) from the statistics and builds the surfel
+# area table.  Inference only.
+# ------------------------------------------------------------------------------------------------
+SURFACE_MAX_VOXELS = 2 ** 31 - 1
+SURFACE_MAX_LINE = 2560                         # MLAGG_SURFACE_MAX_LINE: the longest crop axis (LDS envelope of one line)
+SURFACE_DESC_FIELDS = 16
+
+
+def _require_labels(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.is_contiguous()):
+        raise RuntimeError(f"{name}: expected a contiguous 3-D uint8 tensor on the MI355X device, got "
+                           f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', '?')}")
+
+
+def surface_stats(gt, pred, wanted):
+    """gt, pred (X, Y, Z) uint8 label volumes on the device, wanted (256,) uint8 on the same device -> (256, 10) int32 device tensor:
+    per label value the gt and prediction voxel counts, the union box (x, y, z min / max) and the gt's z min / max."""
+    _require_labels(gt, "gt")
+    _require_labels(pred, "pred")
+    if gt.shape != pred.shape or gt.device != pred.device:
+        raise RuntimeError(f"gt {tuple(gt.shape)} and pred {tuple(pred.shape)}: same shape and device expected")
+    if not (wanted.dtype == torch.uint8 and tuple(wanted.shape) == (256,) and wanted.device == gt.device):
+        raise RuntimeError("wanted: expected a (256,) uint8 tensor on the volumes' device")
+    stats = torch.empty((256, 10), dtype=torch.int32, device=gt.device)
+    _lib.check(_lib.lib().mlagg_surface_stats(_ptr(gt), _ptr(pred), *gt.shape, _ptr(wanted.contiguous()), _ptr(stats), _stream()),
+               "mlagg_surface_stats")
+    return stats
+
+
+def surface_prepare(gt, pred, desc, spacing):
+    """Neighbour codes and the z / y passes of the feature transform for every crop of desc ((L, 16) int64 host tensor, see
+    include/mlagg_hip.h).  Returns the state mlagg_surface_reduce needs: (codes, ft, counts, d_desc, layout)."""
+    _require_labels(gt, "gt")
+    _require_labels(pred, "pred")
+    L = desc.shape[0]
+    n = desc[:, 4:7].long() + 1
+    vox = n.prod(1)
+    layout = {"total": int(vox.sum()), "max_crop": int(vox.max()), "zlines": int((n[:, 0] * n[:, 1]).sum()),
+              "ylines": int((n[:, 0] * n[:, 2]).sum()), "xlines": int((n[:, 1] * n[:, 2]).sum()),
+              "nmax_y": int(n[:, 1].max()), "nmax_x": int(n[:, 0].max()), "labels": L}
+    if layout["max_crop"] > SURFACE_MAX_VOXELS:
+        raise RuntimeError(f"surface: a crop of {layout['max_crop']} voxels, at most {SURFACE_MAX_VOXELS} are supported")
+    if int(n.max()) > SURFACE_MAX_LINE:
+        raise RuntimeError(f"surface: a crop axis of {int(n.max())} voxels, at most {SURFACE_MAX_LINE} are supported")
+    dev = gt.device
+    d_desc = desc.to(dev)
+    codes = torch.empty(2 * layout["total"], dtype=torch.uint8, device=dev)
+    ft = torch.empty(2 * layout["total"], dtype=torch.int32, device=dev)
+    counts = torch.empty((L, 2), dtype=torch.int32, device=dev)
+    s = [float(v) for v in spacing]
+    _lib.check(_lib.lib().mlagg_surface_prepare(_ptr(gt), _ptr(pred), *gt.shape, _ptr(d_desc), L, layout["total"], layout["max_crop"],
+                                                layout["zlines"], layout["ylines"], layout["nmax_y"], s[1], s[2], _ptr(codes),
+                                                _ptr(ft), _ptr(counts), _stream()),
+               "mlagg_surface_prepare")
+    return codes, ft, counts, d_desc, layout
+
+
+def surface_reduce(state, tol, area, spacing, pairs_total=None):
+    """The x pass at the other mask's surfels.  tol (L,) float64 and area (256,) float64 device tensors.  Returns (sums (L, 4)
+    float64 device tensor: gt area, gt area within tol, prediction area, prediction area within tol; pairs (pairs_total, 2) float64
+    (distance, area) at desc's pair offsets, unsorted, or None)."""
+    codes, ft, counts, d_desc, layout = state
+    dev = codes.device
+    L = layout["labels"]
+    partial = torch.empty(4 * layout["xlines"], dtype=torch.float64, device=dev)
+    sums = torch.empty((L, 4), dtype=torch.float64, device=dev)
+    pairs = pair_count = None
+    if pairs_total is not None:
+        pairs = torch.empty((max(int(pairs_total), 1), 2), dtype=torch.float64, device=dev)
+        pair_count = torch.empty((L, 2), dtype=torch.int32, device=dev)
+    s = [float(v) for v in spacing]
+    _lib.check(_lib.lib().mlagg_surface_reduce(_ptr(codes), _ptr(ft), _ptr(d_desc), L, layout["total"], layout["xlines"],
+                                               layout["nmax_x"], _ptr(tol), _ptr(area), s[0], s[1], s[2], _ptr(partial), _ptr(sums),
+                                               _ptr(pairs), _ptr(pair_count), _stream()),
+               "mlagg_surface_reduce")
+    return sums, (None if pairs is None else pairs[:int(pairs_total)])
