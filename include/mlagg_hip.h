@@ -817,6 +817,22 @@ int mlagg_surface_reduce(const unsigned char *codes, const int *ft, const long l
                          long long xlines, int nmax_x, const double *tol, const double *area, double s0, double s1, double s2,
                          double *partial, double *sums, double *pairs, int *pair_count, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K25: 3-D spatial augmentation of a training batch (batchgenerators augment_spatial / interpolate_img for a 3-D patch, the
+ * SpatialTransform of nnUNetTrainer.get_training_transforms, nnUNetTrainer.py:666-677; no elastic deformation, random_crop False).
+ * vol (B, C, Xi, Yi, Zi) fp32: per sample the cubic B-spline coefficients (scipy's "mirror" prefilter) where resample[b] != 0, the
+ * raw data where it is 0.  lab (B, 1, Xi, Yi, Zi) int16 labels as the loader delivers them (-1 padding included), or NULL.
+ * affine: HOST array of B x 12 float64, row-major 3 x 4 per sample: input coordinate j = A[j][3] + A[j][0] x + A[j][1] y + A[j][2] z
+ * for output voxel (x, y, z).  resample: HOST array of B ints.
+ *   resampled sample: out = cubic B-spline of vol at that coordinate (taps mirror-indexed), 0 where the coordinate leaves
+ *                     [0, n - 1] on any axis; out_lab = the largest label whose trilinear indicator (8 taps, mirror-indexed) is
+ *                     >= 0.5, 0 where none is or outside.
+ *   cropped sample:   out / out_lab = the centre crop starting at ((Xi - Xo) / 2, (Yi - Yo) / 2, (Zi - Zo) / 2); needs Xo <= Xi ...
+ * out (B, C, Xo, Yo, Zo) fp32, out_lab (B, 1, Xo, Yo, Zo) fp32 (required with lab).  All contiguous.  No atomics: bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int mlagg_aug3d_resample(const float *vol, const short *lab, int B, int C, int Xi, int Yi, int Zi, const double *affine,
+                         const int *resample, float *out, float *out_lab, int Xo, int Yo, int Zo, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

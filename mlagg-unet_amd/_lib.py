@@ -174,6 +174,7 @@ SIGNATURES = {
                                                                                            _F, _F, _F, _S]),
     "mlagg_surface_reduce": (_I, [_F, _F, _F, _I, ctypes.c_longlong, ctypes.c_longlong, _I, _F, _F] + [ctypes.c_double] * 3
                              + [_F] * 4 + [_S]),
+    "mlagg_aug3d_resample": (_I, [_F, _F] + [_I] * 5 + [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I), _F, _F] + [_I] * 3 + [_S]),
     "mlagg_selscan1_chunk": (_I, [_I, _I, _I]),
     "mlagg_selscan1_state_floats": (_SZ, [_I, _I, _I, _I]),
     "mlagg_selscan1_fwd": (_I, [_F, ctypes.c_long] + [_F] * 5 + [_I] + [_F] * 5 + [_I] * 4 + [_S]),

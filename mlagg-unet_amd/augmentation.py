@@ -88,6 +88,11 @@ def draw_params(rng, batch, channels, rotation=(-math.pi, math.pi), mirror_axes=
             p["do_rot"][b] = True
         if rng.uniform() < 0.2:
             p["do_scale"][b], p["scale"][b] = True, _two_sided(rng, 0.7, 1.4)
+    return _draw_intensity_and_mirror(rng, p, B, C, mirror_axes)
+
+
+def _draw_intensity_and_mirror(rng, p, B, C, mirror_axes):
+    """The draws after SpatialTransform (B:683-695), shared by the 2-D and 3-D chains; p["mirror"] has one column per axis."""
     for b in range(B):                                                     # GaussianNoise p 0.1, variance U(0, 0.1) used as std
         if rng.uniform() < 0.1:
             p["do_noise"][b], p["noise_std"][b] = True, rng.uniform(0, 0.1)
@@ -119,9 +124,9 @@ def draw_params(rng, batch, channels, rotation=(-math.pi, math.pi), mirror_axes=
                 p[key_do][b] = True
                 p[key_g][b] = [_two_sided(rng, 0.7, 1.5) for _ in range(C)]
     for b in range(B):                                                     # Mirror: each axis with probability 1/2
-        for i, ax in enumerate((0, 1)):
+        for ax in range(p["mirror"].shape[1]):
             if ax in mirror_axes and rng.uniform() < 0.5:
-                p["mirror"][b, i] = True
+                p["mirror"][b, ax] = True
     return p
 
 
@@ -298,31 +303,33 @@ def simulate_low_resolution(data, do, zoom):
 
 
 def gamma_transform(data, do, gamma, invert):
-    """augment_gamma(per_channel, retain_stats, epsilon 1e-7) where `do` (B,); `gamma` (B, C)."""
+    """augment_gamma(per_channel, retain_stats, epsilon 1e-7) where `do` (B,); `gamma` (B, C); 2-D or 3-D batches."""
+    sp, one = tuple(range(2, data.dim())), (1,) * (data.dim() - 2)       # spatial axes: 2-D and 3-D batches
     x = -data if invert else data
-    mn = x.mean((2, 3), keepdim=True)
-    sd = x.std((2, 3), keepdim=True, unbiased=False)
-    lo = x.amin((2, 3), keepdim=True)
-    rng = x.amax((2, 3), keepdim=True) - lo
-    y = torch.pow((x - lo) / (rng + 1e-7), gamma.view(*gamma.shape, 1, 1)) * (rng + 1e-7) + lo
-    y = y - y.mean((2, 3), keepdim=True)
-    y = y / (y.std((2, 3), keepdim=True, unbiased=False) + 1e-8) * sd + mn
+    mn = x.mean(sp, keepdim=True)
+    sd = x.std(sp, keepdim=True, unbiased=False)
+    lo = x.amin(sp, keepdim=True)
+    rng = x.amax(sp, keepdim=True) - lo
+    y = torch.pow((x - lo) / (rng + 1e-7), gamma.view(*gamma.shape, *one)) * (rng + 1e-7) + lo
+    y = y - y.mean(sp, keepdim=True)
+    y = y / (y.std(sp, keepdim=True, unbiased=False) + 1e-8) * sd + mn
     y = -y if invert else y
-    return torch.where(do.view(-1, 1, 1, 1), y, data)
+    return torch.where(do.view(-1, 1, *one), y, data)
 
 
 def contrast_transform(data, do, factor):
     """augment_contrast(preserve_range, per_channel): (x - mean) * factor + mean, clipped to the channel's old range."""
-    mn = data.mean((2, 3), keepdim=True)
-    lo, hi = data.amin((2, 3), keepdim=True), data.amax((2, 3), keepdim=True)
-    y = torch.minimum(torch.maximum((data - mn) * factor.view(*factor.shape, 1, 1) + mn, lo), hi)
-    return torch.where(do.view(-1, 1, 1, 1), y, data)
+    sp, one = tuple(range(2, data.dim())), (1,) * (data.dim() - 2)
+    mn = data.mean(sp, keepdim=True)
+    lo, hi = data.amin(sp, keepdim=True), data.amax(sp, keepdim=True)
+    y = torch.minimum(torch.maximum((data - mn) * factor.view(*factor.shape, *one) + mn, lo), hi)
+    return torch.where(do.view(-1, 1, *one), y, data)
 
 
 def mirror_transform(data, seg, flags):
-    """MirrorTransform: flags (B, 2): flip rows / columns of that sample."""
-    for i, dim in enumerate((2, 3)):
-        m = flags[:, i].view(-1, 1, 1, 1)
+    """MirrorTransform: flags (B, n_axes): flip spatial axis i of that sample (2-D: rows / columns; 3-D: x / y / z)."""
+    for i in range(flags.shape[1]):
+        dim, m = i + 2, flags[:, i].view(-1, *(1,) * (data.dim() - 1))
         data = torch.where(m, data.flip(dim), data)
         seg = torch.where(m, seg.flip(dim), seg)
     return data, seg

@@ -37,7 +37,8 @@ const char *const kNames[K_COUNT] = {
     "sw_gather_kernel", "sw_fold_kernel", "sw_finalize_kernel", "resample_linear_kernel", "export_kernel",
     "pp_box_kernel", "pp_stats_kernel (+ final)", "pp_normalize_kernel", "pp_minmax_kernel", "pp_cubic_kernel", "pp_gather_kernel",
     "cc_local_kernel", "cc_merge_kernel", "cc_compress_kernel", "cc_size_kernel", "cc_max_kernel", "cc_write_kernel",
-    "sf_stats_kernel (+ init)", "sf_codes_kernel", "sf_zpass_kernel", "sf_ypass_kernel", "sf_xpass_kernel", "sf_sum_kernel"};
+    "sf_stats_kernel (+ init)", "sf_codes_kernel", "sf_zpass_kernel", "sf_ypass_kernel", "sf_xpass_kernel", "sf_sum_kernel",
+    "aug3d_resample_kernel"};
 }  // namespace
 
 // begin/end pairs of one kernel are issued back to back from one host thread (the launcher), so the

@@ -11,7 +11,10 @@ batches bit for bit -- but
     (data, [target_0..target_4]) pair nnUNetTrainer.train_step consumes (nnUNetTrainer.py:833-845);
   * `PrefetchLoader` overlaps batch assembly (worker threads, one RandomState each) and the H2D copy with the train step.
 
-Out of scope: batchgenerators' augmentation transforms (third-party, absent offline)."""
+`DataLoader3D` is the reference's nnUNetDataLoader3D (training/dataloading/data_loader_3d.py:7-52 on get_bbox,
+base_data_loader.py:63-139) on the same case folder and pinned buffers; `to_device` / `PrefetchLoader` take the trainer's
+per-axis deep-supervision scales for its batches (`ds_scales`).  The augmentation transforms live in augmentation.py (2-D)
+and augmentation3d.py (3-D)."""
 import os
 import pickle
 import queue
@@ -138,35 +141,111 @@ class DataLoader2D:
             h, w = v1[0] - v0[0], v1[1] - v0[1]
             data_all[j, :, o0[0]:o0[0] + h, o0[1]:o0[1] + w] = data[:, sl, v0[0]:v1[0], v0[1]:v1[1]]
             seg_all[j, :, o0[0]:o0[0] + h, o0[1]:o0[1] + w] = seg[:, sl, v0[0]:v1[0], v0[1]:v1[1]]
+        self._check_labels(seg_all, keys)
+        return {"data": data_t, "seg": seg_t, "keys": keys}
+
+    def _check_labels(self, seg_all, keys):
         if self.max_label is not None and int(seg_all.max()) > self.max_label:
             # torch's nll_loss (the reference's CE) fails on a label >= C; the fused loss kernel would quietly count such a
             # pixel as "no class hit", so a corrupt case is stopped here, on the host, where the check costs nothing
             raise RuntimeError(f"segmentation label {int(seg_all.max())} > {self.max_label} (largest label of the dataset) "
                                f"in cases {sorted(set(map(str, keys)))}")
+
+    def clone(self, rng):
+        """The same loader with its own random state (one per PrefetchLoader worker)."""
+        return type(self)(self.ds, self.batch_size, self.patch_size, tuple(np.array(self.patch_size) - self.need_to_pad),
+                          self.annotated_classes_key, self.oversample, rng=rng, pin_memory=self.pin, has_ignore=self.has_ignore)
+
+
+class DataLoader3D(DataLoader2D):
+    """nnUNetDataLoader3D.generate_train_batch, draw for draw: the keys, then per sample get_bbox's class choice (no
+    overwrite_class, unlike the 2-D loader) and its voxel choice or one randint per axis.  The 3-D crop of each case goes
+    straight into the pinned batch buffers (data padded with 0, seg int16 padded with -1)."""
+
+    def _bbox(self, shape, force_fg, class_locations):      # base_data_loader.py:63-139 for dim 3
+        dim = len(shape)
+        need = self.need_to_pad.copy()
+        for d in range(dim):
+            if need[d] + shape[d] < self.patch_size[d]:
+                need[d] = self.patch_size[d] - shape[d]
+        lbs = [-need[i] // 2 for i in range(dim)]
+        ubs = [shape[i] + need[i] // 2 + need[i] % 2 - self.patch_size[i] for i in range(dim)]
+        if not force_fg and not self.has_ignore:
+            return [self.rng.randint(lbs[i], ubs[i] + 1) for i in range(dim)]
+        if not force_fg:                                     # ignore label: a patch around an ANNOTATED voxel (:91-97)
+            sel = self.annotated_classes_key
+            if len(class_locations[sel]) == 0:
+                sel = None
+        else:
+            eligible = [i for i in class_locations.keys() if len(class_locations[i]) > 0]
+            # the all-annotated-labels key competes only when nothing else is present (:112-115)
+            if len(eligible) > 1 and self.annotated_classes_key in [i for i in eligible if isinstance(i, tuple)]:
+                eligible.remove(self.annotated_classes_key)
+            sel = eligible[self.rng.choice(len(eligible))] if eligible else None
+        vox = class_locations[sel] if sel is not None else None
+        if vox is not None and len(vox) > 0:
+            v = vox[self.rng.choice(len(vox))]
+            return [max(lbs[i], int(v[i + 1]) - self.patch_size[i] // 2) for i in range(dim)]
+        return [self.rng.randint(lbs[i], ubs[i] + 1) for i in range(dim)]
+
+    def generate_train_batch(self):
+        keys = self.rng.choice(self.indices, self.batch_size, replace=True, p=None)
+        data_t, seg_t = self._buffers()
+        data_all, seg_all = data_t.numpy(), seg_t.numpy()
+        for j, key in enumerate(keys):
+            force_fg = self.get_do_oversample(j)
+            data, seg = self.ds.arrays(key)
+            shape = data.shape[1:]
+            cl = self.ds.properties(key)["class_locations"] if (force_fg or self.has_ignore) else None
+            lb = self._bbox(shape, force_fg, cl)
+            v0 = [max(0, lb[i]) for i in range(3)]
+            v1 = [min(shape[i], lb[i] + self.patch_size[i]) for i in range(3)]
+            o = [v0[i] - lb[i] for i in range(3)]
+            dst = (slice(None),) + tuple(slice(o[i], o[i] + v1[i] - v0[i]) for i in range(3))
+            src = (slice(None),) + tuple(slice(v0[i], v1[i]) for i in range(3))
+            data_all[j][dst] = data[src]
+            seg_all[j][dst] = seg[src]
+        self._check_labels(seg_all, keys)
         return {"data": data_t, "seg": seg_t, "keys": keys}
 
 
-def targets_from_seg(seg, n_levels=5):
-    """RemoveLabelTransform(-1, 0) (B:701) + DownsampleSegForDSTransform2, order 0 (B:730): the deep-supervision targets."""
+def targets_from_seg(seg, n_levels=5, ds_scales=None):
+    """RemoveLabelTransform(-1, 0) (B:701) + DownsampleSegForDSTransform2, order 0 (B:730): the deep-supervision targets.
+    2-D: n_levels halvings of both axes.  `ds_scales` (the trainer's _get_deep_supervision_scales(), one per-axis scale
+    list per level, e.g. [1, .5, .5]): level shape round(shape * scale), nearest-exact; an all-ones scale is the map itself."""
     seg = torch.where(seg < 0, torch.zeros_like(seg), seg)
-    targets = [seg]
-    for s in range(1, n_levels):
-        size = (seg.shape[2] >> s, seg.shape[3] >> s)
+    if ds_scales is None:
+        targets = [seg]
+        for s in range(1, n_levels):
+            size = (seg.shape[2] >> s, seg.shape[3] >> s)
+            targets.append(torch.nn.functional.interpolate(seg, size=size, mode="nearest-exact"))
+        return targets
+    targets = []
+    for sc in ds_scales:
+        if len(sc) != seg.dim() - 2:
+            raise RuntimeError(f"deep-supervision scale {list(sc)} for a {seg.dim() - 2}-D segmentation")
+        if all(float(v) == 1.0 for v in sc):
+            targets.append(seg)
+            continue
+        size = tuple(int(v) for v in np.round(np.array(seg.shape[2:], dtype=float) * np.array(sc, dtype=float)))
         targets.append(torch.nn.functional.interpolate(seg, size=size, mode="nearest-exact"))
     return targets
 
 
-def to_device(batch, device, n_levels=5, stream=None, augmenter=None):
-    """Host batch -> (data (B, C, H, W) fp32, [target_s (B, 1, H/2^s, W/2^s) fp32 labels]) on `device`; with an
-    `augmenter` (augmentation.GpuAugmenter) the training transforms run on the device in between."""
+def to_device(batch, device, n_levels=5, stream=None, augmenter=None, ds_scales=None):
+    """Host batch -> (data (B, C, *spatial) fp32, [target_s (B, 1, *spatial_s) fp32 labels]) on `device`; with an
+    `augmenter` (augmentation.GpuAugmenter / augmentation3d.GpuAugmenter3D) the training transforms run on the device in
+    between.  2-D: n_levels halvings; `ds_scales`: per-axis scales (targets_from_seg), for 3-D batches."""
     device = torch.device(device)
     ctx = torch.cuda.stream(stream) if stream is not None else _Null()
     with ctx:
         data = batch["data"].to(device, non_blocking=True)
-        seg = batch["seg"].to(device, non_blocking=True).float()
+        seg = batch["seg"].to(device, non_blocking=True)
+        # the 3-D augmenter reads the loader's int16 labels as they are (K25); everything else takes fp32 label maps
+        seg = seg if getattr(augmenter, "takes_int16_seg", False) else seg.float()
         if augmenter is not None:
             data, seg = augmenter(data, seg)
-        targets = targets_from_seg(seg, n_levels)
+        targets = targets_from_seg(seg.float(), n_levels, ds_scales)
     return data, targets
 
 
@@ -183,18 +262,16 @@ class PrefetchLoader:
     (numpy's slicing / copies release the GIL); batches arrive on the device through a side stream, and `next()` makes the
     caller's current stream wait for that copy only."""
 
-    def __init__(self, loader, device, num_workers=4, depth=6, seed=1234, n_levels=5, augmenter=None):
+    def __init__(self, loader, device, num_workers=4, depth=6, seed=1234, n_levels=5, augmenter=None, ds_scales=None):
         self.device = torch.device(device)
         self.q = queue.Queue(maxsize=depth)
         self.stop = threading.Event()
         self.n_levels = n_levels
+        self.ds_scales = None if ds_scales is None else [list(s) for s in ds_scales]
         self.copy_stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
         self.workers = []
         for i in range(num_workers):
-            clone = DataLoader2D(loader.ds, loader.batch_size, loader.patch_size,
-                                 tuple(np.array(loader.patch_size) - loader.need_to_pad), loader.annotated_classes_key,
-                                 loader.oversample, rng=np.random.RandomState(seed + i), pin_memory=loader.pin,
-                                 has_ignore=loader.has_ignore)
+            clone = loader.clone(np.random.RandomState(seed + i))
             aug = augmenter.clone(seed + 7919 * (i + 1)) if augmenter is not None else None
             t = threading.Thread(target=self._work, args=(clone, aug), daemon=True)
             t.start()
@@ -205,11 +282,11 @@ class PrefetchLoader:
             try:
                 b = loader.generate_train_batch()
                 if self.copy_stream is not None:
-                    data, targets = to_device(b, self.device, self.n_levels, self.copy_stream, augmenter)
+                    data, targets = to_device(b, self.device, self.n_levels, self.copy_stream, augmenter, self.ds_scales)
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
                 else:
-                    data, targets = to_device(b, self.device, self.n_levels, None, augmenter)
+                    data, targets = to_device(b, self.device, self.n_levels, None, augmenter, self.ds_scales)
                     ev = None
                 item = (data, targets, ev, b)                 # keep the pinned host batch alive until consumed
             except BaseException as e:                        # missing .pkl, bad .npz, out of memory on the copy stream ...

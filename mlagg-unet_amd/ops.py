@@ -3129,3 +3129,35 @@ def surface_reduce(state, tol, area, spacing, pairs_total=None):
                                                _ptr(pairs), _ptr(pair_count), _stream()),
                "mlagg_surface_reduce")
     return sums, (None if pairs is None else pairs[:int(pairs_total)])
+
+
+# ------------------------------------------------------------------------------------------------
+# K25: 3-D spatial augmentation (augmentation3d.GpuAugmenter3D)
+# ------------------------------------------------------------------------------------------------
+def aug3d_resample(vol, lab, affine, resample, out_shape):
+    """vol (B, C, Xi, Yi, Zi) fp32 (spline coefficients of the resampled samples, raw data of the cropped ones), lab (B, 1, Xi, Yi, Zi)
+    int16 or None, affine (B, 3, 4) float64 host array (output voxel index -> input coordinate), resample (B,) host bools ->
+    (out (B, C, *out_shape) fp32, out_lab (B, 1, *out_shape) fp32 or None).  See include/mlagg_hip.h, K25."""
+    import ctypes
+    _sw_volume(vol, "vol", 5)
+    B, C, Xi, Yi, Zi = (int(v) for v in vol.shape)
+    Xo, Yo, Zo = (int(v) for v in out_shape)
+    if min(Xo, Yo, Zo) < 1:
+        raise RuntimeError(f"aug3d_resample: output shape {tuple(out_shape)}")
+    if lab is not None:
+        if not (isinstance(lab, torch.Tensor) and lab.device == vol.device and lab.dtype == torch.int16 and lab.is_contiguous()
+                and tuple(lab.shape) == (B, 1, Xi, Yi, Zi)):
+            raise RuntimeError(f"lab: expected a contiguous int16 tensor of shape {(B, 1, Xi, Yi, Zi)} on {vol.device}, got "
+                               f"{getattr(lab, 'dtype', type(lab))} {tuple(getattr(lab, 'shape', ()))}")
+    A = np.ascontiguousarray(np.asarray(affine, dtype=np.float64).reshape(B, 12))
+    rs = np.asarray(resample, dtype=bool).reshape(-1)
+    if rs.shape[0] != B:
+        raise RuntimeError(f"aug3d_resample: {rs.shape[0]} resample flags for {B} samples")
+    if (~rs).any() and (Xo > Xi or Yo > Yi or Zo > Zi):
+        raise RuntimeError(f"aug3d_resample: a cropped sample needs an input ({Xi}, {Yi}, {Zi}) at least the output ({Xo}, {Yo}, {Zo})")
+    out = torch.empty((B, C, Xo, Yo, Zo), device=vol.device, dtype=torch.float32)
+    out_lab = torch.empty((B, 1, Xo, Yo, Zo), device=vol.device, dtype=torch.float32) if lab is not None else None
+    _lib.check(_lib.lib().mlagg_aug3d_resample(_ptr(vol), _ptr(lab), B, C, Xi, Yi, Zi,
+                                               A.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _int_array(rs.astype(int)), _ptr(out),
+                                               _ptr(out_lab), Xo, Yo, Zo, _stream()), "mlagg_aug3d_resample")
+    return out, out_lab
