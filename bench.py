@@ -7,10 +7,17 @@ synthetic AbdomenMRI-shaped batches -- BASELINE.json config 2: 256x256x1, batch 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --dump-outputs DIR      # + DIR/{loss,params,grads}.npy of the last timed step
+    python bench.py --full                  # + roofline, loss read-back timing and CPU baseline
 
 A step = zero_grad + forward + Dice/CE deep-supervision loss + backward + clip_grad_norm_(12) + AdamW
 (reference nnUNetTrainer.py:833-863), inputs resident in HBM before the timed region
 (nnUNetTrainerBenchmark_5epochs_noDataLoading.py:16-22).  One JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, one untimed step, the timed steps, the
+outputs of --dump-outputs and the line.  The untimed step stands where --full instruments a step to find the
+roofline's kernel, so both modes time and dump the same steps from the same state.  --full adds the measurements
+that take runs of their own: the roofline (per-kernel HIP-event times and the MFMA figures), the timed steps once
+more with the per-step loss read-back, and the CPU baseline of the oracle (single GPU).
 """
 import argparse
 import json
@@ -195,7 +202,9 @@ def main_3d(args, cfg, world, rank, dev, dev_index, ddp):
         note(f"warm-up step {i + 1}/{args.warmup} done ({torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB peak)")
     tokens = size[0] * size[1] * size[2]
     dominant, table, fixed = None, {}, []
-    if not args.no_roofline:
+    if not args.no_roofline and not args.full:
+        one_step()          # the step --full instruments, untimed (module docstring)
+    elif not args.no_roofline:
         profiling.select_all()
         one_step()
         table = profiling.collect()
@@ -244,7 +253,7 @@ def main_3d(args, cfg, world, rank, dev, dev_index, ddp):
                            "final_loss": round(float(loss), 5), "launch": "eager", "miopen": "immediate mode",
                            "peak_hbm_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)},
                 "roofline": roof}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_3d(size, strides, cfg["classes"])
         print(json.dumps(line), flush=True)
         if outputs is not None:
@@ -275,8 +284,12 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (weak scaling); default: the config's")
     ap.add_argument("--precision", default=None, choices=["fp32", "bf16", "fp16"],
                     help="arithmetic type of the dense products; default: the config's (a diagnostic override)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline, the timed steps again with the "
+                         "per-step loss read-back, and the CPU baseline (single GPU).  Off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="leave out the roofline under --full, and in either mode the untimed step before the timed ones")
     ap.add_argument("--graph", action="store_true",
                     help="replay the whole step as one hipGraph (trainer.GraphedTrainStep).  Off by default: at "
                          "config 2 the step is GPU-bound either way (61.58 vs 61.63 ms measured A/B on one box) and "
@@ -361,13 +374,15 @@ def main():
         torch.cuda.synchronize()
         note(f"warm-up step {i + 1}/{args.warmup} done")
 
-    # pick the dominant hand-written kernel from one instrumented (untimed, eager) step; during the timed
+    # --full: pick the dominant hand-written kernel from one instrumented (untimed, eager) step; during the timed
     # region ONLY that kernel is bracketed by HIP events on its launch stream (event records are captured
     # into the graph with the kernel, so they time every replay)
     roof = None
     dominant = None
     mfma = None
-    if not args.no_roofline:
+    if not args.no_roofline and not args.full:
+        eager_step()        # the step --full instruments, untimed (module docstring)
+    elif not args.no_roofline:
         from mlagg_unet_amd import ops
         profiling.select_all()
         ops.FLOP_COUNT = {}
@@ -415,12 +430,14 @@ def main():
     outputs = step_outputs(loss, net) if args.dump_outputs and rank == 0 else None
 
     # the path nnUNetv2_train drives reads the loss back every step (`l.detach().cpu().numpy()`, reference B:863; the plugin's
-    # train_step mirrors it): the same steps once more with that host synchronisation, reported beside the headline
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        float(one_step().cpu())
-    dt_synced = time.perf_counter() - t1
+    # train_step mirrors it): under --full the same steps once more with that host synchronisation, reported beside the headline
+    dt_synced = None
+    if args.full:
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            float(one_step().cpu())
+        dt_synced = time.perf_counter() - t1
 
     if not args.no_roofline and dominant is not None:
         if use_graph:
@@ -460,8 +477,9 @@ def main():
                        "parallelism": f"dp{world}" + (" (single-rank RCCL rehearsal of the DDP path)" if ddp and world == 1 else ""),
                        "final_loss": round(float(loss), 5),
                        "launch": "hipGraph replay of the whole step" if use_graph else "eager",
-                       "ms_per_step_with_loss_readback": round(1e3 * dt_synced / args.steps, 3),
-                       "images_per_sec_with_loss_readback": round(args.batch * world * args.steps / dt_synced, 3),
+                       **({"ms_per_step_with_loss_readback": round(1e3 * dt_synced / args.steps, 3),
+                           "images_per_sec_with_loss_readback": round(args.batch * world * args.steps / dt_synced, 3)}
+                          if dt_synced is not None else {}),
                        "distributed": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(), "rank0_device": str(dev),
                                         "grad_sync": trainer.GRAD_SYNC} if ddp else None),
                        "miopen": "tuned find-db (mlagg-unet_amd/miopen_db)" if miopen_db else "immediate mode",
@@ -469,7 +487,7 @@ def main():
                        "matrix_arithmetic": matrix_arithmetic(cfg["precision"])},
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline and args.config == 2:
+        if world == 1 and args.full and not args.no_cpu_baseline and args.config == 2:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
         if outputs is not None:

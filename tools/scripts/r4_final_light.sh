@@ -9,5 +9,5 @@ T=$(find $RAW/trace -name "*kernel_trace.csv" | head -1)
 python3 tools/summarize_trace.py "$T" --steps 10 --top 80 --aten > $O/kernel_trace_timed_region.md 2>> $O/trace.err
 cp $(find $RAW/trace -name "*kernel_stats.csv" | head -1) $O/rocprofv3_kernel_stats_whole_process.csv
 head -30 $O/kernel_trace_timed_region.md
-timeout -k 10 400 python3 bench.py > $O/bench_final.json 2> $O/bench_final.err
+timeout -k 10 400 python3 bench.py --full > $O/bench_final.json 2> $O/bench_final.err
 tail -1 $O/bench_final.json | cut -c1-400

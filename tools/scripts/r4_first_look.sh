@@ -6,7 +6,7 @@ O=gpurun_out/r4a
 mkdir -p $O
 export TMPDIR=/tmp
 timeout -k 10 300 python -m pytest tests/test_blocks_gpu.py tests/test_graph_gpu.py -x -q -k "adamw or graph" > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
-B="timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+B="timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline"
 $B > $O/eager.json 2> $O/eager.err && tail -c 600 $O/eager.err
 $B --graph --no-roofline > $O/graph.json 2> $O/graph.err
 MLAGG_K5_MIN_ROWS=10240 $B --no-roofline > $O/eager_k5_10240.json 2>/dev/null
