@@ -136,21 +136,17 @@ class _ConvMixin:
     def _lib_conv(self, x, w):
         raise NotImplementedError
 
-    def _fp32_conv(self, x):
-        return self._lib_conv(x, self.weight)
-
-    def _lp_conv(self, x, form):
-        return None
+    def _native(self, x, form):
+        """The convolution on this package's kernels (K18 / K19 / K19t, as ops.conv_plan decides), or None: the library's."""
+        return ops.conv2d(x, self.weight, self.stride, self.padding, self.dilation, self.groups, self.transposed, self.output_padding,
+                          form)
 
     def raw(self, x):
-        cdt = ops.conv_dtype()
-        if cdt == torch.float32:
-            return self._fp32_conv(x)
-        if x.dtype == torch.float32:
-            y = self._lp_conv(x, ops.conv_form())                    # K18 / K19, one rounded product, fp32 map out (round 4)
-            if y is not None:
-                return y
-        return self._lib_conv(x if x.dtype == cdt else x.to(cdt), self.weight.to(cdt))
+        y = self._native(x, ops.conv_form())          # 16-bit modes: one rounded product, fp32 map out (round 4)
+        if y is None:
+            cdt = ops.conv_dtype()
+            y = self._lib_conv(ops.lp(x, cdt), ops.lp(self.weight, cdt))
+        return y
 
     def fused(self, x, res=None, act=ops.EPI_NONE, dtype=None):
         if not x.is_cuda or getattr(self, "padding_mode", "zeros") != "zeros":
@@ -180,20 +176,6 @@ class Conv2d(_ConvMixin, nn.Conv2d):
     def _lib_conv(self, x, w):
         return F.conv2d(x, w, None, self.stride, self.padding, self.dilation, self.groups)
 
-    def _fp32_conv(self, x):
-        if ops.conv1x1_supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
-            return ops.conv1x1(x, self.weight)                       # K18
-        if ops.conv3x3_supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
-            return ops.conv3x3(x, self.weight)                       # K19
-        return self._lib_conv(x, self.weight)
-
-    def _lp_conv(self, x, form):
-        if ops.conv1x1_supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups, form):
-            return ops.conv1x1(x, self.weight, form)
-        if ops.conv3x3_supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups, form):
-            return ops.conv3x3(x, self.weight, form)
-        return None
-
     def _eager(self, x):
         return nn.Conv2d.forward(self, x)
 
@@ -206,44 +188,6 @@ class Conv2d(_ConvMixin, nn.Conv2d):
 class ConvTranspose2d(_ConvMixin, nn.ConvTranspose2d):
     def _lib_conv(self, x, w):
         return F.conv_transpose2d(x, w, None, self.stride, self.padding, self.output_padding, self.groups, self.dilation)
-
-    def _pointwise(self):
-        """A 1 x 1, stride-1 transposed convolution IS the 1 x 1 convolution with the weight's first two axes exchanged (the segmentation
-        heads, T:549-561): it takes K18 like the other pointwise convolutions."""
-        return (tuple(self.kernel_size) == (1, 1) and tuple(self.stride) == (1, 1) and tuple(self.padding) == (0, 0)
-                and tuple(self.output_padding) == (0, 0) and self.groups == 1 and tuple(self.dilation) == (1, 1))
-
-    def _k18(self, x, form):
-        # only where all three products run on K18 (the heads on the 256 x 256 and 128 x 128 maps): on the small maps the library's
-        # transposed-convolution solvers are the faster ones
-        I, O = self.weight.shape[:2]
-        P = int(x.shape[2] * x.shape[3])
-        return (self._pointwise() and ops.conv1x1_supported(x, self.weight, (1, 1), (0, 0), (1, 1), 1, form)
-                and ops._k18_product(O, I, P, form) and ops._k18_product(I, O, P, form))
-
-    def _t2(self, x, form):
-        return ops.conv_t2x2_supported(x, self.weight, self.stride, self.padding, self.output_padding, self.dilation, self.groups, form)
-
-    def _s2t(self, x, form):
-        return ops.conv3x3_s2t_supported(x, self.weight, self.stride, self.padding, self.output_padding, self.dilation, self.groups, form)
-
-    def _fp32_conv(self, x):
-        if self._k18(x, ops._DTYPE_BF16X3):
-            return ops.conv1x1(x, self.weight.permute(1, 0, 2, 3))
-        if self._t2(x, ops._DTYPE_BF16X3):
-            return ops.conv_t2x2(x, self.weight)                     # K18 + pixel shuffle
-        if self._s2t(x, ops._DTYPE_BF16X3):
-            return ops.conv3x3_s2t(x, self.weight)                   # K19t (PatchExpand)
-        return self._lib_conv(x, self.weight)
-
-    def _lp_conv(self, x, form):
-        if self._k18(x, form):
-            return ops.conv1x1(x, self.weight.permute(1, 0, 2, 3), form)
-        if self._t2(x, form):
-            return ops.conv_t2x2(x, self.weight, form)
-        if self._s2t(x, form):
-            return ops.conv3x3_s2t(x, self.weight, form)
-        return None
 
     def _eager(self, x):
         return nn.ConvTranspose2d.forward(self, x)
@@ -587,7 +531,7 @@ class _MapToTokens(torch.autograd.Function):
 
 
 def _map_to_tokens(x):
-    return _MapToTokens.apply(x, ops._claim(x) if x.is_cuda else None)
+    return _MapToTokens.apply(x, ops.claim_slot(x) if x.is_cuda else None)
 
 
 class _TokensToMap(torch.autograd.Function):

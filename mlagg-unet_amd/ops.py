@@ -84,19 +84,17 @@ def conv_form():
     return _DTYPE_BF16X3 if cdt == torch.float32 else _LP_CODE[cdt]
 
 
-def _lib_conv_fwd(x, w, padding, form):
-    """Library forward of a stride-1 convolution inside a K18 / K19 Function, in the arithmetic of `form` (fp32 maps in and out)."""
-    if form == _DTYPE_BF16X3:
-        return torch.nn.functional.conv2d(x, w, None, 1, padding)
-    t = _FORM_TORCH[form]
-    return torch.nn.functional.conv2d(x.to(t), w.to(t), None, 1, padding).float()
+def _lib_conv(x, w, stride, padding, transposed, form):
+    """Library forward of a product that a convolution Function leaves to the library (2-D or 3-D, isotropic stride and padding, no
+    bias), in the arithmetic of `form`: fp32 maps in and out."""
+    nd, t = x.dim() - 2, _FORM_TORCH[form]
+    return torch.convolution(lp(x, t), lp(w, t), None, (stride,) * nd, (padding,) * nd, (1,) * nd, transposed, (0,) * nd, 1).float()
 
 
-def _lib_conv_bwd(dy, x, w, padding, mask, form):
-    if form != _DTYPE_BF16X3:
-        t = _FORM_TORCH[form]
-        dy, x, w = dy.to(t), x.to(t), w.to(t)
-    out = torch.ops.aten.convolution_backward(dy, x, w, None, (1, 1), (padding, padding), (1, 1), False, (0, 0), 1, mask)
+def _lib_conv_bwd(dy, x, w, stride, padding, transposed, mask, form):
+    nd, t = x.dim() - 2, _FORM_TORCH[form]
+    out = torch.ops.aten.convolution_backward(lp(dy, t).contiguous(), lp(x, t), lp(w, t), None, (stride,) * nd, (padding,) * nd, (1,) * nd,
+                                              transposed, (0,) * nd, 1, mask)
     return [None if o is None else o.float() for o in out]
 
 
@@ -370,7 +368,7 @@ class _GradArena:
         return self.buf
 
 
-def _claim(t):
+def claim_slot(t):
     """The gradient slot of a ``split_cols`` piece, if it has one nobody claimed yet (a piece feeding two kernels: the second takes
     the ordinary path and autograd's sum of the two gradients is copied into the slot)."""
     slot = getattr(t, "_mlagg_slot", None)
@@ -562,12 +560,12 @@ class DWConvGatedFn(torch.autograd.Function):
 
 def dwconv3x3_gated(x, gate, weight, bias, H, W):
     """SiLU(depthwise 3x3(x) + bias) * gate on token-major maps (x, gate: column blocks of one projection output are fine)."""
-    return DWConvGatedFn.apply(x, gate, weight, bias, H, W, _claim(x), _claim(gate))
+    return DWConvGatedFn.apply(x, gate, weight, bias, H, W, claim_slot(x), claim_slot(gate))
 
 
 def dwconv3x3_nlc(x, weight, bias, H, W, silu=False, res=None):
     """Depthwise 3x3 on a token-major map; `res` (same shape as the output) is added in the same pass."""
-    return DWConv3x3Fn.apply(x, weight, bias, H, W, silu, _claim(x), res)
+    return DWConv3x3Fn.apply(x, weight, bias, H, W, silu, claim_slot(x), res)
 
 
 class DWConv3dFn(torch.autograd.Function):
@@ -839,14 +837,14 @@ def flash_attn(q, k, v, softmax_scale=None):
 
 
 def local_diff_attn(q, kv, lam, subln_w, lepe_w, lepe_b, H, W, nh, scale):
-    return LocalDiffAttnFn.apply(q, kv, lam, subln_w, lepe_w, lepe_b, H, W, nh, scale, _claim(q), _claim(kv))
+    return LocalDiffAttnFn.apply(q, kv, lam, subln_w, lepe_w, lepe_b, H, W, nh, scale, claim_slot(q), claim_slot(kv))
 
 
 def pooled_diff_attn(q, k_pool, v_pool, lam, subln_w, nh, scale):
     cdt = compute_dtype()
     if cdt != torch.float32 and k_pool.shape[1] <= 320:
-        return PooledDiffAttnLpFn.apply(q, k_pool, v_pool, lam, subln_w, nh, scale, cdt, _claim(q))
-    return PooledDiffAttnFn.apply(q, k_pool, v_pool, lam, subln_w, nh, scale, _claim(q))
+        return PooledDiffAttnLpFn.apply(q, k_pool, v_pool, lam, subln_w, nh, scale, cdt, claim_slot(q))
+    return PooledDiffAttnFn.apply(q, k_pool, v_pool, lam, subln_w, nh, scale, claim_slot(q))
 
 
 # fp32 projections on the 16-bit matrix instructions (csrc/linear_lp.hip MODE 2: each fp32 operand as three bf16 pieces, six partial
@@ -1122,7 +1120,7 @@ def linear(x, weight, bias=None):
         O, I = weight.shape
         M = x.numel() // I
         if _x3_ok(M, O, I) and _x3_ok(M, I, O):
-            slot = _claim(x)
+            slot = claim_slot(x)
     return LinearFn.apply(x, weight, bias, slot)
 
 
@@ -1648,7 +1646,7 @@ class GateFn(torch.autograd.Function):
 
 
 def gate(a0, a1, act):
-    return GateFn.apply(a0, a1, act, _claim(act))
+    return GateFn.apply(a0, a1, act, claim_slot(act))
 
 
 class GeluPoolFn(torch.autograd.Function):
@@ -1680,7 +1678,7 @@ class GeluPoolFn(torch.autograd.Function):
 
 
 def gelu_pool(s, H, W, r):
-    return GeluPoolFn.apply(s, H, W, r, _claim(s))
+    return GeluPoolFn.apply(s, H, W, r, claim_slot(s))
 
 
 class DiffLambdaFn(torch.autograd.Function):
@@ -2089,35 +2087,46 @@ def _k18_product(O, I, P, form=_DTYPE_BF16X3):
 
 
 def _conv1x1_k18(x, xb, w, y, B, O, I, P, form, accumulate=False):
-    """y (B, O, P) (+)= w (O, I) . x (B, I, P) on K18; a contraction that is not a multiple of 16 on zero-padded weight columns."""
+    """y (B, O, P) (+)= w (O, I) . x (B, I, P) on K18 (y None: a new map); a contraction that is not a multiple of 16 on zero-padded
+    weight columns."""
+    if y is None:
+        y = torch.empty((B, O) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
     I16 = -(-I // 16) * 16
     if I16 != I:
         wp = torch.zeros(O, I16, device=w.device, dtype=torch.float32)
         wp[:, :I] = w
         w = wp
+    _flop("K18", 2 * B * O * I * P)
     _lib.check(_lib.lib().mlagg_conv1x1_fwd_acc(_ptr(x), xb, _ptr(w), None, _ptr(y), O * P, B, O, I16, I, P, form, int(accumulate), _stream()),
                "mlagg_conv1x1_fwd_acc")
+    return y
+
+
+def _conv1x1_wgrad(dy, dyb, x, B, O, I, P, form):
+    """dW (O, I) = dy (B, O, P) . x (B, I, P)^T on K18."""
+    lib = _lib.lib()
+    dW = torch.empty(O, I, device=x.device, dtype=torch.float32)
+    ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, O, I, P), device=x.device, dtype=torch.float32)
+    _flop("K18", 2 * B * O * I * P)
+    _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, P, form, _stream()),
+               "mlagg_conv1x1_wgrad_lp")
+    return dW
 
 
 class Conv1x1Fn(torch.autograd.Function):
-    """y = conv2d(x, W) for a 1 x 1 kernel (stride 1, no bias): each of the three products on K18 (this package's split-bf16 GEMM
-    kernels: forward, data gradient = the forward kernel on W^T, weight gradient with the pixels as the contraction) or on the
-    library, whichever is faster at the shape (see K18_* above)."""
+    """y = conv2d(x, W) for a 1 x 1 kernel (stride 1, no bias): forward and data gradient (the forward kernel on W^T) on K18 or on the
+    library as the plan says (_conv1x1_plan unless one is given), the weight gradient (the pixels as the contraction) on K18."""
 
     @staticmethod
-    def forward(ctx, x, weight, form=_DTYPE_BF16X3):
+    def forward(ctx, x, weight, form=_DTYPE_BF16X3, plan=None):
         x, xb, P = _planes(x, "x")
         B, I = x.shape[:2]
         O = weight.shape[0]
+        plan = plan or _conv1x1_plan(O, I, P, form)
         w = _require(weight.reshape(O, I).contiguous(), "weight")
-        if _k18_product(O, I, P, form):
-            y = torch.empty((B, O) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
-            _flop("K18", 2 * B * O * I * P)
-            _conv1x1_k18(x, xb, w, y, B, O, I, P, form)
-        else:
-            y = _lib_conv_fwd(x, weight, 0, form)
+        y = _conv1x1_k18(x, xb, w, None, B, O, I, P, form) if plan[0] else _lib_conv(x, weight, 1, 0, False, form)
         ctx.save_for_backward(x, w)
-        ctx.wshape, ctx.form = weight.shape, form
+        ctx.wshape, ctx.plan, ctx.form = weight.shape, plan, form
         return y
 
     @staticmethod
@@ -2126,25 +2135,21 @@ class Conv1x1Fn(torch.autograd.Function):
         B, I = x.shape[:2]
         O = w.shape[0]
         dy, dyb, P = _planes(dy, "dy")
-        lib = _lib.lib()
         form = ctx.form
         dx = dW = None
         if ctx.needs_input_grad[0]:
-            if _k18_product(I, O, P, form):
+            if ctx.plan[1]:
                 wt = transpose_2d(w.unsqueeze(0))[0]                                   # (I, O): the contraction runs along its rows
-                dx = torch.empty((B, I) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
-                _flop("K18", 2 * B * O * I * P)
-                _conv1x1_k18(dy, dyb, wt, dx, B, I, O, P, form)
+                dx = _conv1x1_k18(dy, dyb, wt, None, B, I, O, P, form)
             else:
-                dx = _lib_conv_bwd(dy, x, w.view(ctx.wshape), 0, (True, False, False), form)[0]
+                dx = _lib_conv_bwd(dy, x, w.view(ctx.wshape), 1, 0, False, (True, False, False), form)[0]
         if ctx.needs_input_grad[1]:
-            dW = torch.empty(O, I, device=x.device, dtype=torch.float32)
-            ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, O, I, P), device=x.device, dtype=torch.float32)
-            _flop("K18", 2 * B * O * I * P)
-            _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, P, form,
-                                                  _stream()), "mlagg_conv1x1_wgrad_lp")
-            dW = dW.view(ctx.wshape)
-        return dx, dW, None
+            dW = _conv1x1_wgrad(dy, dyb, x, B, O, I, P, form).view(ctx.wshape)
+        return dx, dW, None, None
+
+
+def _conv1x1_plan(O, I, P, form):
+    return ("K18" if _k18_product(O, I, P, form) else None, "K18" if _k18_product(I, O, P, form) else None, "K18")
 
 
 def _pixel_shuffle2(src, B, O, H, W, inverse):
@@ -2167,9 +2172,7 @@ class ConvT2x2Fn(torch.autograd.Function):
         B, I, H, W = x.shape
         O = weight.shape[1]
         w4 = _require(weight.permute(2, 3, 1, 0).reshape(4 * O, I).contiguous(), "weight")
-        z = torch.empty(B, 4 * O, H, W, device=x.device, dtype=torch.float32)
-        _flop("K18", 2 * B * 4 * O * I * P)
-        _conv1x1_k18(x, xb, w4, z, B, 4 * O, I, P, form)
+        z = _conv1x1_k18(x, xb, w4, None, B, 4 * O, I, P, form)
         ctx.save_for_backward(x, w4)
         ctx.form, ctx.O = form, O
         return _pixel_shuffle2(z, B, O, H, W, False)
@@ -2179,58 +2182,19 @@ class ConvT2x2Fn(torch.autograd.Function):
         x, w4 = ctx.saved_tensors
         B, I, H, W = x.shape
         O, form, P = ctx.O, ctx.form, H * W
-        lib = _lib.lib()
         dy, dyb = _map_slice(dy, "dy")                                                # a half of cat([up, skip])'s gradient: read in place
         if dy.dtype != torch.float32:
             dy, dyb = dy.float(), 0
         dyu = torch.empty(B, 4 * O, H, W, device=x.device, dtype=torch.float32)        # (B, 4 O, H, W)
-        _lib.check(lib.mlagg_pixel_unshuffle2_strided(_ptr(dy), dyb, _ptr(dyu), B, O, H, W, _stream()), "mlagg_pixel_unshuffle2_strided")
+        _lib.check(_lib.lib().mlagg_pixel_unshuffle2_strided(_ptr(dy), dyb, _ptr(dyu), B, O, H, W, _stream()),
+                   "mlagg_pixel_unshuffle2_strided")
         dx = dW = None
         if ctx.needs_input_grad[0]:
             wt = transpose_2d(w4.unsqueeze(0))[0]                                      # (I, 4 O)
-            dx = torch.empty(B, I, H, W, device=x.device, dtype=torch.float32)
-            _flop("K18", 2 * B * 4 * O * I * P)
-            _conv1x1_k18(dyu, 4 * O * P, wt, dx, B, I, 4 * O, P, form)
+            dx = _conv1x1_k18(dyu, 4 * O * P, wt, None, B, I, 4 * O, P, form)
         if ctx.needs_input_grad[1]:
-            dW4 = torch.empty(4 * O, I, device=x.device, dtype=torch.float32)
-            ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, 4 * O, I, P), device=x.device, dtype=torch.float32)
-            _flop("K18", 2 * B * 4 * O * I * P)
-            _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(dyu), 4 * O * P, _ptr(x), x.stride(0), _ptr(dW4), _ptr(ws), B, 4 * O, I, P, form,
-                                                  _stream()), "mlagg_conv1x1_wgrad_lp")
-            dW = dW4.view(2, 2, O, I).permute(3, 2, 0, 1).contiguous()
+            dW = _conv1x1_wgrad(dyu, 4 * O * P, x, B, 4 * O, I, P, form).view(2, 2, O, I).permute(3, 2, 0, 1).contiguous()
         return dx, dW, None
-
-
-def conv_t2x2_supported(x, weight, stride, padding, output_padding, dilation, groups, form=_DTYPE_BF16X3):
-    """A kernel-2 / stride-2 transposed convolution (no padding) on an fp32 device map whose three products K18 takes."""
-    if not (K18 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and groups == 1):
-        return False
-    if tuple(weight.shape[2:]) != (2, 2) or any(int(v) != 2 for v in stride) or any(int(v) != 0 for v in padding) or \
-            any(int(v) != 0 for v in output_padding) or any(int(v) != 1 for v in dilation):
-        return False
-    I, O = int(weight.shape[0]), int(weight.shape[1])
-    H, W = int(x.shape[2]), int(x.shape[3])
-    P = H * W
-    return W % 2 == 0 and P % 16 == 0 and _k18_product(4 * O, I, P, form) and _k18_product(I, 4 * O, P, form)
-
-
-def conv_t2x2(x, weight, form=_DTYPE_BF16X3):
-    return ConvT2x2Fn.apply(x, weight, form)
-
-
-def conv1x1_supported(x, weight, stride, padding, dilation, groups, form=_DTYPE_BF16X3):
-    """A 1 x 1, stride-1, dense convolution on an fp32 device map whose weight gradient (at least) runs on K18 in operand form `form`."""
-    if not (K18 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and groups == 1):
-        return False
-    if tuple(weight.shape[2:]) != (1, 1) or any(int(v) != 1 for v in stride) or any(int(v) != 0 for v in padding) or \
-            any(int(v) != 1 for v in dilation):
-        return False
-    P = int(x.shape[2] * x.shape[3])
-    return P >= (K18_WGRAD_MIN_PIXELS if form == _DTYPE_BF16X3 else LP_K_MIN_PIXELS) and P % 16 == 0
-
-
-def conv1x1(x, weight, form=_DTYPE_BF16X3):
-    return Conv1x1Fn.apply(x, weight, form)
 
 
 K19 = _os.environ.get("MLAGG_K19", "1") == "1"
@@ -2261,7 +2225,11 @@ def _k19_product(O, I, H, W, form=_DTYPE_BF16X3):
     return K19 and H * W >= floor and bool(_lib.lib().mlagg_conv3x3_supported(O, I, H, W))
 
 
-def _conv3x3_k19(x, xb, w, transposed, O, I, H, W, form=_DTYPE_BF16X3, out=None):
+def _conv3x3_plan(O, I, H, W, form):
+    return tuple("K19" if on else None for on in (_k19_product(O, I, H, W, form), _k19_product(I, O, H, W, form), _k19_wgrad(O, I, H, W, form)))
+
+
+def _conv3x3_k19(x, xb, w, transposed, O, I, H, W, form, out=None):
     lib = _lib.lib()
     B = x.shape[0]
     y = torch.empty(B, O, H, W, device=x.device, dtype=torch.float32) if out is None else out
@@ -2273,22 +2241,20 @@ def _conv3x3_k19(x, xb, w, transposed, O, I, H, W, form=_DTYPE_BF16X3, out=None)
 
 
 class Conv3x3Fn(torch.autograd.Function):
-    """y = conv2d(x, W, padding=1) for a dense 3 x 3 kernel (stride 1, no bias): forward and data gradient on K19 (nine shifted
-    split-bf16 GEMMs straight on the NCHW maps) where it beats the library's Winograd kernels, the weight gradient on the library."""
+    """y = conv2d(x, W, padding=1) for a dense 3 x 3 kernel (stride 1, no bias): each product on K19 (nine shifted GEMMs straight on
+    the NCHW maps) or on the library as the plan says (_conv3x3_plan unless one is given)."""
 
     @staticmethod
-    def forward(ctx, x, weight, form=_DTYPE_BF16X3, slot=None):
+    def forward(ctx, x, weight, form=_DTYPE_BF16X3, slot=None, plan=None):
         ctx.slot = slot
         x, xb, P = _planes(x, "x")
         B, I, H, W = x.shape
         O = weight.shape[0]
+        plan = plan or _conv3x3_plan(O, I, H, W, form)
         w = _require(weight.contiguous(), "weight")
-        if _k19_product(O, I, H, W, form):
-            y = _conv3x3_k19(x, xb, w, False, O, I, H, W, form)
-        else:
-            y = _lib_conv_fwd(x, w, 1, form)
+        y = _conv3x3_k19(x, xb, w, False, O, I, H, W, form) if plan[0] else _lib_conv(x, w, 1, 1, False, form)
         ctx.save_for_backward(x, w)
-        ctx.form = form
+        ctx.plan, ctx.form = plan, form
         return y
 
     @staticmethod
@@ -2296,18 +2262,18 @@ class Conv3x3Fn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         B, I, H, W = x.shape
         O = w.shape[0]
-        form = ctx.form
+        (_, dgrad, wgrad), form = ctx.plan, ctx.form
         dx = dW = None
         if ctx.needs_input_grad[0]:
-            if _k19_product(I, O, H, W, form):
+            if dgrad:
                 dy, dyb, _ = _planes(dy, "dy")
                 out = ctx.slot.view() if ctx.slot is not None else None          # a piece of split_planes: written where the map's gradient lives
                 dx = _conv3x3_k19(dy, dyb, w, True, I, O, H, W, form, out)
             else:
-                dx = _lib_conv_bwd(dy, x, w, 1, (True, False, False), form)[0]
+                dx = _lib_conv_bwd(dy, x, w, 1, 1, False, (True, False, False), form)[0]
         if ctx.needs_input_grad[1]:
-            lib = _lib.lib()
-            if _k19_wgrad(O, I, H, W, form):
+            if wgrad:
+                lib = _lib.lib()
                 dy, dyb, _ = _planes(dy, "dy")
                 dW = torch.empty(O, I, 3, 3, device=x.device, dtype=torch.float32)
                 ws = torch.empty(lib.mlagg_conv3x3_wgrad_workspace_floats(B, O, I, H, W), device=x.device, dtype=torch.float32)
@@ -2315,26 +2281,8 @@ class Conv3x3Fn(torch.autograd.Function):
                 _lib.check(lib.mlagg_conv3x3_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, H, W, form,
                                                       _stream()), "mlagg_conv3x3_wgrad_lp")
             else:
-                dyc = dy.contiguous()
-                dW = _lib_conv_bwd(dyc, x, w, 1, (False, True, False), form)[1]
-        return dx, dW, None, None
-
-
-def conv3x3_supported(x, weight, stride, padding, dilation, groups, form=_DTYPE_BF16X3):
-    """A dense 3 x 3, stride-1, padding-1 convolution on an fp32 device map whose forward or data gradient runs on K19 (16-bit operand
-    forms: or its weight gradient -- the one-channel stem)."""
-    if not (K19 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and groups == 1):
-        return False
-    if tuple(weight.shape[2:]) != (3, 3) or any(int(v) != 1 for v in stride) or any(int(v) != 1 for v in padding) or \
-            any(int(v) != 1 for v in dilation):
-        return False
-    O, I = int(weight.shape[0]), int(weight.shape[1])
-    H, W = int(x.shape[2]), int(x.shape[3])
-    return _k19_product(O, I, H, W, form) or _k19_product(I, O, H, W, form) or (form != _DTYPE_BF16X3 and _k19_wgrad(O, I, H, W, form))
-
-
-def conv3x3(x, weight, form=_DTYPE_BF16X3):
-    return Conv3x3Fn.apply(x, weight, form, _claim(x))
+                dW = _lib_conv_bwd(dy.contiguous(), x, w, 1, 1, False, (False, True, False), form)[1]
+        return dx, dW, None, None, None
 
 
 # K19t: the 3 x 3, stride-2, padding-1 transposed convolution of PatchExpand (T:506-513) -- forward, data gradient and weight gradient
@@ -2349,6 +2297,11 @@ K19T_WGRAD = _os.environ.get("MLAGG_K19T_WGRAD", "0") == "1"
 def _k19t_shape(O, I, H, W, form=_DTYPE_BF16X3):
     floor = K19_MIN_PIXELS if form == _DTYPE_BF16X3 else LP_K_MIN_PIXELS
     return K19T and H * W >= floor and bool(_lib.lib().mlagg_conv3x3_s2t_supported(O, I, H, W))
+
+
+def _s2t_plan(O, I, H, W, form):
+    on = _k19t_shape(O, I, H, W, form)
+    return ("K19t" if on else None,) * 2 + ("K19t" if on and K19T_WGRAD else None,)
 
 
 def _k19t_fwd(x, xb, w, O, I, H, W, form):
@@ -2384,34 +2337,20 @@ def _k19t_wgrad(x, xb, dy, O, I, H, W, form):
     return dW
 
 
-def _lib_convt_s2(x, w, form):
-    if form == _DTYPE_BF16X3:
-        return torch.nn.functional.conv_transpose2d(x, w, None, 2, 1)
-    t = _FORM_TORCH[form]
-    return torch.nn.functional.conv_transpose2d(x.to(t), w.to(t), None, 2, 1).float()
-
-
-def _lib_convt_s2_bwd(dy, x, w, mask, form):
-    if form != _DTYPE_BF16X3:
-        t = _FORM_TORCH[form]
-        dy, x, w = dy.to(t), x.to(t), w.to(t)
-    out = torch.ops.aten.convolution_backward(dy.contiguous(), x, w, None, (2, 2), (1, 1), (1, 1), True, (0, 0), 1, mask)
-    return [None if o is None else o.float() for o in out]
-
-
 class ConvT3x3S2Fn(torch.autograd.Function):
-    """y = conv_transpose2d(x, W, stride=2, padding=1) for a dense 3 x 3 kernel (no bias), y (B, O, 2H - 1, 2W - 1): the three products
-    on K19t in operand form `form`, each one on the library where the kernel does not take it."""
+    """y = conv_transpose2d(x, W, stride=2, padding=1) for a dense 3 x 3 kernel (no bias), y (B, O, 2H - 1, 2W - 1): each product on
+    K19t or on the library as the plan says (_s2t_plan unless one is given)."""
 
     @staticmethod
-    def forward(ctx, x, weight, form=_DTYPE_BF16X3):
+    def forward(ctx, x, weight, form=_DTYPE_BF16X3, plan=None):
         x, xb, _ = _planes(x, "x")
         B, I, H, W = x.shape
         O = int(weight.shape[1])
+        plan = plan or _s2t_plan(O, I, H, W, form)
         w = _require(weight.contiguous(), "weight")
-        y = _k19t_fwd(x, xb, w, O, I, H, W, form) if _k19t_shape(O, I, H, W, form) else _lib_convt_s2(x, w, form)
+        y = _k19t_fwd(x, xb, w, O, I, H, W, form) if plan[0] else _lib_conv(x, w, 2, 1, True, form)
         ctx.save_for_backward(x, w)
-        ctx.form = form
+        ctx.plan, ctx.form = plan, form
         return y
 
     @staticmethod
@@ -2419,30 +2358,100 @@ class ConvT3x3S2Fn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         B, I, H, W = x.shape
         O = int(w.shape[1])
-        form = ctx.form
-        on = _k19t_shape(O, I, H, W, form)
-        if on and (dy.stride(3) != 1 or dy.data_ptr() % 4):
+        (_, dgrad, wgrad), form = ctx.plan, ctx.form
+        if dgrad and (dy.stride(3) != 1 or dy.data_ptr() % 4):
             dy = dy.contiguous()                                  # any channel / row stride is fine, a strided row is not
         dx = dW = None
         if ctx.needs_input_grad[0]:
-            dx = _k19t_dgrad(dy, w, O, I, H, W, form) if on else _lib_convt_s2_bwd(dy, x, w, (True, False, False), form)[0]
+            dx = _k19t_dgrad(dy, w, O, I, H, W, form) if dgrad else _lib_conv_bwd(dy, x, w, 2, 1, True, (True, False, False), form)[0]
         if ctx.needs_input_grad[1]:
-            if on and K19T_WGRAD:
-                dW = _k19t_wgrad(x, x.stride(0), dy, O, I, H, W, form)
-            else:
-                dW = _lib_convt_s2_bwd(dy, x, w, (False, True, False), form)[1]
-        return dx, dW, None
+            dW = _k19t_wgrad(x, x.stride(0), dy, O, I, H, W, form) if wgrad else _lib_conv_bwd(dy, x, w, 2, 1, True, (False, True, False), form)[1]
+        return dx, dW, None, None
+
+
+def _fp32_map(x, nd):
+    """An fp32 device map with nd spatial axes?  (Reads attributes only: the plan tests stand a namespace in for a device tensor.)"""
+    return x.is_cuda and x.dtype == torch.float32 and x.dim() == nd + 2
+
+
+def _all(v, n):
+    return all(int(a) == n for a in v)
+
+
+def conv_plan(x, weight, stride, padding, dilation, groups, transposed, output_padding, form):
+    """Where each product of the bias-free 2-D convolution (transposed: conv_transpose2d) of `x` with `weight` runs, in operand form
+    `form`: (forward, data gradient, weight gradient), each "K18", "K19", "K19t" or None (the library in the arithmetic of `form`) --
+    or None where the whole layer is the library's.  A function of shapes, geometry, form and the switches above only."""
+    if not (_fp32_map(x, 2) and groups == 1 and _all(dilation, 1) and _all(output_padding, 0)):
+        return None
+    geom = tuple(tuple(int(v) for v in t) for t in (weight.shape[2:], stride, padding)) + (bool(transposed),)
+    I, O = (int(weight.shape[0]), int(weight.shape[1])) if transposed else (int(weight.shape[1]), int(weight.shape[0]))
+    H, W = int(x.shape[2]), int(x.shape[3])
+    P, one = H * W, form != _DTYPE_BF16X3                # one: a 16-bit mode's one-product form
+    if geom[:3] == ((1, 1), (1, 1), (0, 0)):
+        # 1 x 1 on K18; a transposed one (the segmentation heads, T:549-561: the same product, weight axes exchanged) only where all
+        # three products run on it -- on the small maps the library's transposed-convolution solvers are the faster ones
+        if not (K18 and P >= (LP_K_MIN_PIXELS if one else K18_WGRAD_MIN_PIXELS) and P % 16 == 0):
+            return None
+        plan = _conv1x1_plan(O, I, P, form)
+        return None if transposed and None in plan else plan
+    if geom == ((2, 2), (2, 2), (0, 0), True):           # K18 on the tap matrix + pixel shuffle (UnetrUpBlock)
+        ok = K18 and W % 2 == 0 and P % 16 == 0 and _k18_product(4 * O, I, P, form) and _k18_product(I, 4 * O, P, form)
+        return ("K18",) * 3 if ok else None
+    if geom == ((3, 3), (1, 1), (1, 1), False):
+        # K19 where forward or data gradient take it (16-bit operand forms: or the weight gradient -- the one-channel stem)
+        plan = _conv3x3_plan(O, I, H, W, form)
+        return plan if K19 and (plan[0] or plan[1] or (one and plan[2])) else None
+    if geom == ((3, 3), (2, 2), (1, 1), True):           # K19t (PatchExpand)
+        plan = _s2t_plan(O, I, H, W, form)
+        return plan if plan[0] else None
+    return None
+
+
+def conv2d(x, weight, stride, padding, dilation, groups, transposed, output_padding, form):
+    """The bias-free 2-D convolution (transposed: conv_transpose2d) on this package's kernels as conv_plan decides, or None: the
+    caller's library path."""
+    plan = conv_plan(x, weight, stride, padding, dilation, groups, transposed, output_padding, form)
+    if plan is None:
+        return None
+    k = int(weight.shape[2])
+    if k == 1:
+        return Conv1x1Fn.apply(x, weight.permute(1, 0, 2, 3) if transposed else weight, form, plan)
+    if k == 2:
+        return ConvT2x2Fn.apply(x, weight, form)
+    if transposed:
+        return ConvT3x3S2Fn.apply(x, weight, form, plan)
+    return Conv3x3Fn.apply(x, weight, form, claim_slot(x), plan)
+
+
+# For a caller that knows the layer kind: conv_plan's layer rule for that kind, and that kind's Function on its own plan (no layer
+# rule: every product on the library where its kernel does not take it).
+def conv1x1_supported(x, weight, stride, padding, dilation, groups, form=_DTYPE_BF16X3):
+    return tuple(weight.shape[2:]) == (1, 1) and conv_plan(x, weight, stride, padding, dilation, groups, False, (0, 0), form) is not None
+
+
+def conv3x3_supported(x, weight, stride, padding, dilation, groups, form=_DTYPE_BF16X3):
+    return tuple(weight.shape[2:]) == (3, 3) and conv_plan(x, weight, stride, padding, dilation, groups, False, (0, 0), form) is not None
+
+
+def conv_t2x2_supported(x, weight, stride, padding, output_padding, dilation, groups, form=_DTYPE_BF16X3):
+    return tuple(weight.shape[2:]) == (2, 2) and conv_plan(x, weight, stride, padding, dilation, groups, True, output_padding, form) is not None
 
 
 def conv3x3_s2t_supported(x, weight, stride, padding, output_padding, dilation, groups, form=_DTYPE_BF16X3):
-    """A dense 3 x 3 transposed convolution with stride 2, padding 1, no output padding, on an fp32 device map that K19t takes."""
-    if not (K19T and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and groups == 1):
-        return False
-    if tuple(weight.shape[2:]) != (3, 3) or any(int(v) != 2 for v in stride) or any(int(v) != 1 for v in padding) or \
-            any(int(v) != 0 for v in output_padding) or any(int(v) != 1 for v in dilation):
-        return False
-    I, O = int(weight.shape[0]), int(weight.shape[1])
-    return _k19t_shape(O, I, int(x.shape[2]), int(x.shape[3]), form)
+    return tuple(weight.shape[2:]) == (3, 3) and conv_plan(x, weight, stride, padding, dilation, groups, True, output_padding, form) is not None
+
+
+def conv1x1(x, weight, form=_DTYPE_BF16X3):
+    return Conv1x1Fn.apply(x, weight, form)
+
+
+def conv3x3(x, weight, form=_DTYPE_BF16X3):
+    return Conv3x3Fn.apply(x, weight, form, claim_slot(x))
+
+
+def conv_t2x2(x, weight, form=_DTYPE_BF16X3):
+    return ConvT2x2Fn.apply(x, weight, form)
 
 
 def conv3x3_s2t(x, weight, form=_DTYPE_BF16X3):
@@ -2491,8 +2500,7 @@ class Conv3x3x3Fn(torch.autograd.Function):
             if lib.mlagg_conv3x3x3_supported(I, O, *dims):
                 dx = _conv3x3x3_k19(dy, O * dims[0] * dims[1] * dims[2], w, True, I, O, dims)
             else:                                               # contraction (the layer's output channels) not a multiple of 16
-                dx = torch.ops.aten.convolution_backward(dy, x, w, None, (1, 1, 1), (1, 1, 1), (1, 1, 1), False, (0, 0, 0), 1,
-                                                         (True, False, False))[0]
+                dx = _lib_conv_bwd(dy, x, w, 1, 1, False, (True, False, False), _DTYPE_BF16X3)[0]
         if ctx.needs_input_grad[1]:
             B = x.shape[0]
             if K19_3D_WGRAD and lib.mlagg_conv3x3x3_wgrad_supported(O, I, *dims):
@@ -2506,11 +2514,8 @@ class Conv3x3x3Fn(torch.autograd.Function):
 
 
 def conv3x3x3_supported(x, weight, stride, padding):
-    if not (K19_3D and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3)):
-        return False
-    if any(int(v) != 1 for v in stride) or any(int(v) != 1 for v in padding):
-        return False
-    return bool(_lib.lib().mlagg_conv3x3x3_supported(int(weight.shape[0]), int(weight.shape[1]), *(int(v) for v in x.shape[2:])))
+    return (K19_3D and _fp32_map(x, 3) and tuple(weight.shape[2:]) == (3, 3, 3) and _all(stride, 1) and _all(padding, 1)
+            and bool(_lib.lib().mlagg_conv3x3x3_supported(int(weight.shape[0]), int(weight.shape[1]), *(int(v) for v in x.shape[2:]))))
 
 
 def _pad_geometry(D, H, W, stride, wide=False):
@@ -2531,10 +2536,9 @@ K16 = _os.environ.get("MLAGG_K16", "1") == "1"
 
 def conv_wgrad_supported(x, weight, stride, padding):
     """Kernel 3 with padding 1 or kernel 1 with padding 0, isotropic, stride 1 (2-D and 3-D) or 2 (3-D), fp32 device maps."""
-    nd = x.dim() - 2
-    k = weight.shape[2]
-    return (x.is_cuda and x.dtype == torch.float32 and nd in (2, 3) and all(int(v) == k for v in weight.shape[2:]) and k in (1, 3)
-            and all(int(v) == k // 2 for v in padding) and len(set(int(v) for v in stride)) == 1
+    nd, k = x.dim() - 2, int(weight.shape[2])
+    return (nd in (2, 3) and _fp32_map(x, nd) and k in (1, 3) and _all(weight.shape[2:], k) and _all(padding, k // 2)
+            and len(set(int(v) for v in stride)) == 1
             and (int(stride[0]) == 1 or (int(stride[0]) == 2 and nd == 3 and all(int(v) > 1 for v in x.shape[2:]))))
 
 
@@ -2668,24 +2672,21 @@ class ConvNdFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, stride, padding):
-        conv = torch.nn.functional.conv3d if x.dim() == 5 else torch.nn.functional.conv2d
-        y = conv(x, weight, None, stride, padding)
+        y = _lib_conv(x, weight, stride, padding, False, _DTYPE_BF16X3)
         ctx.save_for_backward(x, weight)
-        ctx.geom = (tuple(int(v) for v in stride), tuple(int(v) for v in padding))
+        ctx.geom = (stride, padding)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         stride, padding = ctx.geom
-        nd = x.dim() - 2
         dx = dW = None
         dy = dy.contiguous()
         if ctx.needs_input_grad[0]:
-            dx = torch.ops.aten.convolution_backward(dy, x, weight, None, stride, padding, (1,) * nd, False, (0,) * nd, 1,
-                                                     (True, False, False))[0]
+            dx = _lib_conv_bwd(dy, x, weight, stride, padding, False, (True, False, False), _DTYPE_BF16X3)[0]
         if ctx.needs_input_grad[1]:
-            dW = conv_weight_grad(x, dy, int(weight.shape[2]), stride[0]).view(weight.shape)
+            dW = conv_weight_grad(x, dy, int(weight.shape[2]), stride).view(weight.shape)
         return dx, dW, None, None
 
 
@@ -2697,7 +2698,7 @@ def conv_nd(x, weight, stride, padding):
     if conv_taps_supported(x, weight, stride, padding):
         return ConvTapsFn.apply(x, weight)
     if conv_wgrad_supported(x, weight, stride, padding):
-        return ConvNdFn.apply(x, weight, tuple(stride), tuple(padding))
+        return ConvNdFn.apply(x, weight, int(stride[0]), int(padding[0]))          # isotropic: conv_wgrad_supported
     conv = torch.nn.functional.conv3d if x.dim() == 5 else torch.nn.functional.conv2d
     return conv(x, weight, None, stride, padding)
 
