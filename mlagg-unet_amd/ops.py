@@ -3,10 +3,16 @@
 PyTorch is plumbing here: device memory, the current HIP stream and autograd bookkeeping.  Every
 op requires CUDA(HIP) fp32 tensors and raises RuntimeError otherwise -- there is no eager path.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from . import _lib
+
+_launch = _lib.launch
+_stream = _lib.stream           # the raw current stream, for callers that invoke an entry point directly (tests)
+_C = _lib.CONSTANTS
 
 
 # ------------------------------------------------------------------------------------------------
@@ -16,7 +22,7 @@ from . import _lib
 # the library convolutions / small GEMMs round their OPERANDS to that type for the matrix cores.
 # ------------------------------------------------------------------------------------------------
 PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
-_LP_CODE = {torch.bfloat16: 1, torch.float16: 2}            # MLAGG_DTYPE_* of include/mlagg_hip.h
+_LP_CODE = {torch.bfloat16: _C["MLAGG_DTYPE_BF16"], torch.float16: _C["MLAGG_DTYPE_F16"]}
 import threading as _threading
 
 
@@ -74,8 +80,8 @@ def conv_dtype():
 # work, no cast kernels, no NHWC transposes.  Maps below LP_K_MIN_PIXELS pixels, strided and transposed convolutions stay 16-bit library
 # calls.
 LP_K_MIN_PIXELS = int(_os.environ.get("MLAGG_LP_K_MIN_PIXELS", "1024"))
-_DTYPE_BF16X3 = 3
-_FORM_TORCH = {1: torch.bfloat16, 2: torch.float16, 3: torch.float32}
+_DTYPE_BF16X3 = _C["MLAGG_DTYPE_BF16X3"]
+_FORM_TORCH = {_LP_CODE[torch.bfloat16]: torch.bfloat16, _LP_CODE[torch.float16]: torch.float16, _DTYPE_BF16X3: torch.float32}
 
 
 def conv_form():
@@ -111,13 +117,6 @@ def _flop(family, n):
         FLOP_COUNT[family] = FLOP_COUNT.get(family, 0) + int(n)
 
 
-def _stream():
-    """Raw handle of torch's current HIP stream on the current device.  Every kernel wrapper asks for it: the two C calls below cost
-    0.3 us, `torch.cuda.current_stream().cuda_stream` 9 us (tools/host_profile.py: 2.6 ms of host time per direction and step, and
-    the 224 x 224 configurations are bound by the host's enqueue rate)."""
-    return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
-
-
 def _require(t, name, shape=None):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
         raise RuntimeError(f"{name}: expected a float32 tensor on the MI355X device, got "
@@ -141,12 +140,10 @@ class SelectiveScanFn(torch.autograd.Function):
         C = _require(C.contiguous(), "C", (b, g, n, L))
         D = None if D is None else _require(D.contiguous(), "D", (d,))
         delta_bias = None if delta_bias is None else _require(delta_bias.contiguous(), "delta_bias", (d,))
-        lib = _lib.lib()
         out = torch.empty_like(u)
-        state = torch.empty(lib.mlagg_selscan_state_floats(b, d, L, n), device=u.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_selscan_fwd(_ptr(u), _ptr(delta), _ptr(A), _ptr(B), _ptr(C), _ptr(D),
-                                         _ptr(delta_bias), _ptr(out), _ptr(state), b, d, L, n, g,
-                                         int(bool(delta_softplus)), _stream()), "mlagg_selscan_fwd")
+        state = torch.empty(_lib.lib().mlagg_selscan_state_floats(b, d, L, n), device=u.device, dtype=torch.float32)
+        _launch("mlagg_selscan_fwd", _ptr(u), _ptr(delta), _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(delta_bias), _ptr(out), _ptr(state), b,
+                d, L, n, g, int(bool(delta_softplus)))
         ctx.save_for_backward(u, delta, A, B, C, D, delta_bias, state)
         ctx.delta_softplus = bool(delta_softplus)
         return out
@@ -157,16 +154,14 @@ class SelectiveScanFn(torch.autograd.Function):
         b, d, L = u.shape
         n, g = A.shape[1], B.shape[1]
         dout = _require(dout.contiguous(), "dout", (b, d, L))
-        lib = _lib.lib()
         du, ddelta = torch.empty_like(u), torch.empty_like(u)
         dA, dB, dC = torch.empty_like(A), torch.empty_like(B), torch.empty_like(C)
         dD = None if D is None else torch.empty_like(D)
         dbias = None if delta_bias is None else torch.empty_like(delta_bias)
-        ws = torch.empty(lib.mlagg_selscan_bwd_workspace_floats(b, d, L, n), device=u.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_selscan_bwd(_ptr(u), _ptr(delta), _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(delta_bias),
-                                         _ptr(dout), _ptr(state), _ptr(du), _ptr(ddelta), _ptr(dA), _ptr(dB),
-                                         _ptr(dC), _ptr(dD), _ptr(dbias), _ptr(ws), b, d, L, n, g,
-                                         int(ctx.delta_softplus), _stream()), "mlagg_selscan_bwd")
+        ws = torch.empty(_lib.lib().mlagg_selscan_bwd_workspace_floats(b, d, L, n), device=u.device, dtype=torch.float32)
+        _launch("mlagg_selscan_bwd", _ptr(u), _ptr(delta), _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(delta_bias), _ptr(dout), _ptr(state),
+                _ptr(du), _ptr(ddelta), _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD), _ptr(dbias), _ptr(ws), b, d, L, n, g,
+                int(ctx.delta_softplus))
         return du, ddelta, dA, dB, dC, dD, dbias, None
 
 
@@ -197,12 +192,10 @@ class SelectiveScanLowRankFn(torch.autograd.Function):
         C = _require(C.contiguous(), "C", (b, g, n, L))
         D = None if D is None else _require(D.contiguous(), "D", (d,))
         delta_bias = None if delta_bias is None else _require(delta_bias.contiguous(), "delta_bias", (d,))
-        lib = _lib.lib()
         out = torch.empty_like(u)
-        state = torch.empty(lib.mlagg_selscan_state_floats(b, d, L, n), device=u.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_selscan_lowrank_fwd(_ptr(u), _ptr(dtr), _ptr(Wdt), R, _ptr(A), _ptr(B), _ptr(C), _ptr(D),
-                                                 _ptr(delta_bias), _ptr(out), _ptr(state), b, d, L, n, g,
-                                                 int(bool(delta_softplus)), _stream()), "mlagg_selscan_lowrank_fwd")
+        state = torch.empty(_lib.lib().mlagg_selscan_state_floats(b, d, L, n), device=u.device, dtype=torch.float32)
+        _launch("mlagg_selscan_lowrank_fwd", _ptr(u), _ptr(dtr), _ptr(Wdt), R, _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(delta_bias),
+                _ptr(out), _ptr(state), b, d, L, n, g, int(bool(delta_softplus)))
         ctx.save_for_backward(u, dtr, Wdt, A, B, C, D, delta_bias, state)
         ctx.delta_softplus = bool(delta_softplus)
         return out
@@ -213,16 +206,14 @@ class SelectiveScanLowRankFn(torch.autograd.Function):
         b, d, L = u.shape
         n, g, R = A.shape[1], B.shape[1], dtr.shape[2]
         dout = _require(dout.contiguous(), "dout", (b, d, L))
-        lib = _lib.lib()
         du, ddtr, dW = torch.empty_like(u), torch.empty_like(dtr), torch.empty_like(Wdt)
         dA, dB, dC = torch.empty_like(A), torch.empty_like(B), torch.empty_like(C)
         dD = None if D is None else torch.empty_like(D)
         dbias = None if delta_bias is None else torch.empty_like(delta_bias)
-        ws = torch.empty(lib.mlagg_selscan_bwd_workspace_floats(b, d, L, n), device=u.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_selscan_lowrank_bwd(_ptr(u), _ptr(dtr), _ptr(Wdt), R, _ptr(A), _ptr(B), _ptr(C), _ptr(D),
-                                                 _ptr(delta_bias), _ptr(dout), _ptr(state), _ptr(du), _ptr(ddtr), _ptr(dW),
-                                                 _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD), _ptr(dbias), _ptr(ws), b, d, L, n, g,
-                                                 int(ctx.delta_softplus), _stream()), "mlagg_selscan_lowrank_bwd")
+        ws = torch.empty(_lib.lib().mlagg_selscan_bwd_workspace_floats(b, d, L, n), device=u.device, dtype=torch.float32)
+        _launch("mlagg_selscan_lowrank_bwd", _ptr(u), _ptr(dtr), _ptr(Wdt), R, _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(delta_bias),
+                _ptr(dout), _ptr(state), _ptr(du), _ptr(ddtr), _ptr(dW), _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD), _ptr(dbias), _ptr(ws), b,
+                d, L, n, g, int(ctx.delta_softplus))
         return du, ddtr, dW, dA, dB, dC, dD, dbias, None
 
 
@@ -301,8 +292,8 @@ class MsmmScanFn(torch.autograd.Function):
         y = torch.empty(B, L, dI, device=xc.device, dtype=torch.float32)
         state = torch.empty(lib.mlagg_msmm_scan_state_floats(B, L), device=xc.device, dtype=torch.float32)
         ws = torch.empty(lib.mlagg_msmm_scan_fwd_workspace_floats(B, L), device=xc.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_msmm_scan_fwd(_ptr(xc), _ptr(xdbl), _ptr(idx), _ptr(Wdt), _ptr(A), _ptr(D), _ptr(bias), _ptr(y), _ptr(state),
-                                           _ptr(ws), B, L, _stream()), "mlagg_msmm_scan_fwd")
+        _launch("mlagg_msmm_scan_fwd", _ptr(xc), _ptr(xdbl), _ptr(idx), _ptr(Wdt), _ptr(A), _ptr(D), _ptr(bias), _ptr(y), _ptr(state),
+                _ptr(ws), B, L)
         ctx.save_for_backward(xc, xdbl, idx, Wdt, A, D, bias, state)
         return y
 
@@ -311,16 +302,14 @@ class MsmmScanFn(torch.autograd.Function):
         xc, xdbl, idx, Wdt, A, D, bias, state = ctx.saved_tensors
         B, L, dI = xc.shape
         dy = _require(dy.contiguous(), "dy", (B, L, dI))
-        lib = _lib.lib()
         dev = xc.device
         dxc, dxdbl = torch.empty_like(xc), torch.empty_like(xdbl)
         dW, dA = torch.empty_like(Wdt), torch.empty_like(A)
         dD = None if D is None else torch.empty_like(D)
         dbias = None if bias is None else torch.empty_like(bias)
-        ws = torch.empty(lib.mlagg_msmm_scan_bwd_workspace_floats(B, L), device=dev, dtype=torch.float32)
-        _lib.check(lib.mlagg_msmm_scan_bwd(_ptr(xc), _ptr(xdbl), _ptr(idx), _ptr(Wdt), _ptr(A), _ptr(D), _ptr(bias), _ptr(dy), _ptr(state),
-                                           _ptr(dxc), _ptr(dxdbl), _ptr(dW), _ptr(dA), _ptr(dD), _ptr(dbias), _ptr(ws), B, L, _stream()),
-                   "mlagg_msmm_scan_bwd")
+        ws = torch.empty(_lib.lib().mlagg_msmm_scan_bwd_workspace_floats(B, L), device=dev, dtype=torch.float32)
+        _launch("mlagg_msmm_scan_bwd", _ptr(xc), _ptr(xdbl), _ptr(idx), _ptr(Wdt), _ptr(A), _ptr(D), _ptr(bias), _ptr(dy), _ptr(state),
+                _ptr(dxc), _ptr(dxdbl), _ptr(dW), _ptr(dA), _ptr(dD), _ptr(dbias), _ptr(ws), B, L)
         return dxc, dxdbl, None, dW, dA, dD, dbias
 
 
@@ -457,8 +446,7 @@ def transpose_2d_into(src, dst):
     if not (src.stride(2) == 1 and src.stride(1) == C and src.stride(0) >= R * C and src.data_ptr() % 16 == 0
             and (C % 4 or src.stride(0) % 4 == 0)):
         src = src.contiguous()
-    _lib.check(_lib.lib().mlagg_transpose_2d_into(_ptr(src), src.stride(0), _ptr(dst), dst.stride(0), B, R, C, _stream()),
-               "mlagg_transpose_2d_into")
+    _launch("mlagg_transpose_2d_into", _ptr(src), src.stride(0), _ptr(dst), dst.stride(0), B, R, C)
     return dst
 
 
@@ -494,8 +482,7 @@ class DWConv3x3Fn(torch.autograd.Function):
         w = _require(weight.reshape(C, 9).contiguous(), "weight")
         y = torch.empty(B, N, C, device=x.device, dtype=torch.float32)
         pre = torch.empty_like(y) if silu else None      # pre-activation, needed by SiLU's backward
-        _lib.check(_lib.lib().mlagg_dwconv3x3_fwd(_ptr(x), xs, _ptr(w), _ptr(bias), _ptr(res), _ptr(y), C, _ptr(pre), B, H, W, C,
-                                                  int(silu), _stream()), "mlagg_dwconv3x3_fwd")
+        _launch("mlagg_dwconv3x3_fwd", _ptr(x), xs, _ptr(w), _ptr(bias), _ptr(res), _ptr(y), C, _ptr(pre), B, H, W, C, int(silu))
         ctx.save_for_backward(x, w, pre)
         ctx.geom = (H, W, bool(silu), bias is not None, weight.shape)
         ctx.has_res = res is not None
@@ -510,11 +497,9 @@ class DWConv3x3Fn(torch.autograd.Function):
         dx, dxs = _grad_out(ctx.slot, (B, N, C), x.device)
         dw = torch.empty(C, 9, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32) if has_bias else None
-        lib = _lib.lib()
-        ws = torch.empty(lib.mlagg_dwconv3x3_bwd_workspace_floats(B, H, W, C), device=x.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_dwconv3x3_bwd(_ptr(x), x.stride(1), _ptr(w), _ptr(dy), dys, _ptr(pre), _ptr(dx), dxs,
-                                           _ptr(dw), _ptr(db), _ptr(ws), B, H, W, C, int(silu), _stream()),
-                   "mlagg_dwconv3x3_bwd")
+        ws = torch.empty(_lib.lib().mlagg_dwconv3x3_bwd_workspace_floats(B, H, W, C), device=x.device, dtype=torch.float32)
+        _launch("mlagg_dwconv3x3_bwd", _ptr(x), x.stride(1), _ptr(w), _ptr(dy), dys, _ptr(pre), _ptr(dx), dxs, _ptr(dw), _ptr(db), _ptr(ws),
+                B, H, W, C, int(silu))
         return dx, dw.reshape(wshape), db, None, None, None, None, (dy if ctx.has_res else None)
 
 
@@ -534,8 +519,7 @@ class DWConvGatedFn(torch.autograd.Function):
         w = _require(weight.reshape(C, 9).contiguous(), "weight")
         y = torch.empty(B, N, C, device=x.device, dtype=torch.float32)
         pre = torch.empty_like(y)
-        _lib.check(_lib.lib().mlagg_dwconv3x3_gated_fwd(_ptr(x), xs, _ptr(w), _ptr(bias), _ptr(gate), gs, _ptr(y), C, _ptr(pre), B, H, W, C,
-                                                        _stream()), "mlagg_dwconv3x3_gated_fwd")
+        _launch("mlagg_dwconv3x3_gated_fwd", _ptr(x), xs, _ptr(w), _ptr(bias), _ptr(gate), gs, _ptr(y), C, _ptr(pre), B, H, W, C)
         ctx.save_for_backward(x, gate, w, pre)
         ctx.geom = (H, W, bias is not None, weight.shape)
         return y
@@ -550,11 +534,9 @@ class DWConvGatedFn(torch.autograd.Function):
         dgate, dgs = _grad_out(ctx.slots[1], (B, N, C), x.device)
         dw = torch.empty(C, 9, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32) if has_bias else None
-        lib = _lib.lib()
-        ws = torch.empty(lib.mlagg_dwconv3x3_bwd_workspace_floats(B, H, W, C), device=x.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_dwconv3x3_gated_bwd(_ptr(x), x.stride(1), _ptr(w), _ptr(dy), dys, _ptr(pre), _ptr(gate), gate.stride(1),
-                                                 _ptr(dx), dxs, _ptr(dgate), dgs, _ptr(dw), _ptr(db), _ptr(ws), B, H, W, C, _stream()),
-                   "mlagg_dwconv3x3_gated_bwd")
+        ws = torch.empty(_lib.lib().mlagg_dwconv3x3_bwd_workspace_floats(B, H, W, C), device=x.device, dtype=torch.float32)
+        _launch("mlagg_dwconv3x3_gated_bwd", _ptr(x), x.stride(1), _ptr(w), _ptr(dy), dys, _ptr(pre), _ptr(gate), gate.stride(1), _ptr(dx),
+                dxs, _ptr(dgate), dgs, _ptr(dw), _ptr(db), _ptr(ws), B, H, W, C)
         return dx, dgate, dw.reshape(wshape), db, None, None, None, None
 
 
@@ -582,8 +564,7 @@ class DWConv3dFn(torch.autograd.Function):
         bias = None if bias is None else _require(bias.contiguous(), "bias", (C,))
         y = torch.empty(B, L, C, device=x.device, dtype=torch.float32)
         pre = torch.empty_like(y) if silu else None
-        _lib.check(_lib.lib().mlagg_dwconv3d_fwd(_ptr(x), xs, _ptr(w), _ptr(bias), _ptr(y), C, _ptr(pre), B, D, H, W, C,
-                                                 int(silu), _stream()), "mlagg_dwconv3d_fwd")
+        _launch("mlagg_dwconv3d_fwd", _ptr(x), xs, _ptr(w), _ptr(bias), _ptr(y), C, _ptr(pre), B, D, H, W, C, int(silu))
         ctx.save_for_backward(x, w, pre)
         ctx.geom = (D, H, W, bool(silu), bias is not None, weight.shape)
         return y
@@ -597,10 +578,9 @@ class DWConv3dFn(torch.autograd.Function):
         dx = torch.empty(B, L, C, device=x.device, dtype=torch.float32)
         dw = torch.empty(C, 27, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32) if has_bias else None
-        lib = _lib.lib()
-        ws = torch.empty(lib.mlagg_dwconv3d_bwd_workspace_floats(B, D, H, W, C), device=x.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_dwconv3d_bwd(_ptr(x), x.stride(1), _ptr(w), _ptr(dy), dys, _ptr(pre), _ptr(dx), C, _ptr(dw), _ptr(db),
-                                          _ptr(ws), B, D, H, W, C, int(silu), _stream()), "mlagg_dwconv3d_bwd")
+        ws = torch.empty(_lib.lib().mlagg_dwconv3d_bwd_workspace_floats(B, D, H, W, C), device=x.device, dtype=torch.float32)
+        _launch("mlagg_dwconv3d_bwd", _ptr(x), x.stride(1), _ptr(w), _ptr(dy), dys, _ptr(pre), _ptr(dx), C, _ptr(dw), _ptr(db), _ptr(ws), B,
+                D, H, W, C, int(silu))
         return dx, dw.reshape(wshape), db, None, None
 
 
@@ -625,13 +605,12 @@ class SelectiveScan1Fn(torch.autograd.Function):
         Cs = _require(Cs.contiguous(), "Cs", (B, K, L))
         Wdt = _require(Wdt.contiguous(), "Wdt", (K * C, R))
         A, D, bias = (_require(v.reshape(-1).contiguous(), n, (K * C,)) for v, n in ((A, "A"), (D, "D"), (bias, "delta_bias")))
-        lib = _lib.lib()
         yk = torch.empty(B, L, K * C, device=tok.device, dtype=torch.float32)
-        state = torch.empty(lib.mlagg_selscan1_state_floats(B, L, C, K), device=tok.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_selscan1_fwd(_ptr(tok), ts, _ptr(idx), _ptr(dtr), _ptr(Bs), _ptr(Cs), _ptr(Wdt), R, _ptr(A), _ptr(D),
-                                          _ptr(bias), _ptr(yk), _ptr(state), B, L, C, K, _stream()), "mlagg_selscan1_fwd")
+        state = torch.empty(_lib.lib().mlagg_selscan1_state_floats(B, L, C, K), device=tok.device, dtype=torch.float32)
+        _launch("mlagg_selscan1_fwd", _ptr(tok), ts, _ptr(idx), _ptr(dtr), _ptr(Bs), _ptr(Cs), _ptr(Wdt), R, _ptr(A), _ptr(D), _ptr(bias),
+                _ptr(yk), _ptr(state), B, L, C, K)
         y = torch.empty(B, L, C, device=tok.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_block_sum(_ptr(yk), _ptr(y), B * L, K, C, _stream()), "mlagg_block_sum")
+        _launch("mlagg_block_sum", _ptr(yk), _ptr(y), B * L, K, C)
         ctx.save_for_backward(tok, idx, dtr, Bs, Cs, Wdt, A, D, bias, state)
         return y
 
@@ -641,17 +620,15 @@ class SelectiveScan1Fn(torch.autograd.Function):
         B, L, C = tok.shape
         K, R = idx.shape[0], dtr.shape[2]
         dy, ds = _rows(dy, "dy")
-        lib = _lib.lib()
         dev = tok.device
         duk = torch.empty(B, L, K * C, device=dev, dtype=torch.float32)
         ddtr, dBs, dCs = torch.empty_like(dtr), torch.empty_like(Bs), torch.empty_like(Cs)
         dpar = torch.empty(K * C, 3 + R, device=dev, dtype=torch.float32)
-        ws = torch.empty(lib.mlagg_selscan1_bwd_workspace_floats(B, L, C, K, R), device=dev, dtype=torch.float32)
-        _lib.check(lib.mlagg_selscan1_bwd(_ptr(tok), tok.stride(1), _ptr(idx), _ptr(dtr), _ptr(Bs), _ptr(Cs), _ptr(Wdt), R, _ptr(A),
-                                          _ptr(D), _ptr(bias), _ptr(dy), ds, _ptr(state), _ptr(duk), _ptr(ddtr), _ptr(dBs), _ptr(dCs),
-                                          _ptr(dpar), _ptr(ws), B, L, C, K, _stream()), "mlagg_selscan1_bwd")
+        ws = torch.empty(_lib.lib().mlagg_selscan1_bwd_workspace_floats(B, L, C, K, R), device=dev, dtype=torch.float32)
+        _launch("mlagg_selscan1_bwd", _ptr(tok), tok.stride(1), _ptr(idx), _ptr(dtr), _ptr(Bs), _ptr(Cs), _ptr(Wdt), R, _ptr(A), _ptr(D),
+                _ptr(bias), _ptr(dy), ds, _ptr(state), _ptr(duk), _ptr(ddtr), _ptr(dBs), _ptr(dCs), _ptr(dpar), _ptr(ws), B, L, C, K)
         dtok = torch.empty(B, L, C, device=dev, dtype=torch.float32)
-        _lib.check(lib.mlagg_block_sum(_ptr(duk), _ptr(dtok), B * L, K, C, _stream()), "mlagg_block_sum")
+        _launch("mlagg_block_sum", _ptr(duk), _ptr(dtok), B * L, K, C)
         return dtok, None, ddtr, dBs, dCs, dpar[:, 3:], dpar[:, 0], dpar[:, 1], dpar[:, 2]
 
 
@@ -675,9 +652,8 @@ class LocalDiffAttnFn(torch.autograd.Function):
         lw = _require(lepe_w.reshape(d, 9).contiguous(), "lepe.weight")
         lb = _require(lepe_b.contiguous(), "lepe.bias", (d,))
         out = torch.empty(B, N, d, device=q.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_local_attn_fwd(_ptr(q), qs, _ptr(kv), kvs, _ptr(lam), _ptr(subln_w), _ptr(lw),
-                                                   _ptr(lb), _ptr(out), d, B, H, W, nh, float(scale), _stream()),
-                   "mlagg_local_attn_fwd")
+        _launch("mlagg_local_attn_fwd", _ptr(q), qs, _ptr(kv), kvs, _ptr(lam), _ptr(subln_w), _ptr(lw), _ptr(lb), _ptr(out), d, B, H, W, nh,
+                float(scale))
         ctx.save_for_backward(q, kv, lam, subln_w, lw)
         ctx.geom = (H, W, nh, float(scale), lepe_w.shape)
         return out
@@ -688,16 +664,13 @@ class LocalDiffAttnFn(torch.autograd.Function):
         H, W, nh, scale, lwshape = ctx.geom
         B, N, d = q.shape
         dout, dos = _rows(dout, "dout")
-        lib = _lib.lib()
         dq, dqs = _grad_out(ctx.slots[0], (B, N, d), q.device)
         dkv, dkvs = _grad_out(ctx.slots[1], (B, N, 2 * d), q.device)
         small = torch.zeros(1 + 48 + d * 9 + d, device=q.device, dtype=torch.float32)
         dlam, dsub, dlw, dlb = small[:1], small[1:49], small[49:49 + d * 9], small[49 + d * 9:]
-        ws = torch.empty(lib.mlagg_local_attn_bwd_workspace_floats(B, H, W, nh), device=q.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_local_attn_bwd(_ptr(q), q.stride(1), _ptr(kv), kv.stride(1), _ptr(lam), _ptr(subln_w),
-                                            _ptr(lw), _ptr(dout), dos, _ptr(dq), dqs, _ptr(dkv), dkvs, _ptr(dlam),
-                                            _ptr(dsub), _ptr(dlw), _ptr(dlb), _ptr(ws), B, H, W, nh, scale, _stream()),
-                   "mlagg_local_attn_bwd")
+        ws = torch.empty(_lib.lib().mlagg_local_attn_bwd_workspace_floats(B, H, W, nh), device=q.device, dtype=torch.float32)
+        _launch("mlagg_local_attn_bwd", _ptr(q), q.stride(1), _ptr(kv), kv.stride(1), _ptr(lam), _ptr(subln_w), _ptr(lw), _ptr(dout), dos,
+                _ptr(dq), dqs, _ptr(dkv), dkvs, _ptr(dlam), _ptr(dsub), _ptr(dlw), _ptr(dlb), _ptr(ws), B, H, W, nh, scale)
         return dq, dkv, dlam.reshape(()), dsub, dlw.reshape(lwshape), dlb, None, None, None, None, None, None
 
 
@@ -720,9 +693,8 @@ class PooledDiffAttnFn(torch.autograd.Function):
         need = any(ctx.needs_input_grad)      # grad mode is off inside Function.forward
         lse = torch.empty(B, N, nh, 2, device=q.device, dtype=torch.float32) if need else None
         o_pre = torch.empty(B, N, d, device=q.device, dtype=torch.float32) if need else None
-        _lib.check(_lib.lib().mlagg_pooled_attn_fwd(_ptr(q), qs, _ptr(kp), kps, _ptr(vp), vps, _ptr(lam), _ptr(subln_w),
-                                                    _ptr(out), d, _ptr(lse), _ptr(o_pre), B, N, P, nh, float(scale),
-                                                    _stream()), "mlagg_pooled_attn_fwd")
+        _launch("mlagg_pooled_attn_fwd", _ptr(q), qs, _ptr(kp), kps, _ptr(vp), vps, _ptr(lam), _ptr(subln_w), _ptr(out), d, _ptr(lse),
+                _ptr(o_pre), B, N, P, nh, float(scale))
         ctx.save_for_backward(q, kp, vp, lam, subln_w, lse, o_pre)
         ctx.geom = (nh, float(scale))
         return out
@@ -734,16 +706,14 @@ class PooledDiffAttnFn(torch.autograd.Function):
         B, N, d = q.shape
         P = kp.shape[1]
         dout, dos = _rows(dout, "dout")
-        lib = _lib.lib()
         dq, dqs = _grad_out(ctx.slot, (B, N, d), q.device)
         dkp = torch.empty(B, P, d, device=q.device, dtype=torch.float32)
         dvp = torch.empty(B, P, d, device=q.device, dtype=torch.float32)
         small = torch.zeros(1 + 48, device=q.device, dtype=torch.float32)
-        ws = torch.empty(lib.mlagg_pooled_attn_bwd_workspace_floats(B, N, P, nh), device=q.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_pooled_attn_bwd(_ptr(q), q.stride(1), _ptr(kp), kp.stride(1), _ptr(vp), vp.stride(1),
-                                             _ptr(lam), _ptr(subln_w), _ptr(dout), dos, _ptr(lse), _ptr(o_pre),
-                                             _ptr(dq), dqs, _ptr(dkp), d, _ptr(dvp), d, _ptr(small[:1]), _ptr(small[1:]),
-                                             _ptr(ws), B, N, P, nh, scale, _stream()), "mlagg_pooled_attn_bwd")
+        ws = torch.empty(_lib.lib().mlagg_pooled_attn_bwd_workspace_floats(B, N, P, nh), device=q.device, dtype=torch.float32)
+        _launch("mlagg_pooled_attn_bwd", _ptr(q), q.stride(1), _ptr(kp), kp.stride(1), _ptr(vp), vp.stride(1), _ptr(lam), _ptr(subln_w),
+                _ptr(dout), dos, _ptr(lse), _ptr(o_pre), _ptr(dq), dqs, _ptr(dkp), d, _ptr(dvp), d, _ptr(small[:1]), _ptr(small[1:]),
+                _ptr(ws), B, N, P, nh, scale)
         return dq, dkp, dvp, small[0].reshape(()), small[1:], None, None, None, None
 
 
@@ -768,9 +738,8 @@ class PooledDiffAttnLpFn(torch.autograd.Function):
         need = any(ctx.needs_input_grad)
         lse = torch.empty(B, N, nh, 2, device=q.device, dtype=torch.float32) if need else None
         o12 = torch.empty(2, B, N, d, device=q.device, dtype=torch.float32) if need else None
-        _lib.check(_lib.lib().mlagg_pooled_attn_lp_fwd(_ptr(q), qs, _ptr(kp), kps, _ptr(vp), vps, _ptr(lam), _ptr(subln_w), _ptr(out), d,
-                                                       _ptr(lse), _ptr(o12[0]) if need else None, _ptr(o12[1]) if need else None, B, N, P,
-                                                       nh, float(scale), _LP_CODE[cdt], _stream()), "mlagg_pooled_attn_lp_fwd")
+        _launch("mlagg_pooled_attn_lp_fwd", _ptr(q), qs, _ptr(kp), kps, _ptr(vp), vps, _ptr(lam), _ptr(subln_w), _ptr(out), d, _ptr(lse),
+                _ptr(o12[0]) if need else None, _ptr(o12[1]) if need else None, B, N, P, nh, float(scale), _LP_CODE[cdt])
         ctx.save_for_backward(q, kp, vp, lam, subln_w, lse, o12)
         ctx.geom = (nh, float(scale), cdt)
         return out
@@ -782,16 +751,14 @@ class PooledDiffAttnLpFn(torch.autograd.Function):
         B, N, d = q.shape
         P = kp.shape[1]
         dout, dos = _rows(dout, "dout")
-        lib = _lib.lib()
         dq, dqs = _grad_out(ctx.slot, (B, N, d), q.device)
         dkp = torch.empty(B, P, d, device=q.device, dtype=torch.float32)
         dvp = torch.empty(B, P, d, device=q.device, dtype=torch.float32)
         small = torch.empty(1 + 48, device=q.device, dtype=torch.float32)
-        ws = torch.empty(lib.mlagg_pooled_attn_lp_bwd_workspace_floats(B, N, P, nh), device=q.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_pooled_attn_lp_bwd(_ptr(q), q.stride(1), _ptr(kp), kp.stride(1), _ptr(vp), vp.stride(1), _ptr(lam),
-                                                _ptr(subln_w), _ptr(dout), dos, _ptr(lse), _ptr(o12[0]), _ptr(o12[1]), _ptr(dq), dqs,
-                                                _ptr(dkp), d, _ptr(dvp), d, _ptr(small[:1]), _ptr(small[1:]), _ptr(ws), B, N, P, nh, scale,
-                                                _LP_CODE[cdt], _stream()), "mlagg_pooled_attn_lp_bwd")
+        ws = torch.empty(_lib.lib().mlagg_pooled_attn_lp_bwd_workspace_floats(B, N, P, nh), device=q.device, dtype=torch.float32)
+        _launch("mlagg_pooled_attn_lp_bwd", _ptr(q), q.stride(1), _ptr(kp), kp.stride(1), _ptr(vp), vp.stride(1), _ptr(lam), _ptr(subln_w),
+                _ptr(dout), dos, _ptr(lse), _ptr(o12[0]), _ptr(o12[1]), _ptr(dq), dqs, _ptr(dkp), d, _ptr(dvp), d, _ptr(small[:1]),
+                _ptr(small[1:]), _ptr(ws), B, N, P, nh, scale, _LP_CODE[cdt])
         return dq, dkp, dvp, small[0].reshape(()), small[1:], None, None, None, None
 
 
@@ -811,8 +778,7 @@ class FlashAttnFn(torch.autograd.Function):
         out = torch.empty_like(q)
         need = any(ctx.needs_input_grad[:3])
         lse = torch.empty(B, nh, N, device=q.device, dtype=torch.float32) if need else None
-        _lib.check(_lib.lib().mlagg_flash_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, N, P, nh, e, float(scale),
-                                                   _LP_CODE[q.dtype], _stream()), "mlagg_flash_attn_fwd")
+        _launch("mlagg_flash_attn_fwd", _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, N, P, nh, e, float(scale), _LP_CODE[q.dtype])
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.scale = float(scale)
         return out
@@ -823,11 +789,10 @@ class FlashAttnFn(torch.autograd.Function):
         B, N, nh, e = q.shape
         P = k.shape[1]
         dout = dout.contiguous().to(q.dtype)
-        lib = _lib.lib()
         dq = torch.empty_like(q)
-        ws = torch.empty(lib.mlagg_flash_attn_bwd_workspace_floats(B, N, P, nh, e), device=q.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_flash_attn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dq), _ptr(ws),
-                                            B, N, P, nh, e, ctx.scale, _LP_CODE[q.dtype], _stream()), "mlagg_flash_attn_bwd")
+        ws = torch.empty(_lib.lib().mlagg_flash_attn_bwd_workspace_floats(B, N, P, nh, e), device=q.device, dtype=torch.float32)
+        _launch("mlagg_flash_attn_bwd", _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dq), _ptr(ws), B, N, P, nh, e,
+                ctx.scale, _LP_CODE[q.dtype])
         dkv = ws[B * nh * N:].view(B, P, nh, 2, e)
         return dq, dkv[:, :, :, 0].to(q.dtype), dkv[:, :, :, 1].to(q.dtype), None
 
@@ -911,7 +876,7 @@ def _image_pair(w):
     lib = _lib.lib()
     img = torch.empty(lib.mlagg_weight_image_bytes(N, K), dtype=torch.uint8, device=w.device)
     imgT = torch.empty(lib.mlagg_weight_image_bytes(K, N), dtype=torch.uint8, device=w.device)
-    _lib.check(lib.mlagg_weight_image(_ptr(w), K, _ptr(img), _ptr(imgT), N, K, _stream()), "mlagg_weight_image")
+    _launch("mlagg_weight_image", _ptr(w), K, _ptr(img), _ptr(imgT), N, K)
     return img, imgT
 
 
@@ -959,7 +924,7 @@ class WeightImageSet:
         sig = (ep,) + tuple(t._version for t in self.tensors)
         if sig == self.built and not torch.cuda.is_current_stream_capturing():
             return                                    # nothing changed since the last build (inference loops, a second forward of a step)
-        _lib.check(_lib.lib().mlagg_weight_images(_ptr(self.table), len(self.tensors), self.max_tiles, _stream()), "mlagg_weight_images")
+        _launch("mlagg_weight_images", _ptr(self.table), len(self.tensors), self.max_tiles)
         self.built = sig
         self.entries = {t.data_ptr(): (t._version, ep, v) for t, v in zip(self.tensors, self.views)}
 
@@ -1007,8 +972,7 @@ def _x3(x2, xs, img, bias, M, N, K, epilogue=0, pre=None, pre_stride=0, out_shap
     ys = N if out_stride is None else out_stride
     act = torch.empty_like(y) if epilogue == 1 else None
     _flop("K5", 2 * M * N * K)
-    _lib.check(_lib.lib().mlagg_linear_x3(_ptr(x2), xs, _ptr(img), _ptr(bias), _ptr(y), ys, _ptr(act), _ptr(pre), pre_stride, M, N, K,
-                                          epilogue, _stream()), "mlagg_linear_x3")
+    _launch("mlagg_linear_x3", _ptr(x2), xs, _ptr(img), _ptr(bias), _ptr(y), ys, _ptr(act), _ptr(pre), pre_stride, M, N, K, epilogue)
     return y if epilogue != 1 else (y, act)
 
 
@@ -1016,16 +980,15 @@ def _linear_wgrad(dy2, dys, x, O, I, has_bias):
     """dW (O, I) and db (O) of a token-major Linear: K5w for long token counts, the library GEMM + K8 column sums below."""
     M = dy2.shape[0]
     x2, xs = _rows2d(x, "x")
-    lib = _lib.lib()
     if M >= wgrad_min_rows():
         # dW | db in one allocation (every entry is written by the reduction)
         buf = torch.empty(O * I + (O if has_bias else 0), device=dy2.device, dtype=torch.float32)
         dW = buf[:O * I].view(O, I)
         db = buf[O * I:] if has_bias else None
-        ws = torch.empty(lib.mlagg_linear_wgrad_workspace_floats(M, O, I), device=dy2.device, dtype=torch.float32)
-        wgrad = lib.mlagg_linear_wgrad_x3 if K5_X3 else lib.mlagg_linear_wgrad
+        ws = torch.empty(_lib.lib().mlagg_linear_wgrad_workspace_floats(M, O, I), device=dy2.device, dtype=torch.float32)
         _flop("K5w", 2 * M * O * I)
-        _lib.check(wgrad(_ptr(dy2), dys, _ptr(x2), xs, _ptr(dW), _ptr(db), _ptr(ws), M, O, I, _stream()), "mlagg_linear_wgrad")
+        _launch("mlagg_linear_wgrad_x3" if K5_X3 else "mlagg_linear_wgrad", _ptr(dy2), dys, _ptr(x2), xs, _ptr(dW), _ptr(db), _ptr(ws),
+                M, O, I)
         return dW, db
     dW = dy2.t().matmul(x2)
     db = (column_sum(dy2) if dy2.is_cuda else dy2.sum(0)) if has_bias else None
@@ -1056,14 +1019,11 @@ class LinearFn(torch.autograd.Function):
             y = torch.empty(x.shape[:-1] + (O,), device=x.device, dtype=torch.float32)
             _flop("K5", 2 * M * O * I)
             if cdt == torch.float32 and K5_X3:
-                _lib.check(_lib.lib().mlagg_linear_lp_fwd(_ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I, _DTYPE_BF16X3,
-                                                          _stream()), "mlagg_linear_lp_fwd")
+                _launch("mlagg_linear_lp_fwd", _ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I, _DTYPE_BF16X3)
             elif cdt == torch.float32:
-                _lib.check(_lib.lib().mlagg_linear_fwd(_ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I, _stream()),
-                           "mlagg_linear_fwd")
+                _launch("mlagg_linear_fwd", _ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I)
             else:
-                _lib.check(_lib.lib().mlagg_linear_lp_fwd(_ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I,
-                                                          _LP_CODE[cdt], _stream()), "mlagg_linear_lp_fwd")
+                _launch("mlagg_linear_lp_fwd", _ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I, _LP_CODE[cdt])
             return y
         if cdt != torch.float32:
             return torch.nn.functional.linear(x.to(cdt), weight.to(cdt), lp(bias, cdt)).float()
@@ -1077,7 +1037,6 @@ class LinearFn(torch.autograd.Function):
         cdt = ctx.cdt
         dy2, dys = _mfma_rows(dy, "dy")
         M = dy2.shape[0]
-        lib = _lib.lib()
         if ctx.needs_input_grad[0]:
             if ctx.imgT is not None and _x3_ok(M, I, O):
                 # dx = dy . W on the image of W^T built with the forward's image (no per-step transpose of the weight); a claimed
@@ -1095,14 +1054,11 @@ class LinearFn(torch.autograd.Function):
                     # dx = dy . W as the forward form of the kernel on W^T (I, O): its weight tile is then read along the
                     # contraction, the fast staging path (the transpose is a (O, I) copy of a few hundred KB)
                     wt = transpose_2d(w.unsqueeze(0))[0]
-                    _lib.check(lib.mlagg_linear_lp_fwd(_ptr(dy2), dys, _ptr(wt), None, _ptr(dx), I, M, I, O, _DTYPE_BF16X3, _stream()),
-                               "mlagg_linear_lp_fwd")
+                    _launch("mlagg_linear_lp_fwd", _ptr(dy2), dys, _ptr(wt), None, _ptr(dx), I, M, I, O, _DTYPE_BF16X3)
                 elif cdt == torch.float32:
-                    _lib.check(lib.mlagg_linear_dgrad(_ptr(dy2), dys, _ptr(w), _ptr(dx), I, M, O, I, _stream()),
-                               "mlagg_linear_dgrad")
+                    _launch("mlagg_linear_dgrad", _ptr(dy2), dys, _ptr(w), _ptr(dx), I, M, O, I)
                 else:
-                    _lib.check(lib.mlagg_linear_lp_dgrad(_ptr(dy2), dys, _ptr(w), _ptr(dx), I, M, O, I, _LP_CODE[cdt],
-                                                         _stream()), "mlagg_linear_lp_dgrad")
+                    _launch("mlagg_linear_lp_dgrad", _ptr(dy2), dys, _ptr(w), _ptr(dx), I, M, O, I, _LP_CODE[cdt])
             elif cdt != torch.float32:
                 dx = dy.to(cdt).matmul(weight.to(cdt)).float()
             else:
@@ -1184,8 +1140,7 @@ class LayerNormFn(torch.autograd.Function):
         rows = x2.shape[0]
         y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
         stats = torch.empty(rows, 2, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_layernorm_fwd(_ptr(x2), xs, _ptr(weight), _ptr(bias), _ptr(y), _ptr(stats), rows, C,
-                                                  float(eps), _stream()), "mlagg_layernorm_fwd")
+        _launch("mlagg_layernorm_fwd", _ptr(x2), xs, _ptr(weight), _ptr(bias), _ptr(y), _ptr(stats), rows, C, float(eps))
         ctx.save_for_backward(x2, weight, stats)
         ctx.has_bias = bias is not None
         ctx.xshape = x.shape
@@ -1199,13 +1154,12 @@ class LayerNormFn(torch.autograd.Function):
         if dys % 4 or dy2.data_ptr() % 16:
             dy2 = dy2.contiguous()
             dys = C
-        lib = _lib.lib()
         dx = torch.empty(ctx.xshape, device=dy.device, dtype=torch.float32)
         dg = torch.empty(C, device=dy.device, dtype=torch.float32)
         db = torch.empty(C, device=dy.device, dtype=torch.float32) if ctx.has_bias else None
-        ws = torch.empty(lib.mlagg_layernorm_bwd_workspace_floats(rows, C), device=dy.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_layernorm_bwd(_ptr(x2), x2.stride(0), _ptr(dy2), dys, _ptr(weight), _ptr(stats), _ptr(dx),
-                                           _ptr(dg), _ptr(db), _ptr(ws), rows, C, _stream()), "mlagg_layernorm_bwd")
+        ws = torch.empty(_lib.lib().mlagg_layernorm_bwd_workspace_floats(rows, C), device=dy.device, dtype=torch.float32)
+        _launch("mlagg_layernorm_bwd", _ptr(x2), x2.stride(0), _ptr(dy2), dys, _ptr(weight), _ptr(stats), _ptr(dx), _ptr(dg), _ptr(db),
+                _ptr(ws), rows, C)
         return dx, dg, db, None
 
 
@@ -1234,9 +1188,8 @@ class ResidualLayerNormFn(torch.autograd.Function):
         xsum = torch.empty_like(skip)
         y = torch.empty_like(skip)
         stats = torch.empty(rows, 2, device=skip.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_residual_layernorm_fwd(_ptr(skip), _ptr(branch), _ptr(scale), _ptr(weight), _ptr(bias), _ptr(xsum),
-                                                           _ptr(y), _ptr(stats), rows, rows // B, C, float(eps), _stream()),
-                   "mlagg_residual_layernorm_fwd")
+        _launch("mlagg_residual_layernorm_fwd", _ptr(skip), _ptr(branch), _ptr(scale), _ptr(weight), _ptr(bias), _ptr(xsum), _ptr(y),
+                _ptr(stats), rows, rows // B, C, float(eps))
         ctx.save_for_backward(xsum, weight, stats, scale)
         ctx.has_bias = bias is not None
         return xsum, y
@@ -1247,7 +1200,6 @@ class ResidualLayerNormFn(torch.autograd.Function):
         C = xsum.shape[-1]
         rows = xsum.numel() // C
         B = xsum.shape[0]
-        lib = _lib.lib()
         if dy is None:                  # the norm's output went nowhere: a plain residual junction
             dres = _require(dxsum.contiguous(), "dxsum")
             dbranch = dres if scale is None else dres * scale.view((-1,) + (1,) * (dres.dim() - 1))
@@ -1261,10 +1213,9 @@ class ResidualLayerNormFn(torch.autograd.Function):
         dbranch = torch.empty_like(xsum) if scale is not None else None
         dg = torch.empty(C, device=dy.device, dtype=torch.float32)
         db = torch.empty(C, device=dy.device, dtype=torch.float32) if ctx.has_bias else None
-        ws = torch.empty(lib.mlagg_layernorm_bwd_workspace_floats(rows, C), device=dy.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_residual_layernorm_bwd(_ptr(xsum), _ptr(dy2), dys, _ptr(dres), _ptr(scale), _ptr(weight), _ptr(stats),
-                                                    _ptr(dskip), _ptr(dbranch), _ptr(dg), _ptr(db), _ptr(ws), rows, rows // B, C,
-                                                    _stream()), "mlagg_residual_layernorm_bwd")
+        ws = torch.empty(_lib.lib().mlagg_layernorm_bwd_workspace_floats(rows, C), device=dy.device, dtype=torch.float32)
+        _launch("mlagg_residual_layernorm_bwd", _ptr(xsum), _ptr(dy2), dys, _ptr(dres), _ptr(scale), _ptr(weight), _ptr(stats), _ptr(dskip),
+                _ptr(dbranch), _ptr(dg), _ptr(db), _ptr(ws), rows, rows // B, C)
         return dskip, (dskip if dbranch is None else dbranch), None, dg, db, None
 
 
@@ -1285,8 +1236,7 @@ class DWConv3x3NCHWFn(torch.autograd.Function):
         w = _require(weight.reshape(C, 9).contiguous(), "weight")
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         y = torch.empty(B, C, Ho, Wo, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_dwconv3x3_nchw_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, C, H, W, int(stride),
-                                                       _stream()), "mlagg_dwconv3x3_nchw_fwd")
+        _launch("mlagg_dwconv3x3_nchw_fwd", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, C, H, W, int(stride))
         ctx.save_for_backward(x, w)
         ctx.meta = (int(stride), bias is not None, weight.shape)
         return y
@@ -1297,14 +1247,12 @@ class DWConv3x3NCHWFn(torch.autograd.Function):
         stride, has_bias, wshape = ctx.meta
         B, C, H, W = x.shape
         dy = _require(dy.contiguous(), "dy")
-        lib = _lib.lib()
         dx = torch.empty_like(x)
         dw = torch.empty(C, 9, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32) if has_bias else None
-        ws = torch.empty(lib.mlagg_dwconv3x3_nchw_bwd_workspace_floats(B, C, H, W, stride), device=x.device,
+        ws = torch.empty(_lib.lib().mlagg_dwconv3x3_nchw_bwd_workspace_floats(B, C, H, W, stride), device=x.device,
                          dtype=torch.float32)
-        _lib.check(lib.mlagg_dwconv3x3_nchw_bwd(_ptr(x), _ptr(w), _ptr(dy), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), B, C, H,
-                                                W, stride, _stream()), "mlagg_dwconv3x3_nchw_bwd")
+        _launch("mlagg_dwconv3x3_nchw_bwd", _ptr(x), _ptr(w), _ptr(dy), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), B, C, H, W, stride)
         return dx, dw.reshape(wshape), db, None
 
 
@@ -1326,8 +1274,7 @@ class DWConvResNCHWFn(torch.autograd.Function):
         B, C, H, W = x.shape
         w = _require(weight.reshape(C, 9).contiguous(), "weight")
         y = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_dwconv3x3_nchw_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, C, H, W, 1, _stream()),
-                   "mlagg_dwconv3x3_nchw_fwd")
+        _launch("mlagg_dwconv3x3_nchw_fwd", _ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, C, H, W, 1)
         ctx.save_for_backward(x, w)
         ctx.meta = (bias is not None, weight.shape)
         return y, x.view_as(x)
@@ -1344,13 +1291,12 @@ class DWConvResNCHWFn(torch.autograd.Function):
             dres = _require(dres.contiguous(), "dres")
             if dres.dtype != torch.float32:
                 dres = dres.float()
-        lib = _lib.lib()
         dx = torch.empty_like(x)
         dw = torch.empty(C, 9, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32) if has_bias else None
-        ws = torch.empty(lib.mlagg_dwconv3x3_nchw_bwd_workspace_floats(B, C, H, W, 1), device=x.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_dwconv3x3_nchw_bwd_res(_ptr(x), _ptr(w), _ptr(dy), _ptr(dres), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), B, C, H,
-                                                    W, 1, _stream()), "mlagg_dwconv3x3_nchw_bwd_res")
+        ws = torch.empty(_lib.lib().mlagg_dwconv3x3_nchw_bwd_workspace_floats(B, C, H, W, 1), device=x.device, dtype=torch.float32)
+        _launch("mlagg_dwconv3x3_nchw_bwd_res", _ptr(x), _ptr(w), _ptr(dy), _ptr(dres), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), B, C, H, W,
+                1)
         return dx, dw.reshape(wshape), db
 
 
@@ -1364,19 +1310,15 @@ def dwconv3x3_nchw_res(x, weight, bias):
 
 
 def _int_array(vals):
-    import ctypes
     return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
 
 
 def _xscan(tok, tok_stride, blk_stride, seq, B, HW, CB, nblk, merge):
     Hs, Ws = _int_array([h for h, _ in HW]), _int_array([w for _, w in HW])
-    lib = _lib.lib()
     if merge:
-        _lib.check(lib.mlagg_cross_merge(_ptr(seq), tok, tok_stride, blk_stride, B, len(HW), Hs, Ws, CB, nblk, _stream()),
-                   "mlagg_cross_merge")
+        _launch("mlagg_cross_merge", _ptr(seq), tok, tok_stride, blk_stride, B, len(HW), Hs, Ws, CB, nblk)
     else:
-        _lib.check(lib.mlagg_cross_scan(tok, tok_stride, blk_stride, _ptr(seq), B, len(HW), Hs, Ws, CB, nblk, _stream()),
-                   "mlagg_cross_scan")
+        _launch("mlagg_cross_scan", tok, tok_stride, blk_stride, _ptr(seq), B, len(HW), Hs, Ws, CB, nblk)
 
 
 class CrossScanFn(torch.autograd.Function):
@@ -1479,8 +1421,7 @@ class IndexScanFn(torch.autograd.Function):
         if idx.dtype != torch.int32 or tuple(idx.shape) != (K, L) or not idx.is_cuda or col0 + (K - 1) * blk + CB > width:
             raise RuntimeError("index_scan: idx must be an int32 (K, L) device table and the column blocks must fit the rows")
         seq = torch.empty(B, K * CB, L, device=tok.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_index_scan(tok.data_ptr() + 4 * col0, width, blk, _ptr(idx), _ptr(seq), B, L, K, CB, _stream()),
-                   "mlagg_index_scan")
+        _launch("mlagg_index_scan", tok.data_ptr() + 4 * col0, width, blk, _ptr(idx), _ptr(seq), B, L, K, CB)
         ctx.save_for_backward(idx)
         ctx.meta = (CB, blk, col0, width)
         return seq
@@ -1494,14 +1435,12 @@ class IndexScanFn(torch.autograd.Function):
         K = idx.shape[0]
         if blk == 0 and width == CB:
             dtok = torch.empty(B, L, width, device=dseq.device, dtype=torch.float32)      # the summed form zero-fills itself
-            _lib.check(_lib.lib().mlagg_index_merge(_ptr(dseq), _ptr(idx), _ptr(dtok), width, 0, B, L, K, CB, _stream()),
-                       "mlagg_index_merge")
+            _launch("mlagg_index_merge", _ptr(dseq), _ptr(idx), _ptr(dtok), width, 0, B, L, K, CB)
             return dtok, None, None, None, None
         if blk == 0:
             raise RuntimeError("index_scan: a shared source must be exactly CB columns wide")
         dtok = torch.zeros(B, L, width, device=dseq.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_index_merge(_ptr(dseq), _ptr(idx), dtok.data_ptr() + 4 * col0, width, blk, B, L, K, CB, _stream()),
-                   "mlagg_index_merge")
+        _launch("mlagg_index_merge", _ptr(dseq), _ptr(idx), dtok.data_ptr() + 4 * col0, width, blk, B, L, K, CB)
         return dtok, None, None, None, None
 
 
@@ -1520,11 +1459,10 @@ class IndexMergeFn(torch.autograd.Function):
             # every direction into its own column block (plain stores), then the K blocks summed in a fixed order: deterministic,
             # and faster than K float-atomic read-modify-writes per output
             wide = torch.empty(B, L, K * CB, device=seq.device, dtype=torch.float32)
-            _lib.check(_lib.lib().mlagg_index_merge(_ptr(seq), _ptr(idx), _ptr(wide), K * CB, CB, B, L, K, CB, _stream()),
-                       "mlagg_index_merge")
-            _lib.check(_lib.lib().mlagg_block_sum(_ptr(wide), _ptr(tok), B * L, K, CB, _stream()), "mlagg_block_sum")
+            _launch("mlagg_index_merge", _ptr(seq), _ptr(idx), _ptr(wide), K * CB, CB, B, L, K, CB)
+            _launch("mlagg_block_sum", _ptr(wide), _ptr(tok), B * L, K, CB)
         else:
-            _lib.check(_lib.lib().mlagg_index_merge(_ptr(seq), _ptr(idx), _ptr(tok), CB, 0, B, L, K, CB, _stream()), "mlagg_index_merge")
+            _launch("mlagg_index_merge", _ptr(seq), _ptr(idx), _ptr(tok), CB, 0, B, L, K, CB)
         ctx.save_for_backward(idx)
         ctx.CB = CB
         return tok
@@ -1536,7 +1474,7 @@ class IndexMergeFn(torch.autograd.Function):
         B, L, CB = dtok.shape
         K = idx.shape[0]
         dseq = torch.empty(B, K * CB, L, device=dtok.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_index_scan(_ptr(dtok), CB, 0, _ptr(idx), _ptr(dseq), B, L, K, CB, _stream()), "mlagg_index_scan")
+        _launch("mlagg_index_scan", _ptr(dtok), CB, 0, _ptr(idx), _ptr(dseq), B, L, K, CB)
         return dseq, None, None
 
 
@@ -1552,14 +1490,12 @@ class IndexScanBCFn(torch.autograd.Function):
         K, per = idx.shape[0], R + 2
         if width != K * per or idx.dtype != torch.int32 or tuple(idx.shape) != (K, L) or not idx.is_cuda:
             raise RuntimeError("index_scan_bc: x_dbl must be (B, L, K * (R + 2)) and idx an int32 (K, L) device table")
-        lib = _lib.lib()
         dtr = torch.empty(B, K * R, L, device=xdbl.device, dtype=torch.float32)
         bc = torch.empty(2, B, K, L, device=xdbl.device, dtype=torch.float32)
         base = xdbl.data_ptr()
-        _lib.check(lib.mlagg_index_scan(base, width, per, _ptr(idx), _ptr(dtr), B, L, K, R, _stream()), "mlagg_index_scan")
-        _lib.check(lib.mlagg_index_scan(base + 4 * R, width, per, _ptr(idx), _ptr(bc[0]), B, L, K, 1, _stream()), "mlagg_index_scan")
-        _lib.check(lib.mlagg_index_scan(base + 4 * (R + 1), width, per, _ptr(idx), _ptr(bc[1]), B, L, K, 1, _stream()),
-                   "mlagg_index_scan")
+        _launch("mlagg_index_scan", base, width, per, _ptr(idx), _ptr(dtr), B, L, K, R)
+        _launch("mlagg_index_scan", base + 4 * R, width, per, _ptr(idx), _ptr(bc[0]), B, L, K, 1)
+        _launch("mlagg_index_scan", base + 4 * (R + 1), width, per, _ptr(idx), _ptr(bc[1]), B, L, K, 1)
         ctx.save_for_backward(idx)
         ctx.meta = (R, width)
         return dtr.view(B, K, R, L), bc[0], bc[1]
@@ -1573,13 +1509,11 @@ class IndexScanBCFn(torch.autograd.Function):
         dBs = _require(dBs.contiguous(), "dBs")
         dCs = _require(dCs.contiguous(), "dCs")
         B, K, _, L = ddtr.shape
-        lib = _lib.lib()
         dx = torch.empty(B, L, width, device=ddtr.device, dtype=torch.float32)
         base = dx.data_ptr()
-        _lib.check(lib.mlagg_index_merge(_ptr(ddtr), _ptr(idx), base, width, per, B, L, K, R, _stream()), "mlagg_index_merge")
-        _lib.check(lib.mlagg_index_merge(_ptr(dBs), _ptr(idx), base + 4 * R, width, per, B, L, K, 1, _stream()), "mlagg_index_merge")
-        _lib.check(lib.mlagg_index_merge(_ptr(dCs), _ptr(idx), base + 4 * (R + 1), width, per, B, L, K, 1, _stream()),
-                   "mlagg_index_merge")
+        _launch("mlagg_index_merge", _ptr(ddtr), _ptr(idx), base, width, per, B, L, K, R)
+        _launch("mlagg_index_merge", _ptr(dBs), _ptr(idx), base + 4 * R, width, per, B, L, K, 1)
+        _launch("mlagg_index_merge", _ptr(dCs), _ptr(idx), base + 4 * (R + 1), width, per, B, L, K, 1)
         return dx, None, None
 
 
@@ -1624,8 +1558,7 @@ class GateFn(torch.autograd.Function):
             act2 = act2.contiguous()
             acts = 2 * h
         out = torch.empty(a0.shape[:-1] + (2 * h,), device=a0.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_gate_fwd(_ptr(a0), _ptr(a1), _ptr(act2), acts, _ptr(out), rows, h, _stream()),
-                   "mlagg_gate_fwd")
+        _launch("mlagg_gate_fwd", _ptr(a0), _ptr(a1), _ptr(act2), acts, _ptr(out), rows, h)
         ctx.save_for_backward(a0, a1, act2)
         return out
 
@@ -1640,8 +1573,8 @@ class GateFn(torch.autograd.Function):
             ds = 2 * h
         da0, da1 = torch.empty_like(a0), torch.empty_like(a1)
         dact, dacts = _grad_out(ctx.slot, a0.shape[:-1] + (2 * h,), a0.device)
-        _lib.check(_lib.lib().mlagg_gate_bwd(_ptr(d2), ds, _ptr(a0), _ptr(a1), _ptr(act2), act2.stride(0), _ptr(da0),
-                                             _ptr(da1), _ptr(dact), dacts, rows, h, _stream()), "mlagg_gate_bwd")
+        _launch("mlagg_gate_bwd", _ptr(d2), ds, _ptr(a0), _ptr(a1), _ptr(act2), act2.stride(0), _ptr(da0), _ptr(da1), _ptr(dact), dacts,
+                rows, h)
         return da0, da1, dact, None
 
 
@@ -1660,7 +1593,7 @@ class GeluPoolFn(torch.autograd.Function):
         if N != H * W or H % r or W % r:
             raise RuntimeError(f"gelu_pool: {N} tokens, map {H}x{W}, window {r}")
         pooled = torch.empty(B, (H // r) * (W // r), d, device=s.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_gelu_pool_fwd(_ptr(s), ss, _ptr(pooled), B, H, W, d, r, _stream()), "mlagg_gelu_pool_fwd")
+        _launch("mlagg_gelu_pool_fwd", _ptr(s), ss, _ptr(pooled), B, H, W, d, r)
         ctx.save_for_backward(s)
         ctx.geom = (H, W, r)
         return pooled
@@ -1672,8 +1605,7 @@ class GeluPoolFn(torch.autograd.Function):
         B, N, d = s.shape
         dp = _require(dpooled.contiguous(), "dpooled")
         ds, dss = _grad_out(ctx.slot, (B, N, d), s.device)
-        _lib.check(_lib.lib().mlagg_gelu_pool_bwd(_ptr(s), s.stride(1), _ptr(dp), _ptr(ds), dss, B, H, W, d, r, _stream()),
-                   "mlagg_gelu_pool_bwd")
+        _launch("mlagg_gelu_pool_bwd", _ptr(s), s.stride(1), _ptr(dp), _ptr(ds), dss, B, H, W, d, r)
         return ds, None, None, None, None
 
 
@@ -1691,8 +1623,7 @@ class DiffLambdaFn(torch.autograd.Function):
         if any(v.numel() != n for v in vs):
             raise RuntimeError("diff_lambda: the four vectors differ in length")
         out = torch.empty(3, device=q1.device, dtype=torch.float32)            # [lambda, exp1, exp2]
-        _lib.check(_lib.lib().mlagg_diff_lambda_fwd(*(_ptr(v) for v in vs), float(lambda_init), n, _ptr(out),
-                                                    out.data_ptr() + 4, _stream()), "mlagg_diff_lambda_fwd")
+        _launch("mlagg_diff_lambda_fwd", *(_ptr(v) for v in vs), float(lambda_init), n, _ptr(out), out.data_ptr() + 4)
         ctx.save_for_backward(*vs, out)
         return out[0]
 
@@ -1702,9 +1633,8 @@ class DiffLambdaFn(torch.autograd.Function):
         n = q1.numel()
         dlam = _require(dlam.reshape(1).contiguous(), "dlambda")
         g = torch.empty(4, n, device=q1.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mlagg_diff_lambda_bwd(_ptr(dlam), _ptr(q1), _ptr(k1), _ptr(q2), _ptr(k2), out.data_ptr() + 4, n,
-                                                    _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(g[3]), _stream()),
-                   "mlagg_diff_lambda_bwd")
+        _launch("mlagg_diff_lambda_bwd", _ptr(dlam), _ptr(q1), _ptr(k1), _ptr(q2), _ptr(k2), out.data_ptr() + 4, n, _ptr(g[0]), _ptr(g[1]),
+                _ptr(g[2]), _ptr(g[3]))
         return g[0].view_as(q1), g[1].view_as(k1), g[2].view_as(q2), g[3].view_as(k2), None
 
 
@@ -1725,8 +1655,7 @@ class ScaledResidualFn(torch.autograd.Function):
             raise RuntimeError("scaled_residual: shape mismatch")
         per = skip.numel() // B
         out = torch.empty_like(skip)
-        _lib.check(_lib.lib().mlagg_scaled_residual(_ptr(skip), _ptr(branch), _ptr(scale), _ptr(out), B, per, _stream()),
-                   "mlagg_scaled_residual")
+        _launch("mlagg_scaled_residual", _ptr(skip), _ptr(branch), _ptr(scale), _ptr(out), B, per)
         ctx.save_for_backward(scale)
         return out
 
@@ -1736,8 +1665,7 @@ class ScaledResidualFn(torch.autograd.Function):
         g = _require(g.contiguous(), "grad")
         B = scale.numel()
         db = torch.empty_like(g)
-        _lib.check(_lib.lib().mlagg_scaled_residual(None, _ptr(g), _ptr(scale), _ptr(db), B, g.numel() // B, _stream()),
-                   "mlagg_scaled_residual")
+        _launch("mlagg_scaled_residual", None, _ptr(g), _ptr(scale), _ptr(db), B, g.numel() // B)
         return g, db, None
 
 
@@ -1773,8 +1701,8 @@ class DiceCEStatsFn(torch.autograd.Function):
                 raise RuntimeError("dice_ce_stats: logits / target shapes of a level do not match")
             hw = z.numel() // (B * C)
             ws = torch.empty(lib.mlagg_dice_ce_stats_workspace_floats(B, C, hw), device=dev, dtype=torch.float32)
-            _lib.check(lib.mlagg_dice_ce_stats(_ptr(z), _ptr(t), _ptr(ip[i]), _ptr(gt[i]), ce.data_ptr() + 4 * i, _ptr(ws), B, C, hw,
-                                               ctx.ignore, _stream()), "mlagg_dice_ce_stats")
+            _launch("mlagg_dice_ce_stats", _ptr(z), _ptr(t), _ptr(ip[i]), _ptr(gt[i]), ce.data_ptr() + 4 * i, _ptr(ws), B, C, hw,
+                    ctx.ignore)
             saved += [z, t]
         ctx.save_for_backward(*saved)
         ctx.n = n
@@ -1786,15 +1714,14 @@ class DiceCEStatsFn(torch.autograd.Function):
         n = ctx.n
         saved = ctx.saved_tensors
         B, C = saved[0].shape[:2]
-        lib = _lib.lib()
         g_ip = torch.zeros(n, B, 2, C, device=saved[0].device) if g_ip is None else _require(g_ip.contiguous(), "g_ip")
         g_ce = torch.zeros(n, device=saved[0].device) if g_ce is None else _require(g_ce.contiguous(), "g_ce")
         grads = []
         for i in range(n):
             z, t = saved[2 * i], saved[2 * i + 1]
             dz = torch.empty_like(z)
-            _lib.check(lib.mlagg_dice_ce_grad(_ptr(z), _ptr(t), _ptr(g_ip[i]), g_ce.data_ptr() + 4 * i, _ptr(dz), B, C,
-                                              z.numel() // (B * C), ctx.ignore, _stream()), "mlagg_dice_ce_grad")
+            _launch("mlagg_dice_ce_grad", _ptr(z), _ptr(t), _ptr(g_ip[i]), g_ce.data_ptr() + 4 * i, _ptr(dz), B, C, z.numel() // (B * C),
+                    ctx.ignore)
             grads.append(dz)
         return (None, None, *grads, *([None] * n))
 
@@ -1812,7 +1739,7 @@ def transpose_2d(src):
             and (C % 4 or src.stride(0) % 4 == 0)):
         src = src.contiguous()
     dst = torch.empty(B, C, R, device=src.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mlagg_transpose_2d(_ptr(src), src.stride(0), _ptr(dst), B, R, C, _stream()), "mlagg_transpose_2d")
+    _launch("mlagg_transpose_2d", _ptr(src), src.stride(0), _ptr(dst), B, R, C)
     return dst
 
 
@@ -1830,10 +1757,9 @@ class ChannelBiasFn(torch.autograd.Function):
     def backward(ctx, g):
         g = _require(g.contiguous(), "grad")
         B, C = g.shape[:2]
-        lib = _lib.lib()
         db = torch.empty(C, device=g.device, dtype=torch.float32)
-        ws = torch.empty(lib.mlagg_channel_sum_workspace_floats(B, C), device=g.device, dtype=torch.float32)
-        _lib.check(lib.mlagg_channel_sum(_ptr(g), _ptr(db), _ptr(ws), B, C, g.numel() // (B * C), _stream()), "mlagg_channel_sum")
+        ws = torch.empty(_lib.lib().mlagg_channel_sum_workspace_floats(B, C), device=g.device, dtype=torch.float32)
+        _launch("mlagg_channel_sum", _ptr(g), _ptr(db), _ptr(ws), B, C, g.numel() // (B * C))
         return g, db
 
 
@@ -1862,8 +1788,7 @@ class ChannelEpilogueFn(torch.autograd.Function):
             # written or saved in a modified state (a fresh convolution output) may be handed in
             raise RuntimeError("channel_epilogue(GELU): x must be the fresh output of the producing call")
         y = torch.empty_like(x) if act == EPI_GELU else None
-        _lib.check(_lib.lib().mlagg_channel_epilogue_fwd(_ptr(x), _ptr(bias), _ptr(res), _ptr(y), B, C, hw, int(act), _stream()),
-                   "mlagg_channel_epilogue_fwd")
+        _launch("mlagg_channel_epilogue_fwd", _ptr(x), _ptr(bias), _ptr(res), _ptr(y), B, C, hw, int(act))
         ctx.meta = (int(act), bias is not None, res is not None)
         if act == EPI_GELU:
             # x now holds the pre-activation.  It is the fresh output of the convolution call in front of this function
@@ -1879,18 +1804,16 @@ class ChannelEpilogueFn(torch.autograd.Function):
         dy = _require(dy.contiguous(), "dy")
         B, C = dy.shape[:2]
         hw = dy.numel() // (B * C)
-        lib = _lib.lib()
         db = torch.empty(C, device=dy.device, dtype=torch.float32) if has_bias else None
-        ws = torch.empty(lib.mlagg_channel_sum_workspace_floats(B, C), device=dy.device, dtype=torch.float32) if has_bias else None
+        ws = torch.empty(_lib.lib().mlagg_channel_sum_workspace_floats(B, C), device=dy.device, dtype=torch.float32) if has_bias else None
         if act == EPI_GELU:
             (pre,) = ctx.saved_tensors
             dx = torch.empty_like(dy)
-            _lib.check(lib.mlagg_channel_gelu_bwd(_ptr(pre), _ptr(dy), _ptr(dx), _ptr(db), _ptr(ws), B, C, hw, _stream()),
-                       "mlagg_channel_gelu_bwd")
+            _launch("mlagg_channel_gelu_bwd", _ptr(pre), _ptr(dy), _ptr(dx), _ptr(db), _ptr(ws), B, C, hw)
         else:
             dx = dy
             if has_bias:
-                _lib.check(lib.mlagg_channel_sum(_ptr(dy), _ptr(db), _ptr(ws), B, C, hw, _stream()), "mlagg_channel_sum")
+                _launch("mlagg_channel_sum", _ptr(dy), _ptr(db), _ptr(ws), B, C, hw)
         return dx, db, (dx if has_res else None), None
 
 
@@ -1903,17 +1826,16 @@ def column_sum(x2):
     _require(x2, "x")
     rows, cols = x2.shape
     out = torch.empty(cols, device=x2.device, dtype=torch.float32)
-    lib = _lib.lib()
-    n = lib.mlagg_column_sum_workspace_floats(rows, cols)
+    n = _lib.lib().mlagg_column_sum_workspace_floats(rows, cols)
     ws = torch.empty(n, device=x2.device, dtype=torch.float32) if n else None
-    _lib.check(lib.mlagg_column_sum(_ptr(x2), x2.stride(0), _ptr(out), _ptr(ws), rows, cols, _stream()), "mlagg_column_sum")
+    _launch("mlagg_column_sum", _ptr(x2), x2.stride(0), _ptr(out), _ptr(ws), rows, cols)
     return out
 
 
 ACT_NONE, ACT_LEAKY, ACT_SILU = 0, 1, 2
 
 
-_DT_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}            # MLAGG_DTYPE_* of include/mlagg_hip.h
+_DT_CODE = {torch.float32: _C["MLAGG_DTYPE_F32"], **_LP_CODE}
 
 
 def _require_map(t, name, shape=None):
@@ -1959,10 +1881,8 @@ class PlaneNormFn(torch.autograd.Function):
         stats = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
         nws = _lib.lib().mlagg_plane_norm_fwd_workspace_floats(B, C, hw)          # > 0: planes cut into segments (3-D volumes)
         ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws else None
-        _lib.check(_lib.lib().mlagg_plane_norm_fwd(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(res), _ptr(y), _ptr(stats), _ptr(ws), B, C, hw,
-                                                   float(eps), int(act), float(slope), _DT_CODE[x.dtype],
-                                                   0 if res is None else _DT_CODE[res.dtype], _DT_CODE[y.dtype], _stream()),
-                   "mlagg_plane_norm_fwd")
+        _launch("mlagg_plane_norm_fwd", _ptr(x), _ptr(gamma), _ptr(beta), _ptr(res), _ptr(y), _ptr(stats), _ptr(ws), B, C, hw, float(eps),
+                int(act), float(slope), _DT_CODE[x.dtype], 0 if res is None else _DT_CODE[res.dtype], _DT_CODE[y.dtype])
         ctx.save_for_backward(x, gamma, beta, res, stats)
         ctx.meta = (int(act), float(slope))
         return y
@@ -1982,10 +1902,9 @@ class PlaneNormFn(torch.autograd.Function):
         segmented = lib.mlagg_plane_norm_fwd_workspace_floats(B, C, hw) > 0
         ws = torch.empty(lib.mlagg_plane_norm_bwd_workspace_floats(B, C, hw), device=x.device, dtype=torch.float32) \
             if (dg is not None or db is not None or segmented) else None
-        _lib.check(lib.mlagg_plane_norm_bwd_strided(_ptr(x), _ptr(dy), dyb, _ptr(gamma), _ptr(beta), _ptr(res), _ptr(stats), _ptr(dx),
-                                                    _ptr(dres), _ptr(dg), _ptr(db), _ptr(ws), B, C, hw, act, slope, _DT_CODE[x.dtype],
-                                                    _DT_CODE[dy.dtype], 0 if res is None else _DT_CODE[res.dtype], _stream()),
-                   "mlagg_plane_norm_bwd_strided")
+        _launch("mlagg_plane_norm_bwd_strided", _ptr(x), _ptr(dy), dyb, _ptr(gamma), _ptr(beta), _ptr(res), _ptr(stats), _ptr(dx),
+                _ptr(dres), _ptr(dg), _ptr(db), _ptr(ws), B, C, hw, act, slope, _DT_CODE[x.dtype], _DT_CODE[dy.dtype],
+                0 if res is None else _DT_CODE[res.dtype])
         return dx, dg, db, dres, None, None, None, None
 
 
@@ -2005,9 +1924,8 @@ class ChannelEpilogueLpFn(torch.autograd.Function):
         B, C = x.shape[:2]
         hw = x.numel() // (B * C)
         y = torch.empty(x.shape, device=x.device, dtype=out_dtype)
-        _lib.check(_lib.lib().mlagg_channel_epilogue_lp_fwd(_ptr(x), _DT_CODE[x.dtype], _ptr(bias), _ptr(res),
-                                                            0 if res is None else _DT_CODE[res.dtype], _ptr(y), _DT_CODE[y.dtype], B, C, hw,
-                                                            int(act), _stream()), "mlagg_channel_epilogue_lp_fwd")
+        _launch("mlagg_channel_epilogue_lp_fwd", _ptr(x), _DT_CODE[x.dtype], _ptr(bias), _ptr(res),
+                0 if res is None else _DT_CODE[res.dtype], _ptr(y), _DT_CODE[y.dtype], B, C, hw, int(act))
         ctx.save_for_backward(x if act == EPI_GELU else None, bias, res if act == EPI_GELU else None)
         ctx.meta = (int(act), x.dtype, None if res is None else res.dtype, tuple(x.shape))
         return y
@@ -2019,13 +1937,12 @@ class ChannelEpilogueLpFn(torch.autograd.Function):
         dy = _require_map(dy.contiguous(), "dy", shape)
         B, C = shape[:2]
         hw = dy.numel() // (B * C)
-        lib = _lib.lib()
         dx = torch.empty(shape, device=dy.device, dtype=xdt)
         db = torch.empty(C, device=dy.device, dtype=torch.float32) if bias is not None else None
-        ws = torch.empty(lib.mlagg_channel_sum_workspace_floats(B, C), device=dy.device, dtype=torch.float32) if bias is not None else None
-        _lib.check(lib.mlagg_channel_epilogue_lp_bwd(_ptr(x), _DT_CODE[xdt], _ptr(bias), _ptr(res), 0 if res is None else _DT_CODE[res.dtype],
-                                                     _ptr(dy), _DT_CODE[dy.dtype], _ptr(dx), _DT_CODE[xdt], _ptr(db), _ptr(ws), B, C, hw,
-                                                     act, _stream()), "mlagg_channel_epilogue_lp_bwd")
+        ws = (torch.empty(_lib.lib().mlagg_channel_sum_workspace_floats(B, C), device=dy.device, dtype=torch.float32)
+              if bias is not None else None)
+        _launch("mlagg_channel_epilogue_lp_bwd", _ptr(x), _DT_CODE[xdt], _ptr(bias), _ptr(res), 0 if res is None else _DT_CODE[res.dtype],
+                _ptr(dy), _DT_CODE[dy.dtype], _ptr(dx), _DT_CODE[xdt], _ptr(db), _ptr(ws), B, C, hw, act)
         dres = None
         if rdt is not None and ctx.needs_input_grad[2]:
             # d(res) = d(pre): dy itself without an activation, else the values of dx -- in res's own element type
@@ -2097,19 +2014,16 @@ def _conv1x1_k18(x, xb, w, y, B, O, I, P, form, accumulate=False):
         wp[:, :I] = w
         w = wp
     _flop("K18", 2 * B * O * I * P)
-    _lib.check(_lib.lib().mlagg_conv1x1_fwd_acc(_ptr(x), xb, _ptr(w), None, _ptr(y), O * P, B, O, I16, I, P, form, int(accumulate), _stream()),
-               "mlagg_conv1x1_fwd_acc")
+    _launch("mlagg_conv1x1_fwd_acc", _ptr(x), xb, _ptr(w), None, _ptr(y), O * P, B, O, I16, I, P, form, int(accumulate))
     return y
 
 
 def _conv1x1_wgrad(dy, dyb, x, B, O, I, P, form):
     """dW (O, I) = dy (B, O, P) . x (B, I, P)^T on K18."""
-    lib = _lib.lib()
     dW = torch.empty(O, I, device=x.device, dtype=torch.float32)
-    ws = torch.empty(lib.mlagg_conv1x1_wgrad_workspace_floats(B, O, I, P), device=x.device, dtype=torch.float32)
+    ws = torch.empty(_lib.lib().mlagg_conv1x1_wgrad_workspace_floats(B, O, I, P), device=x.device, dtype=torch.float32)
     _flop("K18", 2 * B * O * I * P)
-    _lib.check(lib.mlagg_conv1x1_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, P, form, _stream()),
-               "mlagg_conv1x1_wgrad_lp")
+    _launch("mlagg_conv1x1_wgrad_lp", _ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, P, form)
     return dW
 
 
@@ -2156,7 +2070,7 @@ def _pixel_shuffle2(src, B, O, H, W, inverse):
     """(B, 4 O, H, W) -> (B, O, 2 H, 2 W), or back (inverse)."""
     src = _require(src.contiguous(), "src")
     dst = torch.empty((B, 4 * O, H, W) if inverse else (B, O, 2 * H, 2 * W), device=src.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mlagg_pixel_shuffle2(_ptr(src), _ptr(dst), B, O, H, W, int(inverse), _stream()), "mlagg_pixel_shuffle2")
+    _launch("mlagg_pixel_shuffle2", _ptr(src), _ptr(dst), B, O, H, W, int(inverse))
     return dst
 
 
@@ -2186,8 +2100,7 @@ class ConvT2x2Fn(torch.autograd.Function):
         if dy.dtype != torch.float32:
             dy, dyb = dy.float(), 0
         dyu = torch.empty(B, 4 * O, H, W, device=x.device, dtype=torch.float32)        # (B, 4 O, H, W)
-        _lib.check(_lib.lib().mlagg_pixel_unshuffle2_strided(_ptr(dy), dyb, _ptr(dyu), B, O, H, W, _stream()),
-                   "mlagg_pixel_unshuffle2_strided")
+        _launch("mlagg_pixel_unshuffle2_strided", _ptr(dy), dyb, _ptr(dyu), B, O, H, W)
         dx = dW = None
         if ctx.needs_input_grad[0]:
             wt = transpose_2d(w4.unsqueeze(0))[0]                                      # (I, 4 O)
@@ -2230,13 +2143,11 @@ def _conv3x3_plan(O, I, H, W, form):
 
 
 def _conv3x3_k19(x, xb, w, transposed, O, I, H, W, form, out=None):
-    lib = _lib.lib()
     B = x.shape[0]
     y = torch.empty(B, O, H, W, device=x.device, dtype=torch.float32) if out is None else out
-    ws = torch.empty(lib.mlagg_conv3x3_workspace_bytes(O, I), device=x.device, dtype=torch.uint8)
+    ws = torch.empty(_lib.lib().mlagg_conv3x3_workspace_bytes(O, I), device=x.device, dtype=torch.uint8)
     _flop("K19", 2 * 9 * B * O * I * H * W)
-    _lib.check(lib.mlagg_conv3x3_fwd_lp(_ptr(x), xb, _ptr(w), int(transposed), None, _ptr(y), y.stride(0), _ptr(ws), B, O, I, H, W, form,
-                                        _stream()), "mlagg_conv3x3_fwd_lp")
+    _launch("mlagg_conv3x3_fwd_lp", _ptr(x), xb, _ptr(w), int(transposed), None, _ptr(y), y.stride(0), _ptr(ws), B, O, I, H, W, form)
     return y
 
 
@@ -2278,8 +2189,7 @@ class Conv3x3Fn(torch.autograd.Function):
                 dW = torch.empty(O, I, 3, 3, device=x.device, dtype=torch.float32)
                 ws = torch.empty(lib.mlagg_conv3x3_wgrad_workspace_floats(B, O, I, H, W), device=x.device, dtype=torch.float32)
                 _flop("K19", 2 * 9 * B * O * I * H * W)
-                _lib.check(lib.mlagg_conv3x3_wgrad_lp(_ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, H, W, form,
-                                                      _stream()), "mlagg_conv3x3_wgrad_lp")
+                _launch("mlagg_conv3x3_wgrad_lp", _ptr(dy), dyb, _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O, I, H, W, form)
             else:
                 dW = _lib_conv_bwd(dy.contiguous(), x, w, 1, 1, False, (False, True, False), form)[1]
         return dx, dW, None, None, None
@@ -2305,35 +2215,31 @@ def _s2t_plan(O, I, H, W, form):
 
 
 def _k19t_fwd(x, xb, w, O, I, H, W, form):
-    lib = _lib.lib()
     B = x.shape[0]
     y = torch.empty(B, O, 2 * H - 1, 2 * W - 1, device=x.device, dtype=torch.float32)
-    ws = torch.empty(lib.mlagg_conv3x3_s2t_workspace_bytes(O, I), device=x.device, dtype=torch.uint8)
+    ws = torch.empty(_lib.lib().mlagg_conv3x3_s2t_workspace_bytes(O, I), device=x.device, dtype=torch.uint8)
     _flop("K19", 2 * 9 * B * O * I * H * W)
-    _lib.check(lib.mlagg_conv3x3_s2t_fwd(_ptr(x), xb, _ptr(w), _ptr(y), y.stride(0), _ptr(ws), B, O, I, H, W, form, _stream()),
-               "mlagg_conv3x3_s2t_fwd")
+    _launch("mlagg_conv3x3_s2t_fwd", _ptr(x), xb, _ptr(w), _ptr(y), y.stride(0), _ptr(ws), B, O, I, H, W, form)
     return y
 
 
 def _k19t_dgrad(dy, w, O, I, H, W, form):
-    lib = _lib.lib()
     B = dy.shape[0]
     dx = torch.empty(B, I, H, W, device=dy.device, dtype=torch.float32)
-    ws = torch.empty(lib.mlagg_conv3x3_s2t_workspace_bytes(O, I), device=dy.device, dtype=torch.uint8)
+    ws = torch.empty(_lib.lib().mlagg_conv3x3_s2t_workspace_bytes(O, I), device=dy.device, dtype=torch.uint8)
     _flop("K19", 2 * 9 * B * O * I * H * W)
-    _lib.check(lib.mlagg_conv3x3_s2_dgrad(_ptr(dy), dy.stride(0), dy.stride(1), dy.stride(2), _ptr(w), _ptr(dx), dx.stride(0), _ptr(ws),
-                                          B, O, I, H, W, form, _stream()), "mlagg_conv3x3_s2_dgrad")
+    _launch("mlagg_conv3x3_s2_dgrad", _ptr(dy), dy.stride(0), dy.stride(1), dy.stride(2), _ptr(w), _ptr(dx), dx.stride(0), _ptr(ws), B, O,
+            I, H, W, form)
     return dx
 
 
 def _k19t_wgrad(x, xb, dy, O, I, H, W, form):
-    lib = _lib.lib()
     B = x.shape[0]
     dW = torch.empty(I, O, 3, 3, device=x.device, dtype=torch.float32)
-    ws = torch.empty(lib.mlagg_conv3x3_s2t_wgrad_workspace_floats(B, O, I, H, W), device=x.device, dtype=torch.float32)
+    ws = torch.empty(_lib.lib().mlagg_conv3x3_s2t_wgrad_workspace_floats(B, O, I, H, W), device=x.device, dtype=torch.float32)
     _flop("K19", 2 * 9 * B * O * I * H * W)
-    _lib.check(lib.mlagg_conv3x3_s2t_wgrad(_ptr(x), xb, _ptr(dy), dy.stride(0), dy.stride(1), dy.stride(2), _ptr(dW), _ptr(ws), B, O, I,
-                                           H, W, form, _stream()), "mlagg_conv3x3_s2t_wgrad")
+    _launch("mlagg_conv3x3_s2t_wgrad", _ptr(x), xb, _ptr(dy), dy.stride(0), dy.stride(1), dy.stride(2), _ptr(dW), _ptr(ws), B, O, I, H, W,
+            form)
     return dW
 
 
@@ -2463,13 +2369,11 @@ K19_3D_WGRAD = _os.environ.get("MLAGG_K19_3D_WGRAD", "1") == "1"
 
 
 def _conv3x3x3_k19(x, xb, w, transposed, O, I, dims):
-    lib = _lib.lib()
     B = x.shape[0]
     D, H, W = dims
     y = torch.empty(B, O, D, H, W, device=x.device, dtype=torch.float32)
-    ws = torch.empty(lib.mlagg_conv3x3x3_workspace_bytes(O, I), device=x.device, dtype=torch.uint8)
-    _lib.check(lib.mlagg_conv3x3x3_fwd(_ptr(x), xb, _ptr(w), int(transposed), None, _ptr(y), O * D * H * W, _ptr(ws), B, O, I, D, H, W,
-                                       _stream()), "mlagg_conv3x3x3_fwd")
+    ws = torch.empty(_lib.lib().mlagg_conv3x3x3_workspace_bytes(O, I), device=x.device, dtype=torch.uint8)
+    _launch("mlagg_conv3x3x3_fwd", _ptr(x), xb, _ptr(w), int(transposed), None, _ptr(y), O * D * H * W, _ptr(ws), B, O, I, D, H, W)
     return y
 
 
@@ -2506,8 +2410,8 @@ class Conv3x3x3Fn(torch.autograd.Function):
             if K19_3D_WGRAD and lib.mlagg_conv3x3x3_wgrad_supported(O, I, *dims):
                 dW = torch.empty(O, I, 3, 3, 3, device=x.device, dtype=torch.float32)
                 ws = torch.empty(lib.mlagg_conv3x3x3_wgrad_workspace_floats(B, O, I, *dims), device=x.device, dtype=torch.float32)
-                _lib.check(lib.mlagg_conv3x3x3_wgrad(_ptr(dy), O * dims[0] * dims[1] * dims[2], _ptr(x), x.stride(0), _ptr(dW), _ptr(ws),
-                                                     B, O, I, *dims, _stream()), "mlagg_conv3x3x3_wgrad")
+                _launch("mlagg_conv3x3x3_wgrad", _ptr(dy), O * dims[0] * dims[1] * dims[2], _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O,
+                        I, *dims)
             else:                                               # widths that are not multiples of 8: K15 on padded copies
                 dW = conv_weight_grad(x if x.is_contiguous() else x.contiguous(), dy, 3, 1).view(w.shape)
         return dx, dW
@@ -2519,7 +2423,6 @@ def conv3x3x3_supported(x, weight, stride, padding):
 
 
 def _pad_geometry(D, H, W, stride, wide=False):
-    import ctypes
     Dq, Hq, Wq, guard = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_long()
     _lib.check(_lib.lib().mlagg_conv_pad_geometry(D, H, W, stride, int(wide), ctypes.byref(Dq), ctypes.byref(Hq), ctypes.byref(Wq),
                                                   ctypes.byref(guard)), "mlagg_conv_pad_geometry")
@@ -2552,8 +2455,6 @@ class _Padded:
     """A channel-major map copied into the zero-padded box of the tap-GEMM kernels (csrc/conv_wgrad.hip mlagg_volume_pad)."""
 
     def __init__(self, t, dims, stride, wide, as_output_of=None):
-        import ctypes  # noqa: F401
-        lib = _lib.lib()
         t = _require(t.contiguous(), "map")
         self.B, self.C = t.shape[:2]
         self.dims = tuple(dims)                                    # geometry of the convolution INPUT
@@ -2565,11 +2466,9 @@ class _Padded:
         self.buf = torch.empty(self.B, self.nph, self.C, self.row, device=t.device, dtype=torch.float32)
         od = tuple(t.shape[2:]) if t.dim() == 5 else (1,) + tuple(t.shape[2:])
         if as_output_of is None:
-            _lib.check(lib.mlagg_volume_pad(_ptr(t), _ptr(self.buf), self.B, self.C, *self.dims, stride, int(wide), 0, 0, 0, 0, _stream()),
-                       "mlagg_volume_pad")
+            _launch("mlagg_volume_pad", _ptr(t), _ptr(self.buf), self.B, self.C, *self.dims, stride, int(wide), 0, 0, 0, 0)
         else:
-            _lib.check(lib.mlagg_volume_pad(_ptr(t), _ptr(self.buf), self.B, self.C, *self.dims, stride, int(wide), 1, *od, _stream()),
-                       "mlagg_volume_pad")
+            _launch("mlagg_volume_pad", _ptr(t), _ptr(self.buf), self.B, self.C, *self.dims, stride, int(wide), 1, *od)
 
     def ptr(self):
         return self.buf.data_ptr() + 4 * self.guard
@@ -2594,17 +2493,15 @@ def _tap_offsets(k, nd, stride, Hq, Wq, I=0, row=0):
 
 def _wgrad_from_padded(xp, dyp, k, nd):
     """K15 on the padded copies of the input (xp) and of the output gradient (dyp, same box geometry): dW (O, I, k^nd)."""
-    import ctypes
-    lib = _lib.lib()
     O, I, B = dyp.C, xp.C, xp.B
     taps = _tap_offsets(k, nd, xp.stride, xp.Hq, xp.Wq, I, xp.row)
     ntaps = len(taps)
     Q8 = (xp.Q + 7) & ~7
     off = (ctypes.c_long * ntaps)(*taps)
     dW = torch.empty(O, I, ntaps, device=xp.buf.device, dtype=torch.float32)
-    ws = torch.empty(lib.mlagg_conv_wgrad_taps_workspace_floats(B, Q8, O, I, ntaps), device=xp.buf.device, dtype=torch.float32)
-    _lib.check(lib.mlagg_conv_wgrad_taps(dyp.ptr(), O * dyp.row, dyp.row, xp.ptr(), xp.nph * I * xp.row, xp.row, off, ntaps, Q8, O, I, B,
-                                         _ptr(dW), 0, _ptr(ws), _stream()), "mlagg_conv_wgrad_taps")
+    ws = torch.empty(_lib.lib().mlagg_conv_wgrad_taps_workspace_floats(B, Q8, O, I, ntaps), device=xp.buf.device, dtype=torch.float32)
+    _launch("mlagg_conv_wgrad_taps", dyp.ptr(), O * dyp.row, dyp.row, xp.ptr(), xp.nph * I * xp.row, xp.row, off, ntaps, Q8, O, I, B,
+            _ptr(dW), 0, _ptr(ws))
     return dW
 
 
@@ -2620,8 +2517,6 @@ def conv_weight_grad(x, dy, k, stride):
 def _conv_taps(src, weight, O, I, k, flip, dims):
     """K16 on a padded copy `src` (wide stride-1 box): y (B, O, *dims) with weight (O', I', k^3) read as [o][i] (forward) or
     transposed with flipped taps (data gradient: O = the convolution's input channels)."""
-    import ctypes
-    lib = _lib.lib()
     ntaps = k ** 3
     taps = _tap_offsets(k, 3, 1, src.Hq, src.Wq)
     off = (ctypes.c_long * ntaps)(*taps)
@@ -2631,8 +2526,7 @@ def _conv_taps(src, weight, O, I, k, flip, dims):
         w_so, w_si = ntaps, O * ntaps
     else:
         w_so, w_si = I * ntaps, ntaps
-    _lib.check(lib.mlagg_conv_taps(src.ptr(), src.C * src.row, src.row, _ptr(w), w_so, w_si, int(flip), off, ntaps, _ptr(y), src.B, O, I,
-                                   *dims, _stream()), "mlagg_conv_taps")
+    _launch("mlagg_conv_taps", src.ptr(), src.C * src.row, src.row, _ptr(w), w_so, w_si, int(flip), off, ntaps, _ptr(y), src.B, O, I, *dims)
     return y
 
 
@@ -2707,12 +2601,17 @@ def conv_nd(x, weight, stride, padding):
 # K20: 3-D sliding-window inference (csrc/sliding_window.hip).  Mirror variants are bitmasks of flipped tile axes (bit a = axis a),
 # in the reference's order (inference.mirror_variants).  No autograd: inference only.
 # ------------------------------------------------------------------------------------------------
-def _sw_volume(t, name, nd):
-    _require(t, name)
-    if t.dim() != nd or not t.is_contiguous():
-        raise RuntimeError(f"{name}: expected a contiguous {nd}-D tensor, got shape {tuple(t.shape)}"
-                           f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
-    return t
+def _expect(t, name, dtype=torch.float32, dim=None, shape=None, contiguous=True, like=None):
+    """The input check of the inference-only entry points (K20-K25): a `dtype` tensor on the MI355X device (`like`'s device when
+    given), of rank `dim` / shape `shape` when given, contiguous unless `contiguous` is False."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and (like is None or t.device == like.device)
+            and (dim is None or t.dim() == dim) and (shape is None or tuple(t.shape) == tuple(shape))
+            and (not contiguous or t.is_contiguous())):
+        want = (f"{'contiguous ' if contiguous else ''}{'' if dim is None else f'{dim}-D '}{dtype} tensor"
+                f"{'' if shape is None else f' of shape {tuple(shape)}'} on {'the MI355X device' if like is None else like.device}")
+        strided = isinstance(t, torch.Tensor) and not t.is_contiguous()
+        raise RuntimeError(f"{name}: expected a {want}, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}"
+                           f"{' (non-contiguous)' if strided else ''} on {getattr(t, 'device', '?')}")
 
 
 def _sw_flips(flips):
@@ -2732,7 +2631,7 @@ def _sw_box(origin, tile, shape, what):
 def sliding_window_gather(volume, origins, flips, tile_size):
     """volume (C, X, Y, Z) -> network input (V * n, C, tx, ty, tz): the n tiles at `origins`, variant-major, variant v flipped
     along the axes of mask flips[v]."""
-    _sw_volume(volume, "volume", 4)
+    _expect(volume, "volume", dim=4)
     flips = _sw_flips(flips)
     tile = tuple(int(t) for t in tile_size)
     if len(tile) != 3 or min(tile) < 1:
@@ -2742,17 +2641,17 @@ def sliding_window_gather(volume, origins, flips, tile_size):
     if not boxes:
         raise RuntimeError("sliding_window_gather: no tiles")
     out = torch.empty((len(flips) * len(boxes), C) + tile, device=volume.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mlagg_sw_gather(_ptr(volume), C, X, Y, Z, _int_array([v for o in boxes for v in o]), len(boxes),
-                                          _int_array(flips), len(flips), _ptr(out), *tile, _stream()), "mlagg_sw_gather")
+    _launch("mlagg_sw_gather", _ptr(volume), C, X, Y, Z, _int_array([v for o in boxes for v in o]), len(boxes), _int_array(flips),
+            len(flips), _ptr(out), *tile)
     return out
 
 
 def sliding_window_fold(out, tile, n, flips, gaussian, origin, acc, weight):
     """Fold tile `tile` of the chunk output out (V * n, K, tx, ty, tz) into acc (K, X, Y, Z) and weight (X, Y, Z) at `origin`:
     acc += mean over the variants of the flipped-back outputs * gaussian, weight += gaussian (in place)."""
-    _sw_volume(out, "out", 5)
-    _sw_volume(acc, "acc", 4)
-    _sw_volume(weight, "weight", 3)
+    _expect(out, "out", dim=5)
+    _expect(acc, "acc", dim=4)
+    _expect(weight, "weight", dim=3)
     flips = _sw_flips(flips)
     V, n, tile = len(flips), int(n), int(tile)
     K, tx, ty, tz = (int(v) for v in out.shape[1:])
@@ -2763,15 +2662,14 @@ def sliding_window_fold(out, tile, n, flips, gaussian, origin, acc, weight):
         raise RuntimeError(f"sliding_window_fold: acc {tuple(acc.shape)} / weight {tuple(weight.shape)} for {K} classes")
     X, Y, Z = weight.shape
     o = _sw_box(origin, (tx, ty, tz), (X, Y, Z), "sliding_window_fold")
-    _lib.check(_lib.lib().mlagg_sw_fold(_ptr(out), tile, n, _int_array(flips), V, K, _ptr(gaussian), tx, ty, tz, *o,
-                                        _ptr(acc), _ptr(weight), X, Y, Z, _stream()), "mlagg_sw_fold")
+    _launch("mlagg_sw_fold", _ptr(out), tile, n, _int_array(flips), V, K, _ptr(gaussian), tx, ty, tz, *o, _ptr(acc), _ptr(weight), X, Y, Z)
 
 
 def sliding_window_finalize(acc, weight, region, return_labels=False):
     """logits (K, X0, Y0, Z0) = acc / weight on `region` (three slices with explicit bounds), a new contiguous tensor; with
     return_labels also the int64 argmax over K (torch.argmax's first-maximum rule).  Returns (logits, labels or None)."""
-    _sw_volume(acc, "acc", 4)
-    _sw_volume(weight, "weight", 3)
+    _expect(acc, "acc", dim=4)
+    _expect(weight, "weight", dim=3)
     if acc.shape[1:] != weight.shape:
         raise RuntimeError(f"sliding_window_finalize: acc {tuple(acc.shape)} / weight {tuple(weight.shape)}")
     K = int(acc.shape[0])
@@ -2787,8 +2685,7 @@ def sliding_window_finalize(acc, weight, region, return_labels=False):
         raise RuntimeError("sliding_window_finalize: region must hold three slices")
     logits = torch.empty((K,) + tuple(size), device=acc.device, dtype=torch.float32)
     labels = torch.empty(tuple(size), device=acc.device, dtype=torch.int64) if return_labels else None
-    _lib.check(_lib.lib().mlagg_sw_finalize(_ptr(acc), _ptr(weight), K, *shape, *lo, *size, _ptr(logits), _ptr(labels), _stream()),
-               "mlagg_sw_finalize")
+    _launch("mlagg_sw_finalize", _ptr(acc), _ptr(weight), K, *shape, *lo, *size, _ptr(logits), _ptr(labels))
     return logits, labels
 
 
@@ -2797,13 +2694,13 @@ def sliding_window_finalize(acc, weight, region, return_labels=False):
 # (idx (X' + Y' + Z', 2) int32, w (X' + Y' + Z', 2) float64); they are checked against the logits' extent here, on the host, before
 # the single upload of the call, so the kernels never read outside the logits.  No autograd: inference only.
 # ------------------------------------------------------------------------------------------------
-def _export_source(logits):
-    _require(logits, "logits")
-    if logits.dim() != 4 or min(logits.shape) < 1:
-        raise RuntimeError(f"logits: expected a non-empty (C, X, Y, Z) tensor, got shape {tuple(logits.shape)}")
-    if min(logits.stride()) < 0:
-        raise RuntimeError("logits: negative strides are not supported")
-    return tuple(int(s) for s in logits.shape), tuple(int(s) for s in logits.stride())
+def _strided_volume(t, name):
+    """(shape, strides) of a non-empty (C, X, Y, Z) fp32 device tensor that the kernels read through its strides."""
+    _expect(t, name, dim=4, contiguous=False)
+    if min(t.shape) < 1 or min(t.stride()) < 0:
+        raise RuntimeError(f"{name}: expected a non-empty (C, X, Y, Z) tensor with non-negative strides, got shape {tuple(t.shape)}, "
+                           f"strides {t.stride()}")
+    return tuple(int(s) for s in t.shape), tuple(int(s) for s in t.stride())
 
 
 def _export_taps(taps, in_shape, out_shape, device):
@@ -2823,14 +2720,13 @@ def _export_taps(taps, in_shape, out_shape, device):
 def resample_linear(logits, taps, out_shape):
     """logits (C, X, Y, Z) fp32, any non-negative strides -> (C, *out_shape) contiguous fp32: out[c, o] = the separable blend of the
     two taps of every axis at o (taps = export._axis_taps tables), in fp64, rounded once."""
-    shape, st = _export_source(logits)
+    shape, st = _strided_volume(logits, "logits")
     out_shape = tuple(int(s) for s in out_shape)
     if len(out_shape) != 3 or min(out_shape) < 1:
         raise RuntimeError(f"resample_linear: output shape {out_shape}")
     idx, w = _export_taps(taps, shape[1:], out_shape, logits.device)
     out = torch.empty((shape[0],) + out_shape, device=logits.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mlagg_resample_linear(_ptr(logits), *shape, *st, _ptr(idx), _ptr(w), _ptr(out), *out_shape, _stream()),
-               "mlagg_resample_linear")
+    _launch("mlagg_resample_linear", _ptr(logits), *shape, *st, _ptr(idx), _ptr(w), _ptr(out), *out_shape)
     return out
 
 
@@ -2841,7 +2737,7 @@ def export_segmentation(logits, taps, crop_shape, box_lo, shape_before_cropping,
     """The fused export of K <= 32 classes: resample logits (K, X, Y, Z) to crop_shape with the tap tables, fp32 softmax over K,
     first-maximum argmax, pasted at box_lo into shape_before_cropping (zeros outside) and transposed by transpose_backward.
     Returns (labels uint8, probabilities (K, ...) fp32 or None), contiguous."""
-    shape, st = _export_source(logits)
+    shape, st = _strided_volume(logits, "logits")
     K = shape[0]
     if K > EXPORT_MAX_CLASSES:
         raise RuntimeError(f"export_segmentation: {K} classes, the fused kernel holds at most {EXPORT_MAX_CLASSES}")
@@ -2857,9 +2753,8 @@ def export_segmentation(logits, taps, crop_shape, box_lo, shape_before_cropping,
     out_shape = tuple(full[p] for p in perm)
     labels = torch.empty(out_shape, device=logits.device, dtype=torch.uint8)
     probs = torch.empty((K,) + out_shape, device=logits.device, dtype=torch.float32) if return_probabilities else None
-    _lib.check(_lib.lib().mlagg_export_segmentation(_ptr(logits), *shape, *st, _ptr(idx), _ptr(w), *crop, _int_array(lo),
-                                                    _int_array(full), _int_array(perm), _ptr(labels), _ptr(probs), _stream()),
-               "mlagg_export_segmentation")
+    _launch("mlagg_export_segmentation", _ptr(logits), *shape, *st, _ptr(idx), _ptr(w), *crop, _int_array(lo), _int_array(full),
+            _int_array(perm), _ptr(labels), _ptr(probs))
     return labels, probs
 
 
@@ -2868,18 +2763,10 @@ def export_segmentation(logits, taps, crop_shape, box_lo, shape_before_cropping,
 # tables from export._axis_taps, as host numpy arrays; they are checked here, on the host, before their upload, so the kernels never
 # read outside a line.  No autograd: inference only.
 # ------------------------------------------------------------------------------------------------
-PP_SCHEMES = {"NoNormalization": 0, "CTNormalization": 1, "ZScoreNormalization": 2, "ZScoreNormalization+mask": 3,
-              "RescaleTo01Normalization": 4, "RGBTo01Normalization": 5}
-PP_STATS_PARTIALS = 256        # MLAGG_PP_STATS_PARTIALS
-
-
-def _pp_source(x):
-    _require(x, "image")
-    if x.dim() != 4 or min(x.shape) < 1:
-        raise RuntimeError(f"image: expected a non-empty (C, X, Y, Z) tensor, got shape {tuple(x.shape)}")
-    if min(x.stride()) < 0:
-        raise RuntimeError("image: negative strides are not supported")
-    return tuple(int(s) for s in x.shape), tuple(int(s) for s in x.stride())
+PP_SCHEMES = {"NoNormalization": _C["MLAGG_PP_NONE"], "CTNormalization": _C["MLAGG_PP_CT"], "ZScoreNormalization": _C["MLAGG_PP_ZSCORE"],
+              "ZScoreNormalization+mask": _C["MLAGG_PP_ZSCORE_MASKED"], "RescaleTo01Normalization": _C["MLAGG_PP_RESCALE01"],
+              "RGBTo01Normalization": _C["MLAGG_PP_RGB01"]}
+PP_STATS_PARTIALS = _C["MLAGG_PP_STATS_PARTIALS"]
 
 
 def _pp_window(shape, lo, ext):
@@ -2892,60 +2779,54 @@ def _pp_window(shape, lo, ext):
 def pp_nonzero_box(x):
     """x (C, X, Y, Z) fp32, any non-negative strides -> int32 device tensor (6,): min x, y, z and max x, y, z of the voxels that are
     non-zero in any channel; (2^31 - 1, -1) per axis when there are none."""
-    shape, st = _pp_source(x)
+    shape, st = _strided_volume(x, "image")
     box = torch.empty(6, dtype=torch.int32, device=x.device)
-    _lib.check(_lib.lib().mlagg_pp_nonzero_box(_ptr(x), *shape, *st, _ptr(box), _stream()), "mlagg_pp_nonzero_box")
+    _launch("mlagg_pp_nonzero_box", _ptr(x), *shape, *st, _ptr(box))
     return box
 
 
 def pp_channel_stats(x, lo, ext, c, scheme, params, stats, mask=None):
     """Channel c of x's crop window (under mask, (ext) uint8, for the masked ZScore): fills stats[c] = fp64 (mean, std, min, max) and
     the scheme's fp32 constants in params[c] (see mlagg_pp_channel_stats)."""
-    shape, st = _pp_source(x)
+    shape, st = _strided_volume(x, "image")
     lo, ext = _pp_window(shape, lo, ext)
     if not 0 <= c < shape[0] or scheme not in PP_SCHEMES.values():
         raise RuntimeError(f"pp_channel_stats: channel {c} of {shape[0]}, scheme {scheme}")
-    if params.dtype != torch.float32 or params.shape != (shape[0], 4) or not params.is_contiguous():
-        raise RuntimeError("pp_channel_stats: params must be a contiguous (C, 4) fp32 tensor")
-    if stats.dtype != torch.float64 or stats.shape != (shape[0], 4) or not stats.is_contiguous():
-        raise RuntimeError("pp_channel_stats: stats must be a contiguous (C, 4) fp64 tensor")
+    _expect(params, "params", shape=(shape[0], 4), like=x)
+    _expect(stats, "stats", torch.float64, shape=(shape[0], 4), like=x)
     if scheme == PP_SCHEMES["ZScoreNormalization+mask"]:
-        if mask is None or mask.dtype != torch.uint8 or tuple(mask.shape) != ext or not mask.is_contiguous():
-            raise RuntimeError(f"pp_channel_stats: the masked ZScore needs a contiguous uint8 mask of shape {ext}")
+        _expect(mask, "mask of the masked ZScore", torch.uint8, shape=ext, like=x)
     partials = torch.empty(shape[0] * PP_STATS_PARTIALS * 5, dtype=torch.float64, device=x.device)
-    _lib.check(_lib.lib().mlagg_pp_channel_stats(_ptr(x), *shape, *st, _int_array(lo), _int_array(ext), int(c), int(scheme), _ptr(mask),
-                                                 _ptr(partials), _ptr(params), _ptr(stats), _stream()), "mlagg_pp_channel_stats")
+    _launch("mlagg_pp_channel_stats", _ptr(x), *shape, *st, _int_array(lo), _int_array(ext), int(c), int(scheme), _ptr(mask),
+            _ptr(partials), _ptr(params), _ptr(stats))
 
 
 def pp_normalize(x, lo, ext, schemes, params, mask=None):
     """Crop x to the window and normalise every channel with its scheme code (PP_SCHEMES) in fp32 -> (C, *ext) contiguous fp32.
     schemes: int32 device tensor (C,); params: fp32 device tensor (C, 4); mask: (ext) uint8 for the masked ZScore."""
-    shape, st = _pp_source(x)
+    shape, st = _strided_volume(x, "image")
     lo, ext = _pp_window(shape, lo, ext)
-    if schemes.dtype != torch.int32 or tuple(schemes.shape) != (shape[0],) or params.dtype != torch.float32 \
-            or tuple(params.shape) != (shape[0], 4) or not params.is_contiguous():
-        raise RuntimeError("pp_normalize: schemes (C,) int32 and params (C, 4) fp32 device tensors")
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != ext or not mask.is_contiguous()):
-        raise RuntimeError(f"pp_normalize: mask must be a contiguous uint8 tensor of shape {ext}")
-    if mask is None and bool((schemes == PP_SCHEMES["ZScoreNormalization+mask"]).any()):
+    _expect(schemes, "schemes", torch.int32, shape=(shape[0],), like=x)
+    _expect(params, "params", shape=(shape[0], 4), like=x)
+    if mask is not None:
+        _expect(mask, "mask", torch.uint8, shape=ext, like=x)
+    elif bool((schemes == PP_SCHEMES["ZScoreNormalization+mask"]).any()):
         raise RuntimeError("pp_normalize: the masked ZScore needs a mask")
     out = torch.empty((shape[0],) + ext, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().mlagg_pp_normalize(_ptr(x), *shape, *st, _int_array(lo), _int_array(ext), _ptr(schemes), _ptr(params),
-                                             _ptr(mask), _ptr(out), _stream()), "mlagg_pp_normalize")
+    _launch("mlagg_pp_normalize", _ptr(x), *shape, *st, _int_array(lo), _int_array(ext), _ptr(schemes), _ptr(params), _ptr(mask), _ptr(out))
     return out
 
 
 def pp_clip_ranges(x, axis=None):
     """x (C, X, Y, Z) contiguous fp32 -> (lo, hi) int32 device tensors (C * D,) of ordered-int encoded min / max: per channel
     (axis None, D = 1) or per channel and slice along spatial axis `axis` (D = its extent)."""
-    shape, _ = _pp_source(x)
+    shape, _ = _strided_volume(x, "image")
     if not x.is_contiguous():
         raise RuntimeError("pp_clip_ranges: x must be contiguous")
     D = 1 if axis is None else shape[1 + int(axis)]
     lo = torch.empty(shape[0] * D, dtype=torch.int32, device=x.device)
     hi = torch.empty_like(lo)
-    _lib.check(_lib.lib().mlagg_pp_clip_ranges(_ptr(x), *shape, -1 if axis is None else int(axis), _ptr(lo), _ptr(hi), _stream()),
-               "mlagg_pp_clip_ranges")
+    _launch("mlagg_pp_clip_ranges", _ptr(x), *shape, -1 if axis is None else int(axis), _ptr(lo), _ptr(hi))
     return lo, hi
 
 
@@ -2988,9 +2869,8 @@ def pp_cubic_axis(x, axis, taps, fir, out_dtype=torch.float64, clip=None):
         dstride = V if dax is None else int(np.prod(out_shape[2 + dax:]))
         if D != (1 if dax is None else out_shape[1 + dax]) or clo.numel() != shape[0] * D or chi.numel() != shape[0] * D:
             raise RuntimeError("pp_cubic_axis: clip ranges do not match the output's domains")
-    _lib.check(_lib.lib().mlagg_pp_cubic_axis(_ptr(x), int(x.dtype == torch.float64), _ptr(out), int(out_dtype == torch.float64),
-                                              outer, n_in, inner, n_out, _ptr(d_start), _ptr(d_w), int(P0), int(M), fir.data_ptr(),
-                                              _ptr(clo), _ptr(chi), cstride, dstride, int(D), _stream()), "mlagg_pp_cubic_axis")
+    _launch("mlagg_pp_cubic_axis", _ptr(x), int(x.dtype == torch.float64), _ptr(out), int(out_dtype == torch.float64), outer, n_in, inner,
+            n_out, _ptr(d_start), _ptr(d_w), int(P0), int(M), fir.data_ptr(), _ptr(clo), _ptr(chi), cstride, dstride, int(D))
     return out
 
 
@@ -3009,8 +2889,7 @@ def pp_gather_axis(x, axis, taps):
     out_shape[1 + axis] = n_out
     out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
     d_idx, d_w = torch.from_numpy(idx).to(x.device), torch.from_numpy(w).to(x.device)
-    _lib.check(_lib.lib().mlagg_pp_gather_axis(_ptr(x), _ptr(out), outer, n_in, inner, n_out, _ptr(d_idx), _ptr(d_w), _stream()),
-               "mlagg_pp_gather_axis")
+    _launch("mlagg_pp_gather_axis", _ptr(x), _ptr(out), outer, n_in, inner, n_out, _ptr(d_idx), _ptr(d_w))
     return out
 
 
@@ -3025,19 +2904,13 @@ def keep_largest_component(labels, group, background_label=0):
     """labels (X, Y, Z) contiguous uint8 on the device, group (256,) uint8 on the same device -> (out (X, Y, Z) uint8, stats (3, 256)
     int32 device tensor: per group the voxel count, the largest component's size and the voxels kept).  Voxels of a non-zero group
     whose 26-connected same-group component is smaller than the group's largest become background_label; ties are all kept."""
-    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.uint8 and labels.dim() == 3):
-        raise RuntimeError(f"labels: expected a 3-D uint8 tensor on the MI355X device, got "
-                           f"{getattr(labels, 'dtype', type(labels))} {tuple(getattr(labels, 'shape', ()))} "
-                           f"on {getattr(labels, 'device', '?')}")
-    if labels.numel() > CC_MAX_VOXELS:
+    _expect(labels, "labels", torch.uint8, dim=3, contiguous=False)
+    if labels.numel() > CC_MAX_VOXELS:                # before contiguity: a huge expanded view is refused for its size
         raise RuntimeError(f"keep_largest_component: {labels.numel()} voxels, at most {CC_MAX_VOXELS} are supported")
     if min(labels.shape) < 1:
         raise RuntimeError(f"keep_largest_component: empty volume {tuple(labels.shape)}")
-    if not labels.is_contiguous():
-        raise RuntimeError("labels: expected a contiguous tensor")
-    if not (isinstance(group, torch.Tensor) and group.dtype == torch.uint8 and tuple(group.shape) == (256,)
-            and group.device == labels.device and group.is_contiguous()):
-        raise RuntimeError("group: expected a contiguous (256,) uint8 tensor on the labels' device")
+    _expect(labels, "labels", torch.uint8, dim=3)
+    _expect(group, "group", torch.uint8, shape=(256,), like=labels)
     if not 0 <= int(background_label) <= 255:
         raise RuntimeError(f"background_label {background_label}: a uint8 label expected")
     if labels.data_ptr() % 4:
@@ -3047,9 +2920,8 @@ def keep_largest_component(labels, group, background_label=0):
     size = torch.empty(n, dtype=torch.int32, device=labels.device)
     stats = torch.empty((3, 256), dtype=torch.int32, device=labels.device)
     out = torch.empty_like(labels)
-    _lib.check(_lib.lib().mlagg_keep_largest_component(_ptr(labels), *labels.shape, _ptr(group), int(background_label), _ptr(parent),
-                                                       _ptr(size), _ptr(stats), _ptr(out), _stream()),
-               "mlagg_keep_largest_component")
+    _launch("mlagg_keep_largest_component", _ptr(labels), *labels.shape, _ptr(group), int(background_label), _ptr(parent), _ptr(size),
+            _ptr(stats), _ptr(out))
     return out, stats
 
 
@@ -3058,36 +2930,26 @@ def keep_largest_component(labels, group, background_label=0):
 # area table.  Inference only.
 # ------------------------------------------------------------------------------------------------
 SURFACE_MAX_VOXELS = 2 ** 31 - 1
-SURFACE_MAX_LINE = 2560                         # MLAGG_SURFACE_MAX_LINE: the longest crop axis (LDS envelope of one line)
-SURFACE_DESC_FIELDS = 16
-
-
-def _require_labels(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.is_contiguous()):
-        raise RuntimeError(f"{name}: expected a contiguous 3-D uint8 tensor on the MI355X device, got "
-                           f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', '?')}")
+SURFACE_MAX_LINE = _C["MLAGG_SURFACE_MAX_LINE"]          # the longest crop axis (LDS envelope of one line)
+SURFACE_DESC_FIELDS = _C["MLAGG_SURFACE_DESC_FIELDS"]
 
 
 def surface_stats(gt, pred, wanted):
     """gt, pred (X, Y, Z) uint8 label volumes on the device, wanted (256,) uint8 on the same device -> (256, 10) int32 device tensor:
     per label value the gt and prediction voxel counts, the union box (x, y, z min / max) and the gt's z min / max."""
-    _require_labels(gt, "gt")
-    _require_labels(pred, "pred")
-    if gt.shape != pred.shape or gt.device != pred.device:
-        raise RuntimeError(f"gt {tuple(gt.shape)} and pred {tuple(pred.shape)}: same shape and device expected")
-    if not (wanted.dtype == torch.uint8 and tuple(wanted.shape) == (256,) and wanted.device == gt.device):
-        raise RuntimeError("wanted: expected a (256,) uint8 tensor on the volumes' device")
+    _expect(gt, "gt", torch.uint8, dim=3)
+    _expect(pred, "pred", torch.uint8, shape=gt.shape, like=gt)
+    _expect(wanted, "wanted", torch.uint8, shape=(256,), contiguous=False, like=gt)
     stats = torch.empty((256, 10), dtype=torch.int32, device=gt.device)
-    _lib.check(_lib.lib().mlagg_surface_stats(_ptr(gt), _ptr(pred), *gt.shape, _ptr(wanted.contiguous()), _ptr(stats), _stream()),
-               "mlagg_surface_stats")
+    _launch("mlagg_surface_stats", _ptr(gt), _ptr(pred), *gt.shape, _ptr(wanted.contiguous()), _ptr(stats))
     return stats
 
 
 def surface_prepare(gt, pred, desc, spacing):
     """Neighbour codes and the z / y passes of the feature transform for every crop of desc ((L, 16) int64 host tensor, see
     include/mlagg_hip.h).  Returns the state mlagg_surface_reduce needs: (codes, ft, counts, d_desc, layout)."""
-    _require_labels(gt, "gt")
-    _require_labels(pred, "pred")
+    _expect(gt, "gt", torch.uint8, dim=3)
+    _expect(pred, "pred", torch.uint8, dim=3)
     L = desc.shape[0]
     n = desc[:, 4:7].long() + 1
     vox = n.prod(1)
@@ -3104,10 +2966,8 @@ def surface_prepare(gt, pred, desc, spacing):
     ft = torch.empty(2 * layout["total"], dtype=torch.int32, device=dev)
     counts = torch.empty((L, 2), dtype=torch.int32, device=dev)
     s = [float(v) for v in spacing]
-    _lib.check(_lib.lib().mlagg_surface_prepare(_ptr(gt), _ptr(pred), *gt.shape, _ptr(d_desc), L, layout["total"], layout["max_crop"],
-                                                layout["zlines"], layout["ylines"], layout["nmax_y"], s[1], s[2], _ptr(codes),
-                                                _ptr(ft), _ptr(counts), _stream()),
-               "mlagg_surface_prepare")
+    _launch("mlagg_surface_prepare", _ptr(gt), _ptr(pred), *gt.shape, _ptr(d_desc), L, layout["total"], layout["max_crop"],
+            layout["zlines"], layout["ylines"], layout["nmax_y"], s[1], s[2], _ptr(codes), _ptr(ft), _ptr(counts))
     return codes, ft, counts, d_desc, layout
 
 
@@ -3125,10 +2985,8 @@ def surface_reduce(state, tol, area, spacing, pairs_total=None):
         pairs = torch.empty((max(int(pairs_total), 1), 2), dtype=torch.float64, device=dev)
         pair_count = torch.empty((L, 2), dtype=torch.int32, device=dev)
     s = [float(v) for v in spacing]
-    _lib.check(_lib.lib().mlagg_surface_reduce(_ptr(codes), _ptr(ft), _ptr(d_desc), L, layout["total"], layout["xlines"],
-                                               layout["nmax_x"], _ptr(tol), _ptr(area), s[0], s[1], s[2], _ptr(partial), _ptr(sums),
-                                               _ptr(pairs), _ptr(pair_count), _stream()),
-               "mlagg_surface_reduce")
+    _launch("mlagg_surface_reduce", _ptr(codes), _ptr(ft), _ptr(d_desc), L, layout["total"], layout["xlines"], layout["nmax_x"], _ptr(tol),
+            _ptr(area), s[0], s[1], s[2], _ptr(partial), _ptr(sums), _ptr(pairs), _ptr(pair_count))
     return sums, (None if pairs is None else pairs[:int(pairs_total)])
 
 
@@ -3139,17 +2997,13 @@ def aug3d_resample(vol, lab, affine, resample, out_shape):
     """vol (B, C, Xi, Yi, Zi) fp32 (spline coefficients of the resampled samples, raw data of the cropped ones), lab (B, 1, Xi, Yi, Zi)
     int16 or None, affine (B, 3, 4) float64 host array (output voxel index -> input coordinate), resample (B,) host bools ->
     (out (B, C, *out_shape) fp32, out_lab (B, 1, *out_shape) fp32 or None).  See include/mlagg_hip.h, K25."""
-    import ctypes
-    _sw_volume(vol, "vol", 5)
+    _expect(vol, "vol", dim=5)
     B, C, Xi, Yi, Zi = (int(v) for v in vol.shape)
     Xo, Yo, Zo = (int(v) for v in out_shape)
     if min(Xo, Yo, Zo) < 1:
         raise RuntimeError(f"aug3d_resample: output shape {tuple(out_shape)}")
     if lab is not None:
-        if not (isinstance(lab, torch.Tensor) and lab.device == vol.device and lab.dtype == torch.int16 and lab.is_contiguous()
-                and tuple(lab.shape) == (B, 1, Xi, Yi, Zi)):
-            raise RuntimeError(f"lab: expected a contiguous int16 tensor of shape {(B, 1, Xi, Yi, Zi)} on {vol.device}, got "
-                               f"{getattr(lab, 'dtype', type(lab))} {tuple(getattr(lab, 'shape', ()))}")
+        _expect(lab, "lab", torch.int16, shape=(B, 1, Xi, Yi, Zi), like=vol)
     A = np.ascontiguousarray(np.asarray(affine, dtype=np.float64).reshape(B, 12))
     rs = np.asarray(resample, dtype=bool).reshape(-1)
     if rs.shape[0] != B:
@@ -3158,7 +3012,6 @@ def aug3d_resample(vol, lab, affine, resample, out_shape):
         raise RuntimeError(f"aug3d_resample: a cropped sample needs an input ({Xi}, {Yi}, {Zi}) at least the output ({Xo}, {Yo}, {Zo})")
     out = torch.empty((B, C, Xo, Yo, Zo), device=vol.device, dtype=torch.float32)
     out_lab = torch.empty((B, 1, Xo, Yo, Zo), device=vol.device, dtype=torch.float32) if lab is not None else None
-    _lib.check(_lib.lib().mlagg_aug3d_resample(_ptr(vol), _ptr(lab), B, C, Xi, Yi, Zi,
-                                               A.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _int_array(rs.astype(int)), _ptr(out),
-                                               _ptr(out_lab), Xo, Yo, Zo, _stream()), "mlagg_aug3d_resample")
+    _launch("mlagg_aug3d_resample", _ptr(vol), _ptr(lab), B, C, Xi, Yi, Zi, A.ctypes.data, _int_array(rs.astype(int)), _ptr(out),
+            _ptr(out_lab), Xo, Yo, Zo)
     return out, out_lab

@@ -196,8 +196,7 @@ class ClipAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, max_norm=0.0):
         from . import _lib
-        lib = _lib.lib()
-        chunk = lib.mlagg_adamw_chunk_elements()
+        chunk = _lib.lib().mlagg_adamw_chunk_elements()
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -252,17 +251,14 @@ class ClipAdamW(torch.optim.Optimizer):
                         torch.cuda.current_stream().synchronize()      # an earlier upload may still be reading the pinned buffer
                     pinned.copy_(host)
                     table.copy_(pinned, non_blocking=True)
-                _lib.check(lib.mlagg_adamw_clip_step_dev(table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(),
-                                                         group["lr"].data_ptr(), self._step_dev.data_ptr(), float(b1), float(b2),
-                                                         float(group["eps"]), float(group["weight_decay"]), float(max_norm),
-                                                         torch.cuda.current_stream().cuda_stream), "mlagg_adamw_clip_step_dev")
+                _lib.launch("mlagg_adamw_clip_step_dev", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(),
+                            group["lr"].data_ptr(), self._step_dev.data_ptr(), float(b1), float(b2), float(group["eps"]),
+                            float(group["weight_decay"]), float(max_norm))
                 continue
             table = host.pin_memory().to(dev, non_blocking=True)
             lr = float(group["lr"])
-            _lib.check(lib.mlagg_adamw_clip_step(table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(), lr,
-                                                 float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                                 float(max_norm), self._steps, torch.cuda.current_stream().cuda_stream),
-                       "mlagg_adamw_clip_step")
+            _lib.launch("mlagg_adamw_clip_step", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(), lr, float(b1),
+                        float(b2), float(group["eps"]), float(group["weight_decay"]), float(max_norm), self._steps)
             self._keepalive = table                   # the table must outlive the asynchronous launches
         return loss
 

@@ -10,10 +10,25 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared_symbols():
+def _header_text():
     text = open(os.path.join(ROOT, "include", "mlagg_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mlagg_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _declared_symbols():
+    return sorted(set(re.findall(r"\b(mlagg_[a-z0-9_]+)\s*\(", _header_text())))
+
+
+def _declarations():
+    """name -> (return type, parameter count) of every declaration, read here independently of _lib's parser: the return type is
+    what precedes the name on its line, the parameters are counted by their commas."""
+    text = _header_text()
+    out = {}
+    for m in re.finditer(r"\b(mlagg_[a-z0-9_]+)\s*\(([^)]*)\)", text):
+        ret = text[text.rfind("\n", 0, m.start()) + 1:m.start()]
+        params = m.group(2).strip()
+        out[m.group(1)] = (" ".join(ret.replace("*", " *").split()), 0 if params in ("", "void") else params.count(",") + 1)
+    return out
 
 
 def test_library_exports_every_declared_symbol():
@@ -27,6 +42,11 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(handle, name), f"{name} declared in mlagg_hip.h but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature"
     assert set(_lib.SIGNATURES) == set(declared)
+    restypes = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+    for name, (ret, nparams) in _declarations().items():
+        res, args = _lib.SIGNATURES[name]
+        assert len(args) == nparams, f"{name}: {len(args)} ctypes arguments for {nparams} declared parameters"
+        assert res is restypes[ret], f"{name}: restype {res} for the declared return type {ret!r}"
     lib = _lib.lib()
     assert lib.mlagg_version().startswith(b"mlagg_hip")
     assert b"unsupported" in lib.mlagg_error_string(-1)
