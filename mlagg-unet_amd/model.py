@@ -248,9 +248,7 @@ class Mlp(nn.Module):
         self.fc2 = Linear(hidden, dim)
 
     def forward(self, x):
-        if ops.mlp_supported(x, self.fc1.weight, self.fc2.weight):
-            return ops.mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)        # GELU in K5's epilogues
-        return self.fc2(F.gelu(self.fc1(x)))
+        return ops.mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
 
 
 class RMSNormWeight(nn.Module):

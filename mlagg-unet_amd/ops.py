@@ -976,11 +976,11 @@ def _x3(x2, xs, img, bias, M, N, K, epilogue=0, pre=None, pre_stride=0, out_shap
     return y if epilogue != 1 else (y, act)
 
 
-def _linear_wgrad(dy2, dys, x, O, I, has_bias):
-    """dW (O, I) and db (O) of a token-major Linear: K5w for long token counts, the library GEMM + K8 column sums below."""
+def _linear_wgrad(dy2, dys, x, O, I, has_bias, kernel):
+    """dW (O, I) and db (O) of a token-major Linear: on K5w (kernel "K5w"), else the library GEMM + K8 column sums."""
     M = dy2.shape[0]
     x2, xs = _rows2d(x, "x")
-    if M >= wgrad_min_rows():
+    if kernel == "K5w":
         # dW | db in one allocation (every entry is written by the reduction)
         buf = torch.empty(O * I + (O if has_bias else 0), device=dy2.device, dtype=torch.float32)
         dW = buf[:O * I].view(O, I)
@@ -995,12 +995,29 @@ def _linear_wgrad(dy2, dys, x, O, I, has_bias):
     return dW, db
 
 
+def linear_plan(M, O, I, cdt, on_device):
+    """Where each product of the token-major projection y (M, O) = x (M, I) W^T + b runs in compute dtype `cdt`: (forward, data
+    gradient, weight gradient) -- "K5x3" (on weight images), "K5" or None (the library in `cdt`) for the first two, "K5w" or None
+    (the library GEMM + K8 column sums) for the third.  Which K5 entry point runs is the mode's (MLAGG_K5_X3, `cdt`), not the plan's.
+    A function of shapes, `cdt`, device-ness and the switches and thresholds above only, read at each call."""
+    if not on_device:
+        return None, None, None
+    fp32 = cdt == torch.float32
+    k5 = M >= (K5_MIN_ROWS if fp32 else LP_K5_MIN_ROWS) and I % 4 == 0
+    fwd = "K5x3" if fp32 and _x3_ok(M, O, I) else ("K5" if k5 else None)
+    dgrad = "K5x3" if fwd == "K5x3" and _x3_ok(M, I, O) else ("K5" if k5 and O % 4 == 0 else None)
+    return fwd, dgrad, "K5w" if M >= wgrad_min_rows() else None
+
+
+_X3_PAIR = ("K5x3", "K5x3")
+
+
 class LinearFn(torch.autograd.Function):
-    """y = x W^T + b for token-major activations: forward and dx on K5 (round-4 form on weight images at every token count from
-    X3_MIN_ROWS up; 16-bit modes: the round-3 kernels for long token counts, the library GEMM below), dW / db on K5w."""
+    """y = x W^T + b for token-major activations, each product where the plan says (linear_plan unless one is given): forward and
+    dx on K5 (on weight images, or the round-3 kernels) or the library, dW / db on K5w or the library."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, slot=None):
+    def forward(ctx, x, weight, bias, slot=None, plan=None):
         ctx.save_for_backward(x, weight)
         ctx.slot = slot
         ctx.has_bias = bias is not None
@@ -1008,37 +1025,35 @@ class LinearFn(torch.autograd.Function):
         ctx.imgT = None
         O, I = weight.shape
         M = x.numel() // I
-        if cdt == torch.float32 and x.is_cuda and _x3_ok(M, O, I):
-            x2, xs = _mfma_rows(x, "x")
-            w = _require(weight.contiguous(), "weight")
+        ctx.plan = plan = plan or linear_plan(M, O, I, cdt, x.is_cuda)
+        if plan[0] is None:
+            if cdt != torch.float32:
+                return torch.nn.functional.linear(x.to(cdt), weight.to(cdt), lp(bias, cdt)).float()
+            return torch.nn.functional.linear(x, weight, bias)
+        x2, xs = _mfma_rows(x, "x")
+        w = _require(weight.contiguous(), "weight")
+        if plan[0] == "K5x3":
             img, ctx.imgT = weight_images(w)
             return _x3(x2, xs, img, bias, M, O, I, out_shape=x.shape[:-1] + (O,))
-        if M >= (K5_MIN_ROWS if cdt == torch.float32 else LP_K5_MIN_ROWS) and I % 4 == 0 and x.is_cuda:
-            x2, xs = _mfma_rows(x, "x")
-            w = _require(weight.contiguous(), "weight")
-            y = torch.empty(x.shape[:-1] + (O,), device=x.device, dtype=torch.float32)
-            _flop("K5", 2 * M * O * I)
-            if cdt == torch.float32 and K5_X3:
-                _launch("mlagg_linear_lp_fwd", _ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I, _DTYPE_BF16X3)
-            elif cdt == torch.float32:
-                _launch("mlagg_linear_fwd", _ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I)
-            else:
-                _launch("mlagg_linear_lp_fwd", _ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I, _LP_CODE[cdt])
-            return y
-        if cdt != torch.float32:
-            return torch.nn.functional.linear(x.to(cdt), weight.to(cdt), lp(bias, cdt)).float()
-        return torch.nn.functional.linear(x, weight, bias)
+        y = torch.empty(x.shape[:-1] + (O,), device=x.device, dtype=torch.float32)
+        _flop("K5", 2 * M * O * I)
+        if cdt == torch.float32 and not K5_X3:
+            _launch("mlagg_linear_fwd", _ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I)
+        else:                           # split-bf16 (fp32) or one-product (16-bit) operands
+            _launch("mlagg_linear_lp_fwd", _ptr(x2), xs, _ptr(w), _ptr(bias), _ptr(y), O, M, O, I,
+                    _DTYPE_BF16X3 if cdt == torch.float32 else _LP_CODE[cdt])
+        return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         dx = dW = db = None
         O, I = weight.shape
-        cdt = ctx.cdt
+        cdt, (_, dgrad, wgrad) = ctx.cdt, ctx.plan
         dy2, dys = _mfma_rows(dy, "dy")
         M = dy2.shape[0]
         if ctx.needs_input_grad[0]:
-            if ctx.imgT is not None and _x3_ok(M, I, O):
+            if dgrad == "K5x3":
                 # dx = dy . W on the image of W^T built with the forward's image (no per-step transpose of the weight); a claimed
                 # split_cols slot: written straight into the shared gradient buffer of the pieces
                 if ctx.slot is not None:
@@ -1046,7 +1061,7 @@ class LinearFn(torch.autograd.Function):
                     _x3(dy2, dys, ctx.imgT, None, M, I, O, out=dx, out_stride=dxs)
                 else:
                     dx = _x3(dy2, dys, ctx.imgT, None, M, I, O, out_shape=x.shape)
-            elif (M >= K5_MIN_ROWS if cdt == torch.float32 else M >= LP_K5_MIN_ROWS) and O % 4 == 0 and I % 4 == 0:
+            elif dgrad == "K5":
                 w = _require(weight.contiguous(), "weight")
                 dx = torch.empty(x.shape, device=dy.device, dtype=torch.float32)
                 _flop("K5", 2 * M * O * I)
@@ -1065,27 +1080,27 @@ class LinearFn(torch.autograd.Function):
                 dx = dy.matmul(weight)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             # weight / bias gradients stay fp32 in every mode (K5w: the token sum is the long one)
-            dW, db = _linear_wgrad(dy2, dys, x, O, I, ctx.has_bias)
-        return dx, dW, db, None
+            dW, db = _linear_wgrad(dy2, dys, x, O, I, ctx.has_bias, wgrad)
+        return dx, dW, db, None, None
 
 
-def linear(x, weight, bias=None):
-    # a split_cols piece as input: its gradient is written in place when both products of this layer run on K5
-    slot = None
-    if getattr(x, "_mlagg_slot", None) is not None and x.is_cuda and compute_dtype() == torch.float32:
+def linear(x, weight, bias=None, plan=None):
+    """The token-major projection on linear_plan's kernels (`plan`: that plan, when the caller has it).  A split_cols piece as
+    input: its gradient is written in place when forward and data gradient both run on K5x3."""
+    if plan is None:
         O, I = weight.shape
-        M = x.numel() // I
-        if _x3_ok(M, O, I) and _x3_ok(M, I, O):
-            slot = claim_slot(x)
-    return LinearFn.apply(x, weight, bias, slot)
+        plan = linear_plan(x.numel() // I, O, I, compute_dtype(), x.is_cuda)
+    slot = claim_slot(x) if plan[:2] == _X3_PAIR else None
+    return LinearFn.apply(x, weight, bias, slot, plan)
 
 
 class MlpFn(torch.autograd.Function):
     """fc2(GELU(fc1(x))) of reference Mlp (T:176-192) as four K5 launches: fc1 writes the pre-activation AND its GELU, and in backward
-    the data gradient of fc2 comes out already multiplied by GELU'(pre) -- the two elementwise GELU passes of the ATen form are gone."""
+    the data gradient of fc2 comes out already multiplied by GELU'(pre) -- the two elementwise GELU passes of the ATen form are gone.
+    `wgrads`: the weight-gradient kernels of fc1 and fc2 (linear_plan's third entries)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2):
+    def forward(ctx, x, w1, b1, w2, b2, wgrads):
         H, I = w1.shape
         O = w2.shape[0]
         M = x.numel() // I
@@ -1098,6 +1113,7 @@ class MlpFn(torch.autograd.Function):
         ctx.save_for_backward(x, w1, w2, pre, act)
         ctx.images = (img1T, img2T)
         ctx.bias = (b1 is not None, b2 is not None)
+        ctx.wgrads = wgrads
         return y
 
     @staticmethod
@@ -1108,23 +1124,31 @@ class MlpFn(torch.autograd.Function):
         O = w2.shape[0]
         dy2, dys = _mfma_rows(dy, "dy")
         M = dy2.shape[0]
-        dW2, db2 = _linear_wgrad(dy2, dys, act, O, H, ctx.bias[1])
+        dW2, db2 = _linear_wgrad(dy2, dys, act, O, H, ctx.bias[1], ctx.wgrads[1])
         dpre = _x3(dy2, dys, img2T, None, M, H, O, epilogue=2, pre=pre, pre_stride=H)          # (dy . W2) * GELU'(pre)
-        dW1, db1 = _linear_wgrad(dpre, H, x, H, I, ctx.bias[0])
+        dW1, db1 = _linear_wgrad(dpre, H, x, H, I, ctx.bias[0], ctx.wgrads[0])
         dx = _x3(dpre, H, img1T, None, M, I, H, out_shape=x.shape) if ctx.needs_input_grad[0] else None
-        return dx, dW1, db1, dW2, db2
+        return dx, dW1, db1, dW2, db2, None
+
+
+def _mlp_plans(x, w1, w2):
+    (H, I), O, cdt = w1.shape, w2.shape[0], compute_dtype()
+    M = x.numel() // I
+    return linear_plan(M, H, I, cdt, x.is_cuda), linear_plan(M, O, H, cdt, x.is_cuda)
 
 
 def mlp_supported(x, w1, w2):
-    H, I = w1.shape
-    O = w2.shape[0]
-    M = x.numel() // I
-    return bool(compute_dtype() == torch.float32 and x.is_cuda and _x3_ok(M, H, I) and _x3_ok(M, O, H) and _x3_ok(M, I, H)
-                and _x3_ok(M, H, O))
+    """Does ops.mlp run MlpFn: forward and data gradient of both layers on K5x3?"""
+    p1, p2 = _mlp_plans(x, w1, w2)
+    return p1[:2] == p2[:2] == _X3_PAIR
 
 
 def mlp(x, w1, b1, w2, b2):
-    return MlpFn.apply(x, w1, b1, w2, b2)
+    """fc2(GELU(fc1(x))): MlpFn where both layers run forward and data gradient on K5x3, else the two projections and GELU."""
+    p1, p2 = _mlp_plans(x, w1, w2)
+    if p1[:2] == p2[:2] == _X3_PAIR:
+        return MlpFn.apply(x, w1, b1, w2, b2, (p1[2], p2[2]))
+    return linear(torch.nn.functional.gelu(linear(x, w1, b1, p1)), w2, b2, p2)
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -2377,51 +2401,6 @@ def _conv3x3x3_k19(x, xb, w, transposed, O, I, dims):
     return y
 
 
-class Conv3x3x3Fn(torch.autograd.Function):
-    """y = conv3d(x, W, padding=1) for a dense 3 x 3 x 3 kernel (stride 1, no bias): forward and data gradient on K19 (27 shifted
-    split-bf16 GEMMs straight on the NCDHW volumes, no padded copy), weight gradient on K15 (its two padded copies are made in
-    backward)."""
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        x, xb, P = _planes(x, "x")
-        dims = tuple(int(v) for v in x.shape[2:])
-        O, I = int(weight.shape[0]), int(weight.shape[1])
-        w = _require(weight.contiguous(), "weight")
-        y = _conv3x3x3_k19(x, xb, w, False, O, I, dims)
-        ctx.save_for_backward(x, w)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dims = tuple(int(v) for v in x.shape[2:])
-        O, I = int(w.shape[0]), int(w.shape[1])
-        dx = dW = None
-        dy = dy.contiguous()
-        lib = _lib.lib()
-        if ctx.needs_input_grad[0]:
-            if lib.mlagg_conv3x3x3_supported(I, O, *dims):
-                dx = _conv3x3x3_k19(dy, O * dims[0] * dims[1] * dims[2], w, True, I, O, dims)
-            else:                                               # contraction (the layer's output channels) not a multiple of 16
-                dx = _lib_conv_bwd(dy, x, w, 1, 1, False, (True, False, False), _DTYPE_BF16X3)[0]
-        if ctx.needs_input_grad[1]:
-            B = x.shape[0]
-            if K19_3D_WGRAD and lib.mlagg_conv3x3x3_wgrad_supported(O, I, *dims):
-                dW = torch.empty(O, I, 3, 3, 3, device=x.device, dtype=torch.float32)
-                ws = torch.empty(lib.mlagg_conv3x3x3_wgrad_workspace_floats(B, O, I, *dims), device=x.device, dtype=torch.float32)
-                _launch("mlagg_conv3x3x3_wgrad", _ptr(dy), O * dims[0] * dims[1] * dims[2], _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O,
-                        I, *dims)
-            else:                                               # widths that are not multiples of 8: K15 on padded copies
-                dW = conv_weight_grad(x if x.is_contiguous() else x.contiguous(), dy, 3, 1).view(w.shape)
-        return dx, dW
-
-
-def conv3x3x3_supported(x, weight, stride, padding):
-    return (K19_3D and _fp32_map(x, 3) and tuple(weight.shape[2:]) == (3, 3, 3) and _all(stride, 1) and _all(padding, 1)
-            and bool(_lib.lib().mlagg_conv3x3x3_supported(int(weight.shape[0]), int(weight.shape[1]), *(int(v) for v in x.shape[2:]))))
-
-
 def _pad_geometry(D, H, W, stride, wide=False):
     Dq, Hq, Wq, guard = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_long()
     _lib.check(_lib.lib().mlagg_conv_pad_geometry(D, H, W, stride, int(wide), ctypes.byref(Dq), ctypes.byref(Hq), ctypes.byref(Wq),
@@ -2435,20 +2414,6 @@ def _pad_geometry(D, H, W, stride, wide=False):
 # (K15 incl. its two pad copies reaches 28-59 TFLOP/s there) and 4-7x on the 1x1 shapes (plain GEMMs); step 43.5 -> 56.2 ms with it.
 # K16 (forward / data gradient of the 3-D stride-1 convolutions on the tap-GEMM kernel) -- MLAGG_K16=0: MIOpen
 K16 = _os.environ.get("MLAGG_K16", "1") == "1"
-
-
-def conv_wgrad_supported(x, weight, stride, padding):
-    """Kernel 3 with padding 1 or kernel 1 with padding 0, isotropic, stride 1 (2-D and 3-D) or 2 (3-D), fp32 device maps."""
-    nd, k = x.dim() - 2, int(weight.shape[2])
-    return (nd in (2, 3) and _fp32_map(x, nd) and k in (1, 3) and _all(weight.shape[2:], k) and _all(padding, k // 2)
-            and len(set(int(v) for v in stride)) == 1
-            and (int(stride[0]) == 1 or (int(stride[0]) == 2 and nd == 3 and all(int(v) > 1 for v in x.shape[2:]))))
-
-
-def conv_taps_supported(x, weight, stride, padding):
-    """K16: 3-D, stride 1, last extent a multiple of 4, at least 8 input channels (a 1-channel stem would waste 31 / 32 of the MFMAs)."""
-    return (K16 and x.dim() == 5 and conv_wgrad_supported(x, weight, stride, padding) and int(stride[0]) == 1 and x.shape[-1] % 4 == 0
-            and x.shape[1] >= 8)
 
 
 class _Padded:
@@ -2530,71 +2495,105 @@ def _conv_taps(src, weight, O, I, k, flip, dims):
     return y
 
 
-class ConvTapsFn(torch.autograd.Function):
-    """y = conv3d(x, W) (stride 1; kernel 3 pad 1 or kernel 1; no bias) entirely on this package's tap-GEMM kernels: K16 forward on a
-    zero-padded copy of x (kept for backward), K16 data gradient on the padded copy of dy, K15 weight gradient on the two copies."""
+def conv_wgrad_supported(x, weight, stride, padding):
+    """K15's geometry: kernel 3 with padding 1 or kernel 1 with padding 0, isotropic, stride 1 (2-D and 3-D) or 2 (3-D), fp32 device
+    maps."""
+    nd, k = x.dim() - 2, int(weight.shape[2])
+    return (nd in (2, 3) and _fp32_map(x, nd) and k in (1, 3) and _all(weight.shape[2:], k) and _all(padding, k // 2)
+            and len(set(int(v) for v in stride)) == 1
+            and (int(stride[0]) == 1 or (int(stride[0]) == 2 and nd == 3 and all(int(v) > 1 for v in x.shape[2:]))))
 
-    @staticmethod
-    def forward(ctx, x, weight):
-        dims = tuple(x.shape[2:])
-        k = int(weight.shape[2])
-        xp = _Padded(x, dims, 1, True)
-        y = _conv_taps(xp, weight, weight.shape[0], weight.shape[1], k, False, dims)
-        ctx.xp = xp
-        ctx.save_for_backward(weight)
-        ctx.meta = (dims, k)
-        return y
 
-    @staticmethod
-    def backward(ctx, dy):
-        (weight,) = ctx.saved_tensors
-        dims, k = ctx.meta
-        xp = ctx.xp
-        dyp = _Padded(dy, dims, 1, True, as_output_of=xp)
-        dx = dW = None
-        if ctx.needs_input_grad[0]:
-            dx = _conv_taps(dyp, weight, weight.shape[1], weight.shape[0], k, True, dims)
-        if ctx.needs_input_grad[1]:
-            dW = _wgrad_from_padded(xp, dyp, k, 3).view(weight.shape)
-        ctx.xp = None
-        return dx, dW
+def conv_taps_supported(x, weight, stride, padding):
+    """K16: 3-D, stride 1, last extent a multiple of 4, at least 8 input channels (a 1-channel stem would waste 31 / 32 of the MFMAs)."""
+    return (K16 and x.dim() == 5 and conv_wgrad_supported(x, weight, stride, padding) and int(stride[0]) == 1 and x.shape[-1] % 4 == 0
+            and x.shape[1] >= 8)
+
+
+def conv3x3x3_supported(x, weight, stride, padding):
+    """K19's 3-D forward: 3 x 3 x 3, stride 1, padding 1."""
+    return (K19_3D and _fp32_map(x, 3) and tuple(weight.shape[2:]) == (3, 3, 3) and _all(stride, 1) and _all(padding, 1)
+            and bool(_lib.lib().mlagg_conv3x3x3_supported(int(weight.shape[0]), int(weight.shape[1]), *(int(v) for v in x.shape[2:]))))
+
+
+def conv_nd_plan(x, weight, stride, padding):
+    """Where each product of the bias-free convolution of `x` (2-D or 3-D) with `weight` runs: (forward, data gradient, weight
+    gradient) -- "K19", "K16" (tap GEMMs on a wide padded copy of x, kept for K15) or None (the library) for the first two, "K19" or
+    "K15" (tap GEMMs on padded copies) for the third -- or None where the whole layer is the library's.  The layer rules above, in
+    this order; a function of shapes, geometry and the switches above only."""
+    if conv3x3x3_supported(x, weight, stride, padding):
+        O, I, dims, lib = int(weight.shape[0]), int(weight.shape[1]), tuple(int(v) for v in x.shape[2:]), _lib.lib()
+        # the data gradient where its contraction (the layer's output channels) is a multiple of 16, the weight gradient where the
+        # width is a multiple of 8 (else K15 on non-wide padded copies made in backward)
+        return ("K19", "K19" if lib.mlagg_conv3x3x3_supported(I, O, *dims) else None,
+                "K19" if K19_3D_WGRAD and lib.mlagg_conv3x3x3_wgrad_supported(O, I, *dims) else "K15")
+    if conv_taps_supported(x, weight, stride, padding):
+        return "K16", "K16", "K15"
+    return (None, None, "K15") if conv_wgrad_supported(x, weight, stride, padding) else None
 
 
 class ConvNdFn(torch.autograd.Function):
-    """y = conv(x, W) (no bias) on channel-major maps: forward and the data gradient stay MIOpen's (library convolutions, the
-    north star's "conv stem / decoder stages live in PyTorch-ROCm"); the weight gradient is K15."""
+    """y = conv(x, W) (no bias) on channel-major maps, each product where conv_nd_plan says: K19 straight on the NCDHW volumes (27
+    shifted split-bf16 GEMMs, no padded copy), K16 / K15 on zero-padded copies, or the library (MIOpen: the north star's "conv stem /
+    decoder stages live in PyTorch-ROCm")."""
 
     @staticmethod
-    def forward(ctx, x, weight, stride, padding):
-        y = _lib_conv(x, weight, stride, padding, False, _DTYPE_BF16X3)
+    def forward(ctx, x, weight, stride, padding, plan):
+        dims = tuple(int(v) for v in x.shape[2:])
+        O, I = int(weight.shape[0]), int(weight.shape[1])
+        ctx.xp = None
+        if plan[0] == "K19":
+            x, xb, _ = _planes(x, "x")
+            weight = _require(weight.contiguous(), "weight")
+            y = _conv3x3x3_k19(x, xb, weight, False, O, I, dims)
+        elif plan[0] == "K16":
+            ctx.xp = _Padded(x, dims, 1, True)
+            y = _conv_taps(ctx.xp, weight, O, I, int(weight.shape[2]), False, dims)
+            x = None                                                    # backward reads the padded copy
+        else:
+            y = _lib_conv(x, weight, stride, padding, False, _DTYPE_BF16X3)
         ctx.save_for_backward(x, weight)
-        ctx.geom = (stride, padding)
+        ctx.geom, ctx.plan = (stride, padding), plan
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        stride, padding = ctx.geom
+        x, w = ctx.saved_tensors
+        (stride, padding), (_, dgrad, wgrad), xp = ctx.geom, ctx.plan, ctx.xp
+        O, I, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+        if xp is not None:
+            dims, dyp = xp.dims, _Padded(dy, xp.dims, 1, True, as_output_of=xp)
+        else:
+            dims, dy = tuple(int(v) for v in x.shape[2:]), dy.contiguous()
         dx = dW = None
-        dy = dy.contiguous()
         if ctx.needs_input_grad[0]:
-            dx = _lib_conv_bwd(dy, x, weight, stride, padding, False, (True, False, False), _DTYPE_BF16X3)[0]
+            if dgrad == "K19":
+                dx = _conv3x3x3_k19(dy, O * dims[0] * dims[1] * dims[2], w, True, I, O, dims)
+            elif dgrad == "K16":
+                dx = _conv_taps(dyp, w, I, O, k, True, dims)
+            else:
+                dx = _lib_conv_bwd(dy, x, w, stride, padding, False, (True, False, False), _DTYPE_BF16X3)[0]
         if ctx.needs_input_grad[1]:
-            dW = conv_weight_grad(x, dy, int(weight.shape[2]), stride).view(weight.shape)
-        return dx, dW, None, None
+            if wgrad == "K19":
+                B = x.shape[0]
+                dW = torch.empty(O, I, 3, 3, 3, device=x.device, dtype=torch.float32)
+                ws = torch.empty(_lib.lib().mlagg_conv3x3x3_wgrad_workspace_floats(B, O, I, *dims), device=x.device, dtype=torch.float32)
+                _launch("mlagg_conv3x3x3_wgrad", _ptr(dy), O * dims[0] * dims[1] * dims[2], _ptr(x), x.stride(0), _ptr(dW), _ptr(ws), B, O,
+                        I, *dims)
+            elif xp is not None:
+                dW = _wgrad_from_padded(xp, dyp, k, 3).view(w.shape)
+            else:
+                dW = conv_weight_grad(x, dy, k, stride).view(w.shape)
+        ctx.xp = None
+        return dx, dW, None, None, None
 
 
 def conv_nd(x, weight, stride, padding):
-    """Bias-free convolution; the tap-GEMM kernels when the shape is one they are built for (K16 + K15: 3-D stride 1; K15 weight
-    gradient behind MIOpen's forward / data gradient: 3-D stride 2), plain torch otherwise."""
-    if conv3x3x3_supported(x, weight, stride, padding):
-        return Conv3x3x3Fn.apply(x, weight)
-    if conv_taps_supported(x, weight, stride, padding):
-        return ConvTapsFn.apply(x, weight)
-    if conv_wgrad_supported(x, weight, stride, padding):
-        return ConvNdFn.apply(x, weight, int(stride[0]), int(padding[0]))          # isotropic: conv_wgrad_supported
-    conv = torch.nn.functional.conv3d if x.dim() == 5 else torch.nn.functional.conv2d
-    return conv(x, weight, None, stride, padding)
+    """Bias-free convolution on conv_nd_plan's kernels; plain torch where the plan is None."""
+    plan = conv_nd_plan(x, weight, stride, padding)
+    if plan is not None:
+        return ConvNdFn.apply(x, weight, int(stride[0]), int(padding[0]), plan)
+    return (torch.nn.functional.conv3d if x.dim() == 5 else torch.nn.functional.conv2d)(x, weight, None, stride, padding)
 
 
 # ------------------------------------------------------------------------------------------------
