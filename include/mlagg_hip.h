@@ -765,6 +765,48 @@ int mlagg_pp_gather_axis(const double *in, float *out, long long outer, int n_in
                          const double *w, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K26: the segmentation of a TRAINING case and ordered rank selection on the device (reference default_preprocessor.py:38-124
+ * with a seg_file, and experiment_planning/dataset_fingerprint/fingerprint_extractor.py:39-103).  Label volumes are int16;
+ * max_label (0..32767) is the largest label the caller expects.  hist (max_label + 3 counters, DEVICE, or NULL) is zeroed and
+ * filled in the same pass: hist[l + 1] = voxels of label l for l = -1 .. max_label, hist[max_label + 2] = voxels of any other
+ * label (the caller's error check).
+ *   seg_crop:     seg (X, Y, Z) with element strides (sx, sy, sz) >= 0 (the transpose_forward view); lo / ext HOST arrays of 3 (the
+ *                 K22 crop window); mask (ext) uint8 contiguous, the filled non-zero mask.  out (ext) contiguous = the window of
+ *                 seg, with -1 where seg == 0 and mask == 0 (cropping.py:24-49, crop_to_nonzero with a segmentation).
+ *   seg_resize:   in (X, Y, Z) contiguous -> out (Xo, Yo, Zo) contiguous: batchgenerators' resize_segmentation(order=1) as
+ *                 resample_data_or_seg (default_resampling.py:122-212) calls it.  tap_idx / tap_w: DEVICE tables of
+ *                 (Xo + Yo + Zo, 2) ints / doubles, the two source indices (inside the axis) and weights of every output index,
+ *                 axis after axis (export._axis_taps 'linear'; 'nearest' for the low-resolution axis of a separate-z case, whose
+ *                 second weight is 0, which is the in-plane rule on the slice map_coordinates(order=0) picks).  out = the largest
+ *                 label whose fp64 weight sum over the 8 source voxels is >= 0.5, else 0 (the reference starts from zeros and
+ *                 writes the labels in ascending order, -1 included).
+ *   rank_rows:    rows of the rank table for N voxels: ceil(N / MLAGG_PP_RANK_BLOCK).
+ *   rank_counts:  seg (N) contiguous; groups (max_label + 2 DEVICE 64-bit words): bit g of groups[l + 1] set when label l
+ *                 (-1 .. max_label) is in group g < n_groups <= MLAGG_PP_MAX_GROUPS.  table (rank_rows(N), n_groups) int64 =
+ *                 per group, the number of group voxels in the rows before this one (exclusive scan of the per-row counts);
+ *                 totals (n_groups) = the voxels of each group.  No atomics: bit-reproducible.
+ *   rank_select:  for i < n_ranks: the voxel of C-order rank ranks[i] (DEVICE) among the voxels of `group`, i.e.
+ *                 np.argwhere(mask)[ranks] (default_preprocessor.py:134-161).  coords (n_ranks, 4) int64 = (0, x, y, z) with
+ *                 (Y, Z) the two last extents of seg, or NULL; values (C, n_ranks) fp32 = image[c, x, y, z] of an image with
+ *                 element strides (sc, sx, sy, sz) >= 0 (images[c][mask][ranks], fingerprint_extractor.py:58-67), or NULL with
+ *                 image NULL.  A rank outside [0, totals[group]) gives coords of -1 and no value.
+ * All volume offsets are 64-bit.
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_PP_RANK_BLOCK 2048
+#define MLAGG_PP_MAX_GROUPS 64
+int mlagg_pp_seg_crop(const short *seg, int X, int Y, int Z, long long sx, long long sy, long long sz, const int *lo, const int *ext,
+                      const unsigned char *mask, short *out, int max_label, unsigned long long *hist, void *stream);
+int mlagg_pp_seg_resize(const short *in, int X, int Y, int Z, const int *tap_idx, const double *tap_w, short *out, int Xo, int Yo,
+                        int Zo, int max_label, unsigned long long *hist, void *stream);
+size_t mlagg_pp_rank_rows(long long N);
+int mlagg_pp_rank_counts(const short *seg, long long N, const unsigned long long *groups, int max_label, int n_groups,
+                         long long *table, long long *totals, void *stream);
+int mlagg_pp_rank_select(const short *seg, long long N, int Y, int Z, const unsigned long long *groups, int max_label, int n_groups,
+                         int group, const long long *table, const long long *totals, const long long *ranks, long long n_ranks,
+                         long long *coords, const float *image, int C, long long sc, long long sx, long long sy, long long sz,
+                         float *values, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K23: keep the largest connected component (reference nnunetv2/postprocessing/remove_connected_components.py:22-34,
  * remove_all_but_largest_component_from_segmentation, with acvl_utils' remove_all_but_largest_component: full connectivity, every
  * component of the maximal size kept).  labels (X, Y, Z) contiguous uint8, X * Y * Z <= 2^31 - 1 (else MLAGG_E_UNSUPPORTED before

@@ -38,7 +38,7 @@ const char *const kNames[K_COUNT] = {
     "pp_box_kernel", "pp_stats_kernel (+ final)", "pp_normalize_kernel", "pp_minmax_kernel", "pp_cubic_kernel", "pp_gather_kernel",
     "cc_local_kernel", "cc_merge_kernel", "cc_compress_kernel", "cc_size_kernel", "cc_max_kernel", "cc_write_kernel",
     "sf_stats_kernel (+ init)", "sf_codes_kernel", "sf_zpass_kernel", "sf_ypass_kernel", "sf_xpass_kernel", "sf_sum_kernel",
-    "aug3d_resample_kernel"};
+    "aug3d_resample_kernel", "pt_seg_crop_kernel", "pt_seg_resize_kernel", "pt_rank_count_kernel (+ scan)", "pt_rank_select_kernel"};
 }  // namespace
 
 // begin/end pairs of one kernel are issued back to back from one host thread (the launcher), so the

@@ -2893,6 +2893,119 @@ def pp_gather_axis(x, axis, taps):
 
 
 # ------------------------------------------------------------------------------------------------
+# K26: the segmentation of a training case and ordered rank selection (csrc/preprocess_train.hip).  Label volumes are int16
+# device tensors; `max_label` is the largest label the caller expects, and the histograms returned are int64 device tensors
+# (max_label + 3,): labels -1 .. max_label, then the count of any other label.  Inference-style: no autograd.
+# ------------------------------------------------------------------------------------------------
+PP_RANK_BLOCK = _C["MLAGG_PP_RANK_BLOCK"]
+PP_MAX_GROUPS = _C["MLAGG_PP_MAX_GROUPS"]
+
+
+def _pp_label_volume(seg, name, contiguous=True):
+    _expect(seg, name, torch.int16, dim=3, contiguous=contiguous)
+    if min(seg.shape) < 1 or min(seg.stride()) < 0:
+        raise RuntimeError(f"{name}: expected a non-empty (X, Y, Z) volume with non-negative strides, got {tuple(seg.shape)}, {seg.stride()}")
+    return tuple(int(s) for s in seg.shape)
+
+
+def _pp_max_label(max_label):
+    max_label = int(max_label)
+    if not 0 <= max_label <= 32767:
+        raise RuntimeError(f"max_label {max_label}: 0 .. 32767 expected (int16 labels)")
+    return max_label
+
+
+def pp_seg_crop(seg, lo, ext, mask, max_label):
+    """seg (X, Y, Z) int16, any non-negative strides; mask (ext) uint8, the filled non-zero mask of the window -> (the window of seg
+    as contiguous int16 with -1 where seg == 0 and the mask is off, the label histogram of the result)."""
+    shape = _pp_label_volume(seg, "seg", contiguous=False)
+    lo, ext = _pp_window((1,) + shape, lo, ext)
+    _expect(mask, "mask", torch.uint8, shape=ext, like=seg)
+    max_label = _pp_max_label(max_label)
+    out = torch.empty(ext, dtype=torch.int16, device=seg.device)
+    hist = torch.empty(max_label + 3, dtype=torch.int64, device=seg.device)
+    _launch("mlagg_pp_seg_crop", _ptr(seg), *shape, *(int(s) for s in seg.stride()), _int_array(lo), _int_array(ext), _ptr(mask), _ptr(out),
+            max_label, _ptr(hist))
+    return out, hist
+
+
+def pp_seg_resize(seg, taps, out_shape, max_label):
+    """seg (X, Y, Z) contiguous int16 -> (resize_segmentation(order=1) of it to out_shape, the label histogram of the result).
+    taps: export._axis_taps tables (idx, w) of the three axes stacked, (sum(out_shape), 2) each."""
+    shape = _pp_label_volume(seg, "seg")
+    out_shape = tuple(int(s) for s in out_shape)
+    if len(out_shape) != 3 or min(out_shape) < 1:
+        raise RuntimeError(f"pp_seg_resize: output shape {out_shape}")
+    max_label = _pp_max_label(max_label)
+    d_idx, d_w = _export_taps(taps, shape, out_shape, seg.device)
+    out = torch.empty(out_shape, dtype=torch.int16, device=seg.device)
+    hist = torch.empty(max_label + 3, dtype=torch.int64, device=seg.device)
+    _launch("mlagg_pp_seg_resize", _ptr(seg), *shape, _ptr(d_idx), _ptr(d_w), _ptr(out), *out_shape, max_label, _ptr(hist))
+    return out, hist
+
+
+def pp_group_table(groups, max_label, device):
+    """groups: a list of label collections -> the (max_label + 2,) int64 device table of pp_rank_counts: bit g of entry l + 1 is set
+    when label l (-1 .. max_label) is in groups[g]."""
+    max_label = _pp_max_label(max_label)
+    if not 1 <= len(groups) <= PP_MAX_GROUPS:
+        raise RuntimeError(f"{len(groups)} label groups: 1 .. {PP_MAX_GROUPS} are supported")
+    table = np.zeros(max_label + 2, dtype=np.uint64)
+    for g, labels in enumerate(groups):
+        for label in labels:
+            if -1 <= int(label) <= max_label:
+                table[int(label) + 1] |= np.uint64(1 << g)
+    return torch.from_numpy(table.view(np.int64)).to(device)
+
+
+def pp_rank_counts(seg, group_table, n_groups, max_label):
+    """seg: contiguous int16 volume of any rank -> (table (rows, n_groups) int64: per group the number of its voxels before each row
+    of PP_RANK_BLOCK consecutive voxels, totals (n_groups,) int64), both on the device."""
+    _expect(seg, "seg", torch.int16)
+    max_label, n_groups = _pp_max_label(max_label), int(n_groups)
+    if seg.numel() < 1 or not 1 <= n_groups <= PP_MAX_GROUPS:
+        raise RuntimeError(f"pp_rank_counts: {seg.numel()} voxels, {n_groups} groups (1 .. {PP_MAX_GROUPS})")
+    _expect(group_table, "group table", torch.int64, shape=(max_label + 2,), like=seg)
+    rows = int(_lib.lib().mlagg_pp_rank_rows(seg.numel()))
+    table = torch.empty((rows, n_groups), dtype=torch.int64, device=seg.device)
+    totals = torch.empty(n_groups, dtype=torch.int64, device=seg.device)
+    _launch("mlagg_pp_rank_counts", _ptr(seg), seg.numel(), _ptr(group_table), max_label, n_groups, _ptr(table), _ptr(totals))
+    return table, totals
+
+
+def pp_rank_select(seg, group_table, max_label, counts, group, ranks, image=None, coords=True):
+    """The voxels of C-order ranks `ranks` (int64 device tensor (n,)) among the voxels of `group` in seg (X, Y, Z) contiguous int16:
+    np.argwhere(mask)[ranks].  counts = pp_rank_counts(seg, ...).  -> (coords (n, 4) int64 = (0, x, y, z) or None, values (C, n)
+    fp32 = image[:, x, y, z] for an image (C, X, Y, Z) fp32 of any non-negative strides, or None)."""
+    shape = _pp_label_volume(seg, "seg")
+    max_label, group = _pp_max_label(max_label), int(group)
+    table, totals = counts
+    rows = int(_lib.lib().mlagg_pp_rank_rows(seg.numel()))
+    _expect(table, "rank table", torch.int64, dim=2, like=seg)
+    n_groups = int(table.shape[1])
+    if table.shape[0] != rows or not 0 <= group < n_groups <= PP_MAX_GROUPS:
+        raise RuntimeError(f"pp_rank_select: table {tuple(table.shape)} for {rows} rows, group {group}")
+    _expect(totals, "totals", torch.int64, shape=(n_groups,), like=seg)
+    _expect(group_table, "group table", torch.int64, shape=(max_label + 2,), like=seg)
+    _expect(ranks, "ranks", torch.int64, dim=1, like=seg)
+    n = int(ranks.shape[0])
+    if n < 1 or (image is None and not coords):
+        raise RuntimeError("pp_rank_select: at least one rank and one output expected")
+    st, C = (0, 0, 0, 0), 0
+    values = None
+    if image is not None:
+        ishape, st = _strided_volume(image, "image")
+        if ishape[1:] != shape or image.device != seg.device:
+            raise RuntimeError(f"pp_rank_select: image {ishape} does not match the segmentation {shape}")
+        C = ishape[0]
+        values = torch.empty((C, n), dtype=torch.float32, device=seg.device)
+    out = torch.empty((n, 4), dtype=torch.int64, device=seg.device) if coords else None
+    _launch("mlagg_pp_rank_select", _ptr(seg), seg.numel(), shape[1], shape[2], _ptr(group_table), max_label, n_groups, group,
+            _ptr(table), _ptr(totals), _ptr(ranks), n, _ptr(out), _ptr(image), C, *st, _ptr(values))
+    return out, values
+
+
+# ------------------------------------------------------------------------------------------------
 # K23: keep the largest connected component (csrc/components.hip).  The group table maps each label to its mask's group (0: not
 # in any mask); postprocessing.py builds it.  Inference only.
 # ------------------------------------------------------------------------------------------------

@@ -1,23 +1,34 @@
-"""Case preprocessing for prediction (the preprocessing part): the reference's DefaultPreprocessor.run_case
-(mlagg/nnunetv2/preprocessing/preprocessors/default_preprocessor.py:38-124) for a test case (no segmentation), with the default
-plans: transpose by transpose_forward, crop to the non-zero box, normalise every channel, resample to the configuration's spacing
-with resample_data_or_seg_to_shape(order=3, order_z=0, force_separate_z=None) (default_experiment_planner.py:123-128).
+"""Case preprocessing (the preprocessing part): the reference's DefaultPreprocessor.run_case
+(mlagg/nnunetv2/preprocessing/preprocessors/default_preprocessor.py:38-124) with the default plans: transpose by transpose_forward,
+crop to the non-zero box, normalise every channel, resample to the configuration's spacing with
+resample_data_or_seg_to_shape(order=3, order_z=0, force_separate_z=None) (default_experiment_planner.py:123-128).  preprocess_case
+does it for a test case (no segmentation); preprocess_training_case adds the segmentation (cropped with -1 outside the filled
+non-zero mask, resampled with resample_data_or_seg_to_shape(is_seg=True, order=1, order_z=0), :129-135) and the sampled
+class_locations (_sample_foreground_locations, :134-161); preprocess_dataset writes the case folder dataloading.Dataset reads.
 
 A CUDA device runs K22 (csrc/preprocess.hip): the box of the non-zero voxels (one read-back of 6 ints), crop + normalisation in
 fp32, and the cubic zoom one axis at a time in fp64 (prefilter and 4-tap evaluation per line, tap tables from _cubic_taps), clipped
-to each resize call's input range and rounded once to fp32.  Anything else runs the reference's arithmetic on the host with numpy
-and scipy (binary_fill_holes, ndi.zoom + clip): the CPU path and the A/B side of tools/bench_preprocess.py.
+to each resize call's input range and rounded once to fp32; and, for a training case, K26 (csrc/preprocess_train.hip): the
+segmentation's crop, its label-wise linear resize without indicator volumes, a label histogram (the case's second read-back) and
+the ordered rank select that turns the host's RandomState draws into coordinates.  Anything else runs the reference's arithmetic on
+the host with numpy and scipy (binary_fill_holes, ndi.zoom + clip): the CPU path and the A/B side of tools/bench_preprocess*.py.
 
-Parity (tests/test_preprocess_*.py against tests/golden/preprocess.npz, made by the reference's own run_case): the host path is
-bit-identical; on the device, CT / RescaleTo01 / RGB / unnormalised channels agree to 1 fp32 ulp on at most 1e-4 of the voxels
-(the separable fp64 zoom differs from scipy's 3-D one only by its summation order), and ZScore channels to the rounding of numpy's
-fp32 mean / std (ZSCORE_TOLERANCE), since the device sums in fp64.
+Parity (tests/test_preprocess_*.py against tests/golden/preprocess.npz and preprocess_train.npz, made by the reference's own
+run_case): the host path is bit-identical; on the device, CT / RescaleTo01 / RGBTo01 / unnormalised channels agree to 1 fp32 ulp on
+at most 1e-4 of the voxels (the separable fp64 zoom differs from scipy's 3-D one only by its summation order), and ZScore channels
+to the rounding of numpy's fp32 mean / std (ZSCORE_TOLERANCE), since the device sums in fp64.  The device's segmentation equals the
+host's except possibly where a label's interpolated indicator is within NEAR_TIE of the 0.5 threshold; class locations are
+integer work and identical for an identical segmentation.
 
-Not supported (NotImplementedError): training cases (seg_file, class_locations), cascade stages, region-based labels, preprocessors
-other than DefaultPreprocessor, data resamplers other than resample_data_or_seg_to_shape with order 3 and order_z 0 or 1.
+Not supported (NotImplementedError): cascade stages, region-based labels (regions_class_order or multi-value labels),
+preprocessors other than DefaultPreprocessor, data resamplers other than resample_data_or_seg_to_shape with order 3 and order_z 0 or
+1, segmentation resamplers other than resample_data_or_seg_to_shape with order 1 and order_z 0.  Experiment planning stays the
+reference's: the plans are an input (fingerprint.py computes the one entry CT normalisation needs).
 File reading is the caller's: the input is the reader's (c, x, y, z) array and its properties (at least 'spacing').
 """
 import copy
+import os
+import pickle
 
 import numpy as np
 import scipy.ndimage as ndi
@@ -29,6 +40,9 @@ SCHEMES = ("NoNormalization", "CTNormalization", "ZScoreNormalization", "Rescale
 # |device - host| of a ZScore channel: numpy's fp32 pairwise mean / std against the device's fp64 ones, a few fp32 ulps of the
 # statistics relative to the normalised value and to mean / std (tests/test_preprocess_gpu.py)
 ZSCORE_TOLERANCE = 2e-6
+# a voxel of a resampled segmentation is a near-tie when some label's fp64 interpolated indicator v has |v - 0.5| <= NEAR_TIE: only
+# there can another summation order than scipy's flip the label
+NEAR_TIE = 2.0 ** -40
 
 SPLINE_POLE = np.sqrt(3.0) - 2.0
 SPLINE_PAD = 12                      # scipy's _prepad_for_spline_filter
@@ -267,7 +281,10 @@ def _filled_mask_device(x, lo, ext):
     return torch.from_numpy(ndi.binary_fill_holes(nz).astype(np.uint8)).to(x.device)
 
 
-def _preprocess_device(view, schemes, masks, fg, device):
+def _preprocess_device(view, schemes, masks, fg, device, seg=None, max_label=None):
+    """K22's crop + normalisation of view (C, X, Y, Z) -> (data, bbox).  With seg (the (X, Y, Z) int16 view of a training case's
+    labels): -> (data, bbox, cropped seg, its label histogram), and the masked ZScore takes its mask from the cropped segmentation
+    (seg >= 0: labelled voxels where the filled mask is off stay in), as run_case does."""
     from . import ops
     C = view.shape[0]
     box = ops.pp_nonzero_box(view).cpu().tolist()
@@ -286,7 +303,12 @@ def _preprocess_device(view, schemes, masks, fg, device):
             params[c] = [p["percentile_00_5"], p["percentile_99_5"], p["mean"], max(p["std"], 1e-8)]
     d_params = torch.from_numpy(params).to(device)
     stats = torch.zeros((C, 4), dtype=torch.float64, device=device)
-    mask = _filled_mask_device(view, lo, ext) if ops.PP_SCHEMES["ZScoreNormalization+mask"] in codes else None
+    need_mask = ops.PP_SCHEMES["ZScoreNormalization+mask"] in codes
+    if seg is not None:
+        seg, hist = ops.pp_seg_crop(seg, lo, ext, _filled_mask_device(view, lo, ext), max_label)
+        mask = (seg >= 0).to(torch.uint8) if need_mask else None
+    else:
+        mask = _filled_mask_device(view, lo, ext) if need_mask else None
     for c, code in enumerate(codes):
         if code in (2, 3, 4, 5):
             ops.pp_channel_stats(view, lo, ext, c, code, d_params, stats, mask)
@@ -296,23 +318,21 @@ def _preprocess_device(view, schemes, masks, fg, device):
             if code == 5 and (mm[c, 2] < 0 or mm[c, 3] > 255):
                 raise RuntimeError("RGBTo01Normalization: values outside [0, 255]; the image does not seem to be RGB")
     data = ops.pp_normalize(view, lo, ext, torch.tensor(codes, dtype=torch.int32, device=device), d_params, mask)
+    if seg is not None:
+        return data, bbox, seg, hist
     return data, bbox
 
 
-def preprocess_case(image, properties, plans, configuration_name, device=None):
-    """DefaultPreprocessor.run_case for a test case: image (c, x, y, z) (numpy or tensor; cast to float32 as the reader delivers
-    it), properties (the reader's, with 'spacing'), plans (the plans.json dict) -> (data (c, x', y', z') float32, a new properties
-    dict with shape_before_cropping, bbox_used_for_cropping and shape_after_cropping_and_before_resampling).  A CUDA `device` (or a
-    device tensor when device is None) runs K22 and returns a device tensor; otherwise the host path returns a numpy array."""
+def _case_setup(image, properties, plans, configuration_name, device, what):
+    """The checks and plan entries preprocess_case and preprocess_training_case share."""
     cfg = get_configuration(plans, configuration_name)
     if isinstance(image, torch.Tensor):
         on_device = image.is_cuda if device is None else torch.device(device).type == "cuda"
     else:
         on_device = device is not None and torch.device(device).type == "cuda"
     if image.ndim != 4 or min(image.shape) < 1:
-        raise RuntimeError(f"preprocess_case: expected a non-empty (c, x, y, z) image, got shape {tuple(image.shape)}")
+        raise RuntimeError(f"{what}: expected a non-empty (c, x, y, z) image, got shape {tuple(image.shape)}")
     schemes, masks = _check_configuration(cfg, int(image.shape[0]))
-    order, order_z, force_separate_z, threshold = _data_resampling_kwargs(cfg)
     tf = [int(t) for t in plans.get("transpose_forward", [0, 1, 2])]
     if sorted(tf) != [0, 1, 2]:
         raise RuntimeError(f"transpose_forward {tf} is not a permutation of (0, 1, 2)")
@@ -323,8 +343,28 @@ def preprocess_case(image, properties, plans, configuration_name, device=None):
     props = dict(properties)
     original_spacing = [float(props["spacing"][i]) for i in tf]
     perm = [0, *[i + 1 for i in tf]]
+    dev = None
     if on_device:
         dev = torch.device(device) if device is not None else image.device
+    return cfg, dev, schemes, masks, fg, props, original_spacing, perm
+
+
+def _target_shape(cfg, shape, original_spacing):
+    target = [float(s) for s in cfg["spacing"]]
+    if len(target) < 3:
+        target = [original_spacing[0]] + target
+    return target, compute_new_shape(shape, original_spacing, target)
+
+
+def preprocess_case(image, properties, plans, configuration_name, device=None):
+    """DefaultPreprocessor.run_case for a test case: image (c, x, y, z) (numpy or tensor; cast to float32 as the reader delivers
+    it), properties (the reader's, with 'spacing'), plans (the plans.json dict) -> (data (c, x', y', z') float32, a new properties
+    dict with shape_before_cropping, bbox_used_for_cropping and shape_after_cropping_and_before_resampling).  A CUDA `device` (or a
+    device tensor when device is None) runs K22 and returns a device tensor; otherwise the host path returns a numpy array."""
+    cfg, dev, schemes, masks, fg, props, original_spacing, perm = _case_setup(image, properties, plans, configuration_name, device,
+                                                                              "preprocess_case")
+    order, order_z, force_separate_z, threshold = _data_resampling_kwargs(cfg)
+    if dev is not None:
         x = torch.as_tensor(image).to(device=dev, dtype=torch.float32).permute(perm)
         props["shape_before_cropping"] = tuple(int(s) for s in x.shape[1:])
         data, bbox = _preprocess_device(x, schemes, masks, fg, dev)
@@ -338,9 +378,291 @@ def preprocess_case(image, properties, plans, configuration_name, device=None):
             data[c] = _normalize_channel_host(data[c], seg[0], schemes[c], masks[c], fg.get(str(c), {}))
     props["bbox_used_for_cropping"] = bbox
     props["shape_after_cropping_and_before_resampling"] = tuple(int(s) for s in data.shape[1:])
-    target = [float(s) for s in cfg["spacing"]]
-    if len(target) < 3:
-        target = [original_spacing[0]] + target
-    new_shape = compute_new_shape(data.shape[1:], original_spacing, target)
+    target, new_shape = _target_shape(cfg, data.shape[1:], original_spacing)
     data = resample_data_to_shape(data, new_shape, original_spacing, target, order, order_z, force_separate_z, threshold)
     return data, props
+
+
+# ------------------------------------------------------------------------------------------------
+# training cases: the segmentation, class locations, the case folder (K26 on the device)
+# ------------------------------------------------------------------------------------------------
+def _seg_resampling_kwargs(cfg):
+    name = cfg.get("resampling_fn_seg", "resample_data_or_seg_to_shape")
+    if name != "resample_data_or_seg_to_shape":
+        raise NotImplementedError(f"segmentation resampling function {name}: only resample_data_or_seg_to_shape is implemented")
+    kw = dict(cfg.get("resampling_fn_seg_kwargs") or {"is_seg": True, "order": 1, "order_z": 0, "force_separate_z": None})
+    if not kw.get("is_seg", False):
+        raise NotImplementedError("the segmentation resampler must be a segmentation resampler (is_seg)")
+    order, order_z = kw.get("order", 3), kw.get("order_z", 0)
+    _check_seg_orders(order, order_z)
+    return order, order_z, kw.get("force_separate_z", None), kw.get("separate_z_anisotropy_threshold", ANISO_THRESHOLD)
+
+
+def _check_seg_orders(order, order_z):
+    if order != 1 or order_z != 0:
+        raise NotImplementedError(f"segmentation resampling of order {order} / order_z {order_z}: only order 1 with order_z 0 "
+                                  "(the planner's default) is implemented")
+
+
+def _label_lists(dataset_json):
+    """(what run_case collects class locations for, in its order: the foreground labels and, with an ignore label, the list of all
+    labels; the largest label value the dataset declares) -- LabelManager.foreground_labels / all_labels for label-based datasets."""
+    labels = dataset_json["labels"]
+    if "regions_class_order" in dataset_json or any(isinstance(v, (list, tuple)) and len(v) > 1 for v in labels.values()):
+        raise NotImplementedError("region-based labels (regions_class_order or multi-value labels) are not supported")
+    value = {k: int(v[0] if isinstance(v, (list, tuple)) else v) for k, v in labels.items()}
+    if value.get("background") != 0:
+        raise RuntimeError("dataset_json['labels'] must declare 'background': 0")
+    all_labels = sorted({v for k, v in value.items() if k != "ignore"})
+    collect = [v for v in all_labels if v != 0]
+    if "ignore" in value:
+        collect.append(list(all_labels))
+    return collect, max(value.values())
+
+
+def _resize_segmentation_host(seg, new_shape, near=None):
+    """batchgenerators' resize_segmentation(order=1) on skimage's resize(mode='edge', anti_aliasing=False): per label in ascending
+    order, the indicator zoomed linearly (ndi.zoom(grid_mode=True, mode='nearest'), clipped to its range) and written where it is
+    >= 0.5.  near (bool, new_shape): set where an indicator is within NEAR_TIE of 0.5."""
+    out = np.zeros(new_shape, dtype=seg.dtype)
+    zoom = np.asarray(new_shape, float) / np.asarray(seg.shape, float)
+    for c in np.unique(seg):
+        ind = (seg == c).astype(float)
+        v = np.clip(ndi.zoom(ind, zoom, order=1, mode="nearest", grid_mode=True), ind.min(), ind.max())
+        out[v >= 0.5] = c
+        if near is not None:
+            near |= np.abs(v - 0.5) <= NEAR_TIE
+    return out
+
+
+def _resample_seg_host(seg, new_shape, sep, axis, near_tie=False):
+    """resample_data_or_seg (default_resampling.py:122-212) for a segmentation of order 1 / order_z 0: seg (c, x, y, z) of any
+    integer-valued dtype -> (c, *new_shape) of the same dtype; with near_tie also the bool near-tie mask of the same shape."""
+    shape = np.array(seg.shape[1:])
+    new_shape = np.array([int(s) for s in new_shape])
+    data = seg.astype(float)
+    out, nears = [], []
+    for c in range(data.shape[0]):
+        if sep:
+            plane = [a for a in range(3) if a != axis]
+            near = [np.zeros(tuple(new_shape[plane]), dtype=bool) if near_tie else None for _ in range(shape[axis])]
+            r = np.stack([_resize_segmentation_host(np.take(data[c], i, axis), tuple(new_shape[plane]), near[i])
+                          for i in range(shape[axis])], axis)
+            n = np.stack(near, axis) if near_tie else None
+            if shape[axis] != new_shape[axis]:
+                # map_coordinates(order=0, mode='nearest') with the in-plane coordinates on the grid: a pick along the axis alone
+                idx, _ = _axis_taps(int(shape[axis]), int(new_shape[axis]), "nearest")
+                r = np.take(r, idx[:, 0], axis)
+                n = np.take(n, idx[:, 0], axis) if near_tie else None
+        else:
+            n = np.zeros(tuple(new_shape), dtype=bool) if near_tie else None
+            r = _resize_segmentation_host(data[c], tuple(new_shape), n)
+        out.append(r[None])
+        nears.append(n[None] if near_tie else None)
+    out = np.vstack(out).astype(seg.dtype)
+    return (out, np.vstack(nears)) if near_tie else out
+
+
+def _seg_taps(shape, new_shape, sep, axis):
+    """The stacked export._axis_taps tables of K26's resize: linear on every zoomed axis, the order-0 pick on the low-resolution
+    axis of a separate-z case."""
+    tabs = []
+    for a in range(3):
+        kind = "linear"
+        if sep and a == axis:
+            kind = "nearest" if shape[a] != new_shape[a] else "identity"
+        tabs.append(_axis_taps(int(shape[a]), int(new_shape[a]), kind))
+    return np.concatenate([t[0] for t in tabs]), np.concatenate([t[1] for t in tabs])
+
+
+def _as_label_tensor(seg, device=None):
+    """Whatever integer-valued dtype the reader delivered -> an int16 tensor (on `device` when given)."""
+    t = torch.as_tensor(np.ascontiguousarray(seg) if isinstance(seg, np.ndarray) else seg)
+    if device is not None:
+        t = t.to(device)
+    return t if t.dtype == torch.int16 else t.to(torch.int16)
+
+
+def _resample_seg_device(seg, new_shape, sep, axis, max_label):
+    """seg (c, X, Y, Z) int16 on the device -> ((c, *new_shape) int16, the label histogram of the last channel's result)."""
+    from . import ops
+    shape = tuple(int(s) for s in seg.shape[1:])
+    new_shape = tuple(int(s) for s in new_shape)
+    taps = _seg_taps(shape, new_shape, sep, axis)
+    outs = [ops.pp_seg_resize(seg[c].contiguous(), taps, new_shape, max_label) for c in range(seg.shape[0])]
+    return torch.stack([o for o, _ in outs]), outs[-1][1]
+
+
+def resample_seg_to_shape(seg, new_shape, current_spacing, new_spacing, order=1, order_z=0, force_separate_z=None,
+                          separate_z_anisotropy_threshold=ANISO_THRESHOLD):
+    """resample_data_or_seg_to_shape(is_seg=True) (default_resampling.py:76-212) for order 1 / order_z 0: seg (c, x, y, z) of labels
+    -> (c, *new_shape) with the input's dtype.  A device tensor runs K26 (int16 arithmetic: labels -32768 .. 32767), anything else the
+    host path.  As in the reference, a segmentation that already has new_shape is returned unchanged."""
+    _check_seg_orders(order, order_z)
+    in_shape, new_shape = tuple(int(s) for s in seg.shape[1:]), tuple(int(s) for s in new_shape)
+    if len(in_shape) != 3 or len(new_shape) != 3 or min(new_shape) < 1:
+        raise RuntimeError(f"resampling needs three non-empty spatial axes, got {in_shape} -> {new_shape}")
+    sep, axis = separate_z_decision(current_spacing, new_spacing, force_separate_z, separate_z_anisotropy_threshold)
+    if in_shape == new_shape:
+        return seg
+    if isinstance(seg, torch.Tensor) and seg.is_cuda:
+        lo, hi = (int(v) for v in torch.aminmax(seg))
+        if lo < -1 or hi > 32767:
+            raise RuntimeError(f"resample_seg_to_shape: labels {lo} .. {hi}; -1 .. 32767 are supported on the device")
+        out, _ = _resample_seg_device(_as_label_tensor(seg), new_shape, sep, axis, max(hi, 0))
+        return out.to(seg.dtype)
+    if isinstance(seg, torch.Tensor):
+        seg = seg.numpy()
+    return _resample_seg_host(np.asarray(seg), new_shape, sep, axis)
+
+
+def _num_to_sample(n):
+    """_sample_foreground_locations: at most 10000 voxels of a class, but at least 1 % of them."""
+    return max(min(10000, n), int(np.ceil(n * 0.01)))
+
+
+def _sample_locations_host(seg, classes_or_regions, seed):
+    rndst = np.random.RandomState(seed)
+    locs = {}
+    for c in classes_or_regions:
+        k = tuple(c) if isinstance(c, (tuple, list)) else c
+        all_locs = np.argwhere(np.isin(seg, list(c)) if isinstance(c, (tuple, list)) else seg == c)
+        if len(all_locs) == 0:
+            locs[k] = []
+            continue
+        locs[k] = all_locs[rndst.choice(len(all_locs), _num_to_sample(len(all_locs)), replace=False)]
+    return locs
+
+
+def _sample_locations_device(seg, classes_or_regions, seed, max_label, hist=None):
+    """seg (1, X, Y, Z) int16 on the device.  The voxel counts come from hist (the host copy of a K26 label histogram) when given,
+    else from the rank table's totals (one read-back); the draws stay on the host, K26 turns the drawn ranks into coordinates."""
+    from . import ops
+    if seg.dim() != 4 or seg.shape[0] != 1:
+        raise RuntimeError(f"sample_foreground_locations: a (1, x, y, z) segmentation expected, got {tuple(seg.shape)}")
+    vol = seg[0].contiguous()
+    rndst = np.random.RandomState(seed)
+    groups = [[int(v) for v in c] if isinstance(c, (tuple, list)) else [int(c)] for c in classes_or_regions]
+    keys = [tuple(c) if isinstance(c, (tuple, list)) else c for c in classes_or_regions]
+    locs, pending = {}, []
+    for g0 in range(0, len(groups), ops.PP_MAX_GROUPS):
+        part = groups[g0:g0 + ops.PP_MAX_GROUPS]
+        table = ops.pp_group_table(part, max_label, vol.device)
+        counts = ops.pp_rank_counts(vol, table, len(part), max_label)
+        if hist is not None:
+            n_vox = [int(sum(hist[v + 1] for v in set(g) if -1 <= v <= max_label)) for g in part]
+        else:
+            n_vox = [int(v) for v in counts[1].cpu()]
+        for g, n in enumerate(n_vox):
+            key = keys[g0 + g]
+            if n == 0:
+                locs[key] = []
+                continue
+            ranks = torch.from_numpy(rndst.choice(n, _num_to_sample(n), replace=False).astype(np.int64)).to(vol.device)
+            locs[key] = None
+            pending.append((key, ops.pp_rank_select(vol, table, max_label, counts, g, ranks)[0]))
+    if pending:
+        host = torch.cat([c for _, c in pending]).cpu().numpy()
+        at = 0
+        for key, c in pending:
+            locs[key] = host[at:at + c.shape[0]]
+            at += c.shape[0]
+        if host.min() < 0:
+            raise RuntimeError("sample_foreground_locations: the voxel counts do not match the segmentation")
+    return locs
+
+
+def sample_foreground_locations(seg, classes_or_regions, seed=1234):
+    """DefaultPreprocessor._sample_foreground_locations (:134-161): per class (an int) or region (a tuple / list of labels), in the
+    given order, rndst.choice(n, max(min(10000, n), ceil(0.01 n)), replace=False) of its n voxels in C order -> {class or tuple:
+    int64 array (k, 4) of (0, x, y, z) in draw order, or [] for an absent class}.  seg (1, x, y, z): a device tensor (int8 /
+    int16 / any integer dtype with labels in -1 .. 32767) runs K26's rank select, a numpy array the reference's arithmetic."""
+    if isinstance(seg, torch.Tensor) and seg.is_cuda:
+        flat = [int(v) for c in classes_or_regions for v in (c if isinstance(c, (tuple, list)) else (c,))]
+        return _sample_locations_device(_as_label_tensor(seg), classes_or_regions, seed, max([0] + flat))
+    if isinstance(seg, torch.Tensor):
+        seg = seg.numpy()
+    return _sample_locations_host(np.asarray(seg), classes_or_regions, seed)
+
+
+def preprocess_training_case(image, seg, properties, plans, configuration_name, dataset_json, device=None):
+    """DefaultPreprocessor.run_case with a segmentation: image (c, x, y, z) and seg (1, x, y, z) (numpy or tensors, as the reader
+    delivers them; seg of any integer-valued dtype), properties (the reader's, with 'spacing'), plans, dataset_json (its 'labels')
+    -> (data (c, x', y', z') float32, seg (1, x', y', z') int8, or int16 when a label above 127 is present, a new properties dict
+    with the three geometry entries of preprocess_case and class_locations: {label: int64 (k, 4) array of (0, x, y, z), or [] for a
+    class absent from the case}, with the tuple of all labels as one more key when the dataset has an ignore label).
+    A CUDA `device` (or device tensors when device is None) runs K22 + K26 and returns device tensors for data and seg; otherwise
+    the host path returns numpy arrays.  class_locations are host arrays either way: the loader indexes them on the host.  On the
+    device, labels outside -1 .. the dataset's largest label are refused (RuntimeError)."""
+    cfg, dev, schemes, masks, fg, props, original_spacing, perm = _case_setup(image, properties, plans, configuration_name, device,
+                                                                              "preprocess_training_case")
+    order, order_z, force_separate_z, threshold = _data_resampling_kwargs(cfg)
+    _, _, seg_force_separate_z, seg_threshold = _seg_resampling_kwargs(cfg)
+    collect, max_label = _label_lists(dataset_json)
+    if seg.ndim != 4 or seg.shape[0] != 1 or tuple(seg.shape[1:]) != tuple(image.shape[1:]):
+        raise RuntimeError(f"preprocess_training_case: a (1, x, y, z) segmentation matching the image {tuple(image.shape)} expected, "
+                           f"got {tuple(seg.shape)}")
+    if dev is not None:
+        x = torch.as_tensor(image).to(device=dev, dtype=torch.float32).permute(perm)
+        s = _as_label_tensor(seg, dev).permute(perm)
+        props["shape_before_cropping"] = tuple(int(v) for v in x.shape[1:])
+        data, bbox, s, hist = _preprocess_device(x, schemes, masks, fg, dev, s[0], max_label)
+        s = s[None]
+    else:
+        x = image.cpu().numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
+        x = np.array(x, dtype=np.float32).transpose(perm)
+        s = seg.cpu().numpy() if isinstance(seg, torch.Tensor) else np.asarray(seg)
+        s = np.array(s, dtype=np.int16 if s.dtype.kind in "ub" else s.dtype).transpose(perm)      # -1 needs a signed dtype
+        props["shape_before_cropping"] = x.shape[1:]
+        data, s, bbox = crop_to_nonzero(x, s)
+        data = np.array(data)
+        for c in range(data.shape[0]):
+            data[c] = _normalize_channel_host(data[c], s[0], schemes[c], masks[c], fg.get(str(c), {}))
+    props["bbox_used_for_cropping"] = bbox
+    props["shape_after_cropping_and_before_resampling"] = tuple(int(v) for v in data.shape[1:])
+    target, new_shape = _target_shape(cfg, data.shape[1:], original_spacing)
+    old_shape = tuple(int(v) for v in data.shape[1:])
+    data = resample_data_to_shape(data, new_shape, original_spacing, target, order, order_z, force_separate_z, threshold)
+    sep, axis = separate_z_decision(original_spacing, target, seg_force_separate_z, seg_threshold)
+    resize = old_shape != tuple(int(v) for v in new_shape)
+    if dev is not None:
+        if resize:
+            foreign = hist[-1:]                            # a label outside the dataset's range may vanish in the resampling
+            s, hist = _resample_seg_device(s, new_shape, sep, axis, max_label)
+            hist[-1:] += foreign
+        hist = hist.cpu().numpy()                          # the case's second and last read-back
+        if hist[-1]:
+            raise RuntimeError(f"preprocess_training_case: {int(hist[-1])} voxels carry a label outside -1 .. {max_label}, the "
+                               "largest label of dataset_json")
+        props["class_locations"] = _sample_locations_device(s, collect, 1234, max_label, hist)
+        present = np.flatnonzero(hist[:-1])
+        s = s.to(torch.int16 if present.size and present[-1] - 1 > 127 else torch.int8)
+    else:
+        if resize:
+            s = _resample_seg_host(s, new_shape, sep, axis)
+        props["class_locations"] = _sample_locations_host(s, collect, 1234)
+        s = s.astype(np.int16 if np.max(s) > 127 else np.int8)
+    return data, s, props
+
+
+def preprocess_dataset(cases, output_folder, plans, configuration_name, dataset_json, device=None, unpack=False):
+    """The per-case work of the reference's preprocessing run (run_case_save, :126-132): cases is an iterable of (identifier,
+    image, seg, properties); every case goes through preprocess_training_case and is written as <identifier>.npz ('data', 'seg',
+    np.savez_compressed) and <identifier>.pkl (the properties with class_locations) into output_folder, the folder
+    dataloading.Dataset reads.  unpack=True also writes <identifier>.npy / <identifier>_seg.npy, which Dataset.arrays memory-maps.
+    -> the identifiers written, in order."""
+    os.makedirs(output_folder, exist_ok=True)
+    done = []
+    for identifier, image, seg, properties in cases:
+        data, s, props = preprocess_training_case(image, seg, properties, plans, configuration_name, dataset_json, device)
+        if isinstance(data, torch.Tensor):
+            data, s = data.cpu().numpy(), s.cpu().numpy()
+        base = os.path.join(output_folder, identifier)
+        np.savez_compressed(base + ".npz", data=data, seg=s)
+        with open(base + ".pkl", "wb") as fh:
+            pickle.dump(props, fh)
+        if unpack:
+            np.save(base + ".npy", data)
+            np.save(base + "_seg.npy", s)
+        done.append(identifier)
+    return done
