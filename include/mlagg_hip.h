@@ -875,6 +875,46 @@ int mlagg_surface_reduce(const unsigned char *codes, const int *ft, const long l
 int mlagg_aug3d_resample(const float *vol, const short *lab, int B, int C, int Xi, int Yi, int Zi, const double *affine,
                          const int *resample, float *out, float *out_lab, int Xo, int Yo, int Zo, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K27: cell-instance F1 evaluation (reference evaluation/compute_cell_metric.py: skimage.measure.label(seg == 1), dice,
+ * remove_boundary_cells, relabel_sequential, _label_overlap, _intersection_over_union and the threshold test of _true_positive).
+ * All maps are contiguous int32 (H, W) unless said otherwise, H * W <= 2^31 - 1, labels >= 0.  Integer atomics only: every result
+ * is independent of the schedule.
+ *
+ * mlagg_cells_label: seg (H, W) of elem_bytes 1 (uint8) or 4 (int32); parent (H * W int32) = the linear index of the first pixel in
+ *   raster order of the pixel's 8-connected component of {seg == foreground}, -1 elsewhere.  gt (optional, NULL: off): counts
+ *   (3 int32, DEVICE) = |gt > 0|, |seg == foreground|, |both|; without gt only counts[1].  Three launches.
+ *
+ * mlagg_cells_relabel: order-preserving compaction over a view.  key = keys[r * stride + c] + bias for r < h, c < w (bias 1 turns a
+ *   parent map into keys, 0 is the background); keys lie in [0, D), D <= 2^31.  The view stands for an Hr x Wr image whose other
+ *   pixels are zero padding (Hr >= h, Wr >= w).  ring != 0: every key seen in that image's 2-pixel ring (rows 0, 1, Hr - 2, Hr - 1,
+ *   columns alike; needs Hr, Wr >= 5) is dropped, as remove_boundary_cells does.  out (h x w contiguous) = 1 + the number of kept
+ *   smaller keys for a kept key, 0 otherwise; total[0] = the number of kept keys.  Workspace: flags (2 * D bytes), newid (D int32),
+ *   blocksum (mlagg_cells_scan_blocks(D) int32).  Five launches.
+ *
+ * mlagg_cells_overlap: overlap ((n_true + 1) x (n_pred + 1) int32) = pixel counts of every (g, p) label pair, area_t (n_true + 1)
+ *   and area_p (n_pred + 1) = its row and column sums; pixels with a label outside the matrix are not counted.  The matrix may take
+ *   at most MLAGG_CELLS_MAX_OVERLAP_BYTES (else MLAGG_E_UNSUPPORTED before any launch).
+ *
+ * mlagg_cells_match: iou (optional, (n_true + 1) x (n_pred + 1) float64) = ov / (area_t + area_p - ov), 0 where that is 0 / 0.
+ *   thresholds: HOST array of n_thresholds <= MLAGG_CELLS_MAX_THRESHOLDS float64.  edges == NULL: stats (4 x
+ *   MLAGG_CELLS_MAX_THRESHOLDS int32, DEVICE), per threshold t: stats[4 t + 0..2] = the number of pairs i, j >= 1 with iou >= th, the
+ *   largest number of them in one row and in one column (0 for "at most one"); degrees: MLAGG_CELLS_MAX_THRESHOLDS x (n_true +
+ *   n_pred + 2) int32 of workspace.  edges != NULL (n_thresholds == 1): edges (edge_cap x 2 int32) = the pairs (i - 1, j - 1) in no
+ *   particular order, stats[3] = their number.
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_CELLS_MAX_THRESHOLDS 8
+#define MLAGG_CELLS_MAX_OVERLAP_BYTES 1073741824
+int mlagg_cells_label(const void *seg, int elem_bytes, int foreground, const int *gt, int H, int W, int *parent, int *counts,
+                      void *stream);
+size_t mlagg_cells_scan_blocks(long long D);
+int mlagg_cells_relabel(const int *keys, int bias, long long stride, int h, int w, int Hr, int Wr, int ring, long long D,
+                        unsigned char *flags, int *newid, int *blocksum, int *total, int *out, void *stream);
+int mlagg_cells_overlap(const int *g, const int *p, int h, int w, int n_true, int n_pred, int *overlap, int *area_t, int *area_p,
+                        void *stream);
+int mlagg_cells_match(const int *overlap, const int *area_t, const int *area_p, int n_true, int n_pred, const double *thresholds,
+                      int n_thresholds, double *iou, int *degrees, int *stats, int *edges, int edge_cap, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,8 +33,11 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "unionfind.h"
 
 namespace {
+
+using namespace mlagg_uf;
 
 constexpr int TX = 8, TY = 8, TZ = 32;                 // tile; z is the contiguous axis
 constexpr int TV = TX * TY * TZ;                       // 2048 voxels
@@ -86,61 +89,6 @@ __device__ __forceinline__ uint32_t load4(const Vol &v, int x, int y, int z)
     uint32_t w = 0;
     for (int j = 0; j < 4 && z + j < v.Z; ++j) w |= (uint32_t)v.lab[o + j] << (8 * j);
     return w;
-}
-
-// LDS reads in the union loops are atomic loads, so that hipcc re-reads what other lanes' atomicMin changed
-__device__ __forceinline__ int lds_find(int *par, int a)
-{
-    int p = __hip_atomic_load(par + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (p != a) {
-        a = p;
-        p = __hip_atomic_load(par + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return a;
-}
-
-__device__ void lds_unite(int *par, int a, int b)
-{
-    while (true) {
-        a = lds_find(par, a);
-        b = lds_find(par, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&par[b], a);
-        if (old == b) return;
-        b = old;
-    }
-}
-
-__device__ __forceinline__ int gfind(const int *par, int a)
-{
-    int p = __hip_atomic_load(par + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != a) {
-        a = p;
-        p = __hip_atomic_load(par + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return a;
-}
-
-__device__ void gunite(int *par, int a, int b)
-{
-    while (true) {
-        a = gfind(par, a);
-        b = gfind(par, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&par[b], a);
-        if (old == b) return;
-        b = old;
-    }
 }
 
 __device__ __forceinline__ void lane_coords(int t, int &lx, int &ly, int &lz)

@@ -3127,3 +3127,113 @@ def aug3d_resample(vol, lab, affine, resample, out_shape):
     _launch("mlagg_aug3d_resample", _ptr(vol), _ptr(lab), B, C, Xi, Yi, Zi, A.ctypes.data, _int_array(rs.astype(int)), _ptr(out),
             _ptr(out_lab), Xo, Yo, Zo)
     return out, out_lab
+
+
+# ------------------------------------------------------------------------------------------------
+# K27: cell-instance F1 evaluation (csrc/cells.hip).  cells.py composes these per image and per tile and does the assignment on the
+# host.  Inference only.
+# ------------------------------------------------------------------------------------------------
+CELLS_MAX_PIXELS = 2 ** 31 - 1
+CELLS_MAX_THRESHOLDS = _C["MLAGG_CELLS_MAX_THRESHOLDS"]
+CELLS_MAX_OVERLAP_BYTES = _C["MLAGG_CELLS_MAX_OVERLAP_BYTES"]
+CELLS_MAX_FLAG_BYTES = 2 ** 30           # the presence flags of a label domain (one byte per possible label)
+
+
+def cells_label(seg, foreground=1, gt=None):
+    """seg (H, W) contiguous uint8 or int32 on the device, gt None or an int32 map of the same shape -> (parent (H, W) int32: the
+    linear index of the first pixel in raster order of the pixel's 8-connected component of {seg == foreground}, -1 elsewhere; counts
+    (3,) int32 device tensor: |gt > 0|, |seg == foreground|, |both| (without gt only the middle one))."""
+    if not (isinstance(seg, torch.Tensor) and seg.dtype in (torch.uint8, torch.int32)):
+        raise RuntimeError(f"seg: expected a uint8 or int32 tensor, got {getattr(seg, 'dtype', type(seg))}")
+    _expect(seg, "seg", seg.dtype, dim=2, contiguous=False)
+    if seg.numel() > CELLS_MAX_PIXELS:
+        raise RuntimeError(f"cells_label: {seg.numel()} pixels, at most {CELLS_MAX_PIXELS} are supported")
+    if min(seg.shape) < 1:
+        raise RuntimeError(f"cells_label: empty image {tuple(seg.shape)}")
+    _expect(seg, "seg", seg.dtype, dim=2)
+    if gt is not None:
+        _expect(gt, "gt", torch.int32, shape=seg.shape, like=seg)
+    parent = torch.empty(seg.shape, dtype=torch.int32, device=seg.device)
+    counts = torch.empty(3, dtype=torch.int32, device=seg.device)
+    _launch("mlagg_cells_label", _ptr(seg), seg.element_size(), int(foreground), _ptr(gt), *seg.shape, _ptr(parent), _ptr(counts))
+    return parent, counts
+
+
+def cells_relabel(keys, domain, bias=0, region=None, ring=False):
+    """Order-preserving compaction of a key map to 1..n.  keys (H, W) contiguous int32 on the device; key = keys + bias in
+    [0, domain), 0 = background (bias 1: a parent map of cells_label).  region (r0, c0, Hr, Wr): the Hr x Wr tile at (r0, c0) of the map
+    zero-padded as far as needed (default: the whole map).  ring: drop every key seen in the tile's 2-pixel ring.  Returns (out (h, w)
+    int32: the part of the tile inside the map, n (1,) int32 device tensor: the number of labels kept)."""
+    _expect(keys, "keys", torch.int32, dim=2)
+    H, W = (int(v) for v in keys.shape)
+    r0, c0, Hr, Wr = (0, 0, H, W) if region is None else (int(v) for v in region)
+    h, w = min(Hr, H - r0), min(Wr, W - c0)
+    if r0 < 0 or c0 < 0 or h < 1 or w < 1:
+        raise RuntimeError(f"cells_relabel: the region {region} lies outside the {H} x {W} map")
+    if ring and (Hr < 5 or Wr < 5):
+        raise RuntimeError(f"cells_relabel: a {Hr} x {Wr} image has no interior inside its 2-pixel ring; at least 5 x 5 is supported")
+    D = int(domain)
+    if D < 1 or D > 2 ** 31:
+        raise RuntimeError(f"cells_relabel: a label domain of {D}, 1 to 2^31 are supported")
+    dev = keys.device
+    flags = torch.empty(2 * D, dtype=torch.uint8, device=dev)
+    newid = torch.empty(D, dtype=torch.int32, device=dev)
+    blocksum = torch.empty(int(_lib.lib().mlagg_cells_scan_blocks(D)), dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int32, device=dev)
+    out = torch.empty((h, w), dtype=torch.int32, device=dev)
+    _launch("mlagg_cells_relabel", keys.data_ptr() + 4 * (r0 * W + c0), int(bias), W, h, w, Hr, Wr, int(bool(ring)), D, _ptr(flags),
+            _ptr(newid), _ptr(blocksum), _ptr(total), _ptr(out))
+    return out, total
+
+
+def cells_overlap(g, p, n_true, n_pred):
+    """g, p (h, w) contiguous int32 label maps on the device with labels in [0, n_true] / [0, n_pred] -> (overlap (n_true + 1,
+    n_pred + 1) int32 pixel counts of every label pair, area_t (n_true + 1,), area_p (n_pred + 1,): its row and column sums)."""
+    _expect(g, "g", torch.int32, dim=2)
+    _expect(p, "p", torch.int32, shape=g.shape, like=g)
+    n_true, n_pred = int(n_true), int(n_pred)
+    nbytes = 4 * (n_true + 1) * (n_pred + 1)
+    if n_true < 0 or n_pred < 0 or nbytes > CELLS_MAX_OVERLAP_BYTES:
+        raise RuntimeError(f"cells_overlap: a ({n_true} + 1) x ({n_pred} + 1) int32 overlap matrix takes {nbytes} bytes, at most "
+                           f"{CELLS_MAX_OVERLAP_BYTES} are supported")
+    overlap = torch.empty((n_true + 1, n_pred + 1), dtype=torch.int32, device=g.device)
+    area_t = torch.empty(n_true + 1, dtype=torch.int32, device=g.device)
+    area_p = torch.empty(n_pred + 1, dtype=torch.int32, device=g.device)
+    _launch("mlagg_cells_overlap", _ptr(g), _ptr(p), *g.shape, n_true, n_pred, _ptr(overlap), _ptr(area_t), _ptr(area_p))
+    return overlap, area_t, area_p
+
+
+def cells_match(overlap, area_t, area_p, thresholds, want_iou=False):
+    """Per threshold (at most CELLS_MAX_THRESHOLDS) the edges {iou >= th} among the pairs i, j >= 1 of cells_overlap's result.
+    Returns (stats (len(thresholds), 3) int32 device tensor: edge count, largest row degree, largest column degree, the degrees 0
+    where no row / column has more than one edge; iou (n_true + 1, n_pred + 1) float64 or None)."""
+    _expect(overlap, "overlap", torch.int32, dim=2)
+    rows, pitch = (int(v) for v in overlap.shape)
+    _expect(area_t, "area_t", torch.int32, shape=(rows,), like=overlap)
+    _expect(area_p, "area_p", torch.int32, shape=(pitch,), like=overlap)
+    th = np.ascontiguousarray(np.asarray(list(thresholds), dtype=np.float64).reshape(-1))
+    if th.shape[0] > CELLS_MAX_THRESHOLDS:
+        raise RuntimeError(f"cells_match: {th.shape[0]} thresholds, at most {CELLS_MAX_THRESHOLDS} per call")
+    dev = overlap.device
+    iou = torch.empty((rows, pitch), dtype=torch.float64, device=dev) if want_iou else None
+    degrees = torch.empty(CELLS_MAX_THRESHOLDS * (rows + pitch), dtype=torch.int32, device=dev)
+    stats = torch.empty((CELLS_MAX_THRESHOLDS, 4), dtype=torch.int32, device=dev)
+    _launch("mlagg_cells_match", _ptr(overlap), _ptr(area_t), _ptr(area_p), rows - 1, pitch - 1, th.ctypes.data, th.shape[0], _ptr(iou),
+            _ptr(degrees), _ptr(stats), None, 0)
+    return stats[:th.shape[0], :3], iou
+
+
+def cells_edges(overlap, area_t, area_p, threshold, count):
+    """The `count` pairs (i - 1, j - 1), i, j >= 1, with iou >= threshold as a (count, 2) int32 device tensor, in no particular order
+    (count: the edge count cells_match reported for this threshold)."""
+    _expect(overlap, "overlap", torch.int32, dim=2)
+    rows, pitch = (int(v) for v in overlap.shape)
+    count = int(count)
+    if count < 1:
+        raise RuntimeError(f"cells_edges: an edge count of {count}")
+    th = np.asarray([threshold], dtype=np.float64)
+    stats = torch.empty((CELLS_MAX_THRESHOLDS, 4), dtype=torch.int32, device=overlap.device)
+    edges = torch.empty((count, 2), dtype=torch.int32, device=overlap.device)
+    _launch("mlagg_cells_match", _ptr(overlap), _ptr(area_t), _ptr(area_p), rows - 1, pitch - 1, th.ctypes.data, 1, None, None,
+            _ptr(stats), _ptr(edges), count)
+    return edges
