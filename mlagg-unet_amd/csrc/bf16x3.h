@@ -4,20 +4,9 @@
 // error of an fp32 FMA chain (the dropped terms are 2^-24 of a product); six v_mfma_f32_32x32x16_bf16 stand for eight
 // v_mfma_f32_32x32x2_f32 at 1/16 of their cost each.  Used by K5 (linear_lp.hip MODE 2) and K5w (linear_wgrad.hip).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
+#include "mfma.h"
 
 namespace bf16x3 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// two fp32 -> one dword of two bf16 (round to nearest even), low half = first value
-__device__ __forceinline__ unsigned pack2(float a, float b)
-{
-    const __hip_bfloat162 v = __float22bfloat162_rn(make_float2(a, b));
-    return *reinterpret_cast<const unsigned *>(&v);
-}
 
 // (a, b) -> three dwords, each holding one bf16 piece of a (low half) and of b (high half).  Pieces by TRUNCATION: hi = the top 16
 // bits of x, r = x - hi (exact), mid = the top 16 bits of r, lo = the top 16 bits of r - mid.  A 24-bit significand splits into
@@ -37,11 +26,7 @@ __device__ __forceinline__ void split3(float a, float b, unsigned &hi, unsigned 
     lo = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
 }
 
-__device__ __forceinline__ f32x16 mfma(const uint4 &a, const uint4 &b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8 *>(&a), *reinterpret_cast<const bf16x8 *>(&b), c, 0, 0,
-                                                   0);
-}
+__device__ __forceinline__ f32x16 mfma(const uint4 &a, const uint4 &b, f32x16 c) { return mfma16<true>(a, b, c); }
 
 // The six partial products, smallest first, as (piece of a, piece of b).  Kernels issue them TERM-MAJOR over their accumulator
 // tiles -- for each term, every tile -- so that consecutive MFMAs never depend on each other: tile-major (the six terms of a tile

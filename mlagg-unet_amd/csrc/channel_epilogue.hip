@@ -19,15 +19,10 @@
 #include "lpio.h"
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "activations.h"
+#include "reduce.h"
 
 namespace {
-
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float x)
-{
-    const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
-    return cdf + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
 
 // one workgroup per (batch, channel) plane
 template <bool GELU>
@@ -90,7 +85,7 @@ channel_gelu_bwd_kernel(const float *__restrict__ pre, const float *__restrict__
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
         __syncthreads();
-        if (threadIdx.x == 0) part[(size_t)b * C + c] = (red[0] + red[1]) + (red[2] + red[3]);
+        if (threadIdx.x == 0) part[(size_t)b * C + c] = sum4(red);
     }
 }
 
@@ -177,7 +172,7 @@ channel_epilogue_lp_bwd_kernel(const void *__restrict__ x, int xdt, const float 
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
         __syncthreads();
-        if (threadIdx.x == 0) part[plane] = (red[0] + red[1]) + (red[2] + red[3]);
+        if (threadIdx.x == 0) part[plane] = sum4(red);
     }
 }
 

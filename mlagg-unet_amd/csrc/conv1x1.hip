@@ -26,8 +26,6 @@
 
 namespace {
 
-using bf16x3::f32x16;
-
 template <int T>
 struct __attribute__((packed, aligned(4))) FVec {
     float v[T];
@@ -220,7 +218,7 @@ int make_wgeom(W1Geom &g, int B, int O, int I, int P, long dy_batch, long x_batc
     g = W1Geom{B, O, I, P, dy_batch, x_batch, 0, 0};
     const int og = (O + 95) / 96, ig = (I + 95) / 96;
     // 1.5 waves per SIMD (1536: best of 1024 / 1536 / 2048 / 3072 / 4096 on the step's shapes) over (sample, slab, channel groups); at least 64 pixels per slab
-    static const int target = [] { const char *e = getenv("MLAGG_K18_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1536; }();
+    static const int target = mlagg_internal::env_int("MLAGG_K18_WAVES", 1536, 1);
     int per_sample = (target + B * og * ig - 1) / (B * og * ig);
     if (per_sample < 1) per_sample = 1;
     int slab = (P + per_sample - 1) / per_sample;

@@ -26,11 +26,9 @@
 #include "prof.h"
 #include "bf16x3.h"
 #include "opmode.h"
+#include "internal.h"
 
 namespace {
-
-using bf16x3::f32x16;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));      // native vector: HIP's uint4 (a struct) kept register arrays on the stack
 
 template <int T>
 struct __attribute__((packed, aligned(4))) FVec {
@@ -437,7 +435,6 @@ template <int TO, int TI, int DT>
 __global__ void __launch_bounds__(64)
 conv3x3_wgrad16_kernel(const float *__restrict__ dY, const float *__restrict__ X, float *__restrict__ part, W16Geom g)
 {
-    using opmode::f32x4;
     constexpr int NQ = opmode::Form<DT>::NQ, NT = opmode::Form<DT>::NT;
     const int lane = threadIdx.x, r16 = lane & 15, kg = lane >> 4;
     // workgroup id -> (XCD, its dispatch slot): slots 3 n .. 3 n + 2 of an XCD are the kernel rows of slab 8 n + xcd
@@ -524,7 +521,7 @@ conv3x3_wgrad16_kernel(const float *__restrict__ dY, const float *__restrict__ X
                     for (int a = 0; a < TO; ++a)
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx)
-                            acc[a][j][kx] = opmode::mfma16<DT>(aq[a][opmode::Form<DT>::termA(term)], bq[kx][opmode::Form<DT>::termB(term)],
+                            acc[a][j][kx] = opmode::mfma_16x16x32<DT>(aq[a][opmode::Form<DT>::termA(term)], bq[kx][opmode::Form<DT>::termB(term)],
                                                                acc[a][j][kx]);
             }
         }
@@ -576,7 +573,6 @@ template <int TO, int TI, int DT>
 __global__ void __launch_bounds__(64)
 conv3x3_wgrad16_lds_kernel(const float *__restrict__ dY, const float *__restrict__ X, float *__restrict__ part, W16Geom g, long dy_last)
 {
-    using opmode::f32x4;
     constexpr int NQ = opmode::Form<DT>::NQ, NT = opmode::Form<DT>::NT;
     constexpr int AP = 36, BP = 44;                              // LDS row pitches, floats
     constexpr int AROWS = 16 * TO, BROWS = 16 * TI;
@@ -616,7 +612,7 @@ conv3x3_wgrad16_lds_kernel(const float *__restrict__ dY, const float *__restrict
     }
     const long baseA = (long)b * g.dy_batch + pb;                                          // float index of (row 0, pixel pb)
     const long baseB = (long)b * g.x_batch + pb + (long)(ky - 1) * g.W - 4;                // ... of the x window's first float
-    opmode::f32x4 ga[NLA], gb[NLB];                              // native vectors: arrays of HIP's float4 struct went to scratch
+    f32x4 ga[NLA], gb[NLB];                              // native vectors: arrays of HIP's float4 struct went to scratch
     // every load is unconditional; a lane's offset is clamped into the operand (uniform bounds per block, 32-bit per-lane arithmetic):
     // a displaced chunk only holds values that are masked (tail pixels, a source row outside the image, neighbours across an edge)
     auto fetch = [&](int blk) __attribute__((always_inline)) {
@@ -625,15 +621,15 @@ conv3x3_wgrad16_lds_kernel(const float *__restrict__ dY, const float *__restrict
         const int loB = (int)min(max(-ub, 0L), 0x7fffffffL), hiB = (int)min(g.x_last + 4 - ub, 0x7fffffffL);
         const float *pa = dY + ua, *pbx = X + ub;
 #pragma unroll
-        for (int m = 0; m < NLA; ++m) ga[m] = *reinterpret_cast<const opmode::f32x4 *>(pa + min(offA[m], hiA));
+        for (int m = 0; m < NLA; ++m) ga[m] = *reinterpret_cast<const f32x4 *>(pa + min(offA[m], hiA));
 #pragma unroll
-        for (int m = 0; m < NLB; ++m) gb[m] = *reinterpret_cast<const opmode::f32x4 *>(pbx + min(max(offB[m], loB), hiB));
+        for (int m = 0; m < NLB; ++m) gb[m] = *reinterpret_cast<const f32x4 *>(pbx + min(max(offB[m], loB), hiB));
     };
     auto stage = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
-        for (int m = 0; m < NLA; ++m) *reinterpret_cast<opmode::f32x4 *>(&sA[buf][ldsA[m]]) = ga[m];
+        for (int m = 0; m < NLA; ++m) *reinterpret_cast<f32x4 *>(&sA[buf][ldsA[m]]) = ga[m];
 #pragma unroll
-        for (int m = 0; m < NLB; ++m) *reinterpret_cast<opmode::f32x4 *>(&sB[buf][ldsB[m]]) = gb[m];
+        for (int m = 0; m < NLB; ++m) *reinterpret_cast<f32x4 *>(&sB[buf][ldsB[m]]) = gb[m];
     };
     int x0 = (pb + 8 * kg) % g.W, y = (pb + 8 * kg) / g.W, pl = pb + 8 * kg;
     auto consume = [&](int buf) __attribute__((always_inline)) {
@@ -677,7 +673,7 @@ conv3x3_wgrad16_lds_kernel(const float *__restrict__ dY, const float *__restrict
                     for (int a = 0; a < TO; ++a)
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx)
-                            acc[a][j][kx] = opmode::mfma16<DT>(aq[a][opmode::Form<DT>::termA(term)], bq[kx][opmode::Form<DT>::termB(term)],
+                            acc[a][j][kx] = opmode::mfma_16x16x32<DT>(aq[a][opmode::Form<DT>::termA(term)], bq[kx][opmode::Form<DT>::termB(term)],
                                                                acc[a][j][kx]);
             }
         }
@@ -727,7 +723,7 @@ int make_w16geom(W16Geom &g, int B, int O, int I, int H, int W, long dy_batch, l
     g = W16Geom{B, O, I, H, W, (int)P, dy_batch, x_batch, 0, 0, 0, (long)(B - 1) * x_batch + (long)I * P - 8, 32 / W, 32 % W};
     const int og = (O + 16 * to - 1) / (16 * to), ig = (I + 16 * ti - 1) / (16 * ti);
     // two waves per SIMD over (sample, slab, kernel row, channel blocks); at least eight 32-pixel blocks per slab
-    static const int target = [] { const char *e = getenv("MLAGG_K19W16_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2048; }();
+    static const int target = mlagg_internal::env_int("MLAGG_K19W16_WAVES", 2048, 1);
     int per_sample = (target + B * og * ig * 3 - 1) / (B * og * ig * 3);
     const long cap = (256L << 20) / (4L * 9 * O * I) / B;   // partial blocks: under 256 MB in total
     if (per_sample > cap) per_sample = (int)cap;
@@ -748,7 +744,7 @@ int w16_tiles(int O, int I, int dt, int &to, int &ti)
     // MLAGG_K19W16: 0 = the 32 x 32 form, 1 = fragment-shaped loads, 2 = LDS-staged lines, unset = by operand form.  Measured on the step's
     // shapes (profiles/round4_h_conv3x3_wgrad_forms.log): the six-product form is bound by vector-instruction issue (operand
     // splitting) and loses 5-10 % to the staging instructions; the one-product forms are bound by the loads and gain 20-35 % from them.
-    static const int mode = [] { const char *e = getenv("MLAGG_K19W16"); return e ? atoi(e) : -1; }();
+    static const int mode = mlagg_internal::env_int("MLAGG_K19W16", -1);
     if (!mode) return 0;
     to = 3;
     ti = I <= 16 ? 1 : 3;
@@ -762,7 +758,7 @@ int make_w3geom(W3Geom &g, int B, int O, int I, int D, int H, int W, long dy_bat
     if ((P & 15) || P >= (1L << 28) || dy_batch < (long)O * P || x_batch < (long)I * P || ((dy_batch | x_batch) & 3)) return MLAGG_E_UNSUPPORTED;
     g = W3Geom{B, O, I, D, H, W, (int)P, D > 1 ? 3 : 1, dy_batch, x_batch, 0, 0, (long)(B - 1) * x_batch + (long)I * P - 8};
     const int og = (O + 31) / 32, ig = (I + 31) / 32;
-    static const int target = [] { const char *e = getenv("MLAGG_K19W_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2048; }();
+    static const int target = mlagg_internal::env_int("MLAGG_K19W_WAVES", 2048, 1);
     int per_sample = (target + B * og * ig * g.nz - 1) / (B * og * ig * g.nz);
     // partial blocks are (taps x O x I) floats each: keep their total under 256 MB (wide layers have many channel tiles per slab anyway)
     const long cap = (256L << 20) / (4L * 9 * g.nz * O * I) / B;
@@ -776,7 +772,6 @@ int make_w3geom(W3Geom &g, int B, int O, int I, int D, int H, int W, long dy_bat
     if ((long)B * g.nslabs > 2147483647L || og > 65535 || ig > 65535) return MLAGG_E_UNSUPPORTED;
     return 0;
 }
-
 
 template <int TO, int TP>
 void launch(const float *x, const unsigned short *wimg, const float *bias, float *y, const C3Geom &g, int dt, hipStream_t st)

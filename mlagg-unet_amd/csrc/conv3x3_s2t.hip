@@ -35,8 +35,6 @@
 
 namespace {
 
-using opmode::f32x16;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned OOB = 0x80000000u;          // a buffer offset past the 2 GB range of every resource here: the load returns 0
 constexpr int WAVES = 4;
 

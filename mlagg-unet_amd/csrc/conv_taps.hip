@@ -23,10 +23,10 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int MAXTAPS = 27;
 constexpr int CCH = 32;                 // contraction channels per LDS weight image
 constexpr int WAVE_VOX = 128;           // voxels per wave: 32 lanes x float4

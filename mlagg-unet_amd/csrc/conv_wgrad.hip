@@ -24,10 +24,10 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int NT = 9;                   // taps per wave
 constexpr int MAXTAPS = 27;
 

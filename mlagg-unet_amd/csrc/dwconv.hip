@@ -13,19 +13,13 @@
 #include "mlagg_hip.h"
 #include "prof.h"
 #include "internal.h"
+#include "activations.h"
 
 namespace {
 
 struct Geom {
     int batch, H, W, C, x_stride, y_stride;
 };
-
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
-__device__ __forceinline__ float dsilu_f(float x)
-{
-    const float s = 1.f / (1.f + __expf(-x));
-    return s * (1.f + x * (1.f - s));
-}
 
 // LDS-tiled 3x3 gather, shared by the forward (FLIP = false: y = bias + sum_j w[j] x[t + off_j], optional
 // SiLU with the pre-activation saved) and the data gradient (FLIP = true: dx = sum_j w[8 - j] g[t + off_j]).

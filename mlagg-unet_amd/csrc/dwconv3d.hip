@@ -14,19 +14,13 @@
 #include "internal.h"
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "activations.h"
 
 namespace {
 
 struct VGeom {
     int B, D, H, W, C, x_stride, y_stride;
 };
-
-__device__ __forceinline__ float silu3_f(float x) { return x / (1.f + __expf(-x)); }
-__device__ __forceinline__ float dsilu3_f(float x)
-{
-    const float s = 1.f / (1.f + __expf(-x));
-    return s * (1.f + x * (1.f - s));
-}
 
 constexpr int TOK = 64;            // tokens per workgroup of the gather kernel
 
@@ -76,7 +70,7 @@ dwconv3d_gather_kernel(const float *__restrict__ x, const float *__restrict__ w,
         }
         if (SILU) {
             if (pre) *reinterpret_cast<float4 *>(pre + (base + t) * C + c) = acc;
-            acc = make_float4(silu3_f(acc.x), silu3_f(acc.y), silu3_f(acc.z), silu3_f(acc.w));
+            acc = make_float4(silu_f(acc.x), silu_f(acc.y), silu_f(acc.z), silu_f(acc.w));
         }
         *reinterpret_cast<float4 *>(y + (base + t) * g.y_stride + c) = acc;
     }
@@ -106,7 +100,7 @@ dwconv3d_wgrad_kernel(const float *__restrict__ x, int x_stride, const float *__
     for (int t = blockIdx.x * WTOK + ln; t < t_end; t += WLANES) {
         float gv = dy[(base + t) * dy_stride + cc];
         if (SILU) {
-            gv *= dsilu3_f(pre[(base + t) * C + cc]);
+            gv *= dsilu_f(pre[(base + t) * C + cc]);
             if (cok) gbuf[(base + t) * C + c] = gv;
         }
         const int d = t / HW, r = t - d * HW, h = r / g.W, wq = r - h * g.W;

@@ -21,6 +21,7 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "internal.h"
 
 namespace {
 
@@ -253,13 +254,7 @@ flash_bwd_kv_kernel(const unsigned short *__restrict__ q, const unsigned short *
     }
 }
 
-template <typename K>
-int allow_lds(K kernel, size_t bytes)
-{
-    if (bytes > 48 * 1024)
-        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return 0;
-}
+using mlagg_internal::allow_lds;
 
 int check(const FGeom &g, int head_dim, int dtype)
 {

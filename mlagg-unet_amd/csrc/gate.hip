@@ -8,10 +8,9 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "activations.h"
 
 namespace {
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
 
 // a0, a1: (rows, h) contiguous; act: (rows, 2h) with row stride act_stride; out: (rows, 2h) contiguous
 __global__ void __launch_bounds__(256)

@@ -11,11 +11,13 @@
 
 #include "../../include/mlagg_hip.h"
 #include "prof.h"
+#include "activations.h"
 
 namespace {
 
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float x)
+// GELU' with the density formed first, x * (c * e) where activations.h's gelu_grad_f has (x * c) * e: another rounding, kept so
+// that this kernel's results stay what they were
+__device__ __forceinline__ float gelu_grad_pdf_f(float x)
 {
     const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
     const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
@@ -84,8 +86,8 @@ gelu_pool_bwd_kernel(const float *__restrict__ s, int s_stride, const float *__r
     const float4 v = *reinterpret_cast<const float4 *>(s + tok * s_stride + 4 * c4);
     const float4 dp = *reinterpret_cast<const float4 *>(dpooled + (p * g.q + c4) * 4);
     *reinterpret_cast<float4 *>(ds + tok * ds_stride + 4 * c4) =
-        make_float4(dp.x * g.inv * gelu_grad_f(v.x), dp.y * g.inv * gelu_grad_f(v.y), dp.z * g.inv * gelu_grad_f(v.z),
-                    dp.w * g.inv * gelu_grad_f(v.w));
+        make_float4(dp.x * g.inv * gelu_grad_pdf_f(v.x), dp.y * g.inv * gelu_grad_pdf_f(v.y), dp.z * g.inv * gelu_grad_pdf_f(v.z),
+                    dp.w * g.inv * gelu_grad_pdf_f(v.w));
 }
 
 int make_geom(PoolGeom &g, int batch, int H, int W, int d, int r, int s_stride)

@@ -16,6 +16,7 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "internal.h"
 
 namespace {
 
@@ -116,13 +117,7 @@ int check(int B, int L, int K, int CB, long tok_stride, int blk_stride)
     return 0;
 }
 
-template <typename Kn>
-int allow_lds(Kn kernel, size_t bytes)
-{
-    if (bytes > 48 * 1024)
-        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return 0;
-}
+using mlagg_internal::allow_lds;
 
 }  // namespace
 

@@ -1,10 +1,42 @@
-// Launchers shared between translation units of libmlagg_hip.so (not part of the C ABI).
+// Host helpers, the column-sum kernels and the launchers shared between translation units of libmlagg_hip.so (not part of the
+// C ABI).  Device helpers live in mfma.h, activations.h and reduce.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stddef.h>
+#include <stdlib.h>
+
+#include "mlagg_hip.h"
 
 namespace mlagg_internal {
 
+// ---- host helpers ----------------------------------------------------------------------------------------------------------------
+// Dynamic LDS of a launch: above the 48 KiB default the kernel has to be allowed it; above the 160 KiB of a CU the shape is unsupported.
+template <typename K>
+int allow_lds(K kernel, size_t bytes)
+{
+    if (bytes > 160 * 1024) return MLAGG_E_UNSUPPORTED;
+    if (bytes > 48 * 1024)
+        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return 0;
+}
+
+// Integer tunable from the environment; unset, or below min_valid: fallback.  Callers keep the result in a function-local static
+// (read once per process).
+inline int env_int(const char *name, int fallback, int min_valid = INT_MIN)
+{
+    const char *e = getenv(name);
+    const int v = e ? atoi(e) : fallback;
+    return v >= min_valid ? v : fallback;
+}
+
+inline bool getenv_flag(const char *name)
+{
+    const char *v = getenv(name);
+    return v && v[0] == '1';
+}
+
+// ---- column sums of per-workgroup partial rows -----------------------------------------------------------------------------------
 // out[c] (+)= sum_r part[r * pitch + c], c < cols: column sums of per-workgroup partial rows.
 // Workgroup = 64 columns x 16 row-groups (1024 threads): coalesced 256-byte row reads, 16-way row
 // parallelism, LDS combine.  Deterministic (fixed summation order), no atomics.

@@ -18,10 +18,9 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 128, BN = 96, KC = 32;
 constexpr int AP = KC + 1;      // A tile pitch

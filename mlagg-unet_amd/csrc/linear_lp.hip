@@ -21,8 +21,6 @@
 // row pitch 80 bytes (the 16-byte operand fetch of 16 consecutive rows then covers 64 distinct banks).  A lane's MFMA
 // operand is 8 consecutive k of one row: one ds_read_b128.
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 
 #include "mlagg_hip.h"
 #include "prof.h"
@@ -30,37 +28,12 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BM = 128, BN = 96, KC = 32;
 constexpr int PITCH = KC + 8;        // 16-bit elements per tile row: 80 bytes
 
 struct LGeom {
     int M, N, K, x_stride, w_stride, y_stride;
 };
-
-// two fp32 -> one dword of two 16-bit values (round to nearest even), low half = first value
-template <bool BF16>
-__device__ __forceinline__ unsigned pack2(float a, float b)
-{
-    if (BF16) {
-        const __hip_bfloat162 v = __float22bfloat162_rn(make_float2(a, b));
-        return *reinterpret_cast<const unsigned *>(&v);
-    }
-    const __half2 v = __floats2half2_rn(a, b);
-    return *reinterpret_cast<const unsigned *>(&v);
-}
-
-template <bool BF16>
-__device__ __forceinline__ f32x16 mfma16(const uint4 &a, const uint4 &b, f32x16 c)
-{
-    if (BF16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8 *>(&a), *reinterpret_cast<const bf16x8 *>(&b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8 *>(&a), *reinterpret_cast<const f16x8 *>(&b), c, 0, 0, 0);
-}
 
 using bf16x3::split3;
 

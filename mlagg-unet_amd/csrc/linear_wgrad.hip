@@ -16,15 +16,12 @@
 // Roofline: HBM-bound, algorithmic bytes 4 * M * (O + I) per launch (dy and x read once).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "internal.h"
 #include "bf16x3.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TMAX = 3;            // output tiles per wave along O and along I
 constexpr int RGROUPS = 16;        // row-groups of the partial reduction
@@ -335,7 +332,7 @@ int make_geom(WGeom &g, int M, int O, int I, int dys, int xs)
     // token slabs: ONE wave per SIMD (1024).  Round 1 ran ~2 per SIMD to hide the operand latency; with the pipelined loads
     // really in flight (see the kernel) one wave does, and half as many partial blocks are written and reduced: 1207 -> 1098 us
     // over the 15 shapes of tools/bench_linear.py (512: 1603, 1536: 1345 -- uneven -- 4096: 1522).  MLAGG_K5W_WAVES overrides.
-    static const int target = [] { const char *e = getenv("MLAGG_K5W_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1024; }();
+    static const int target = mlagg_internal::env_int("MLAGG_K5W_WAVES", 1024, 1);
     int slab = (int)(((long long)M * g.ogroups * g.igroups + target - 1) / target);
     slab = ((slab + 15) / 16) * 16;       // whole 16-token blocks of the 16-deep instruction (and 8 pairs of the fp32 one)
     if (slab < 64) slab = 64;

@@ -21,16 +21,13 @@
 // accumulator VGPRs); the six terms are issued term-major over the tiles (consecutive MFMAs never depend on each other).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "internal.h"
 #include "bf16x3.h"
+#include "activations.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));      // a native vector: arrays of HIP's uint4 struct land in scratch
 
 constexpr int KC = 32;
 constexpr int PITCH = KC + 8;            // 16-bit elements per LDS row: 80 bytes (16 consecutive rows cover all 64 banks)
@@ -38,12 +35,6 @@ constexpr int PITCH = KC + 8;            // 16-bit elements per LDS row: 80 byte
 struct X3Geom {
     int M, N, K, Kp, x_stride, y_stride, pre_stride;
 };
-
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float x)
-{
-    return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
 
 // EPI: 0 y = acc + bias; 1 y = acc + bias (pre-activation), y2 = GELU(y); 2 y = acc * GELU'(pre)
 constexpr int APITCH = KC + 4;           // floats per LDS row of the raw activation tile: 144 bytes (16 consecutive rows: 64 banks)
@@ -326,7 +317,7 @@ extern "C" int mlagg_linear_x3(const float *x, int x_stride, const void *w_image
     // (stage 0 / 1 projections: >= 1024 workgroups); everywhere else 64-column tiles -- a third more workgroups per CU, 10-15 % faster
     // on the 10 240- and 2 560-token shapes; 64-row workgroups for the pooled branch's few hundred rows.
     // MLAGG_X3_TILE=<NW><TN> forces one variant (benchmarks)
-    static const int forced = [] { const char *e = getenv("MLAGG_X3_TILE"); return e ? atoi(e) : 0; }();
+    static const int forced = mlagg_internal::env_int("MLAGG_X3_TILE", 0);
     int nw = M <= 1024 ? 2 : 4, tn = 2;
     if (N % 96 == 0 && (long)((M + 127) / 128) * (N / 96) >= 1024) tn = 3;
     if (forced) { nw = forced / 10; tn = forced % 10; }

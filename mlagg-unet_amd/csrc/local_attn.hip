@@ -26,6 +26,7 @@
 #include "mlagg_hip.h"
 #include "prof.h"
 #include "internal.h"
+#include "reduce.h"
 
 namespace {
 
@@ -41,21 +42,6 @@ struct Geom {
     int q_stride, kv_stride, out_stride;
     float scale;
 };
-
-__device__ __forceinline__ float dpp_xor1(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_xor2(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float quad_sum(float v)
-{
-    v += dpp_xor1(v);
-    v += dpp_xor2(v);
-    return v;
-}
 
 __device__ __forceinline__ void load12(const float *__restrict__ p, float (&x)[PER])
 {
@@ -143,12 +129,12 @@ __device__ __forceinline__ void front_half(const Geom &g, const Unit &u, const f
 #pragma unroll
             for (int e = 0; e < PER; ++e) p += qv[e] * kx[e];
         }
-        lg[j] = (p + dpp_xor1(p)) * g.scale;
+        lg[j] = (p + dpp_quad_xor1(p)) * g.scale;
     }
     window_softmax(lg, f.valid, f.s);
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
-        f.other[j] = dpp_xor2(f.s[j]);
+        f.other[j] = dpp_quad_xor2(f.s[j]);
         f.Aw[j] = u.r < 2 ? f.s[j] - lam * f.other[j] : f.other[j] - lam * f.s[j];
     }
 #pragma unroll

@@ -21,6 +21,7 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "reduce.h"
 
 namespace {
 
@@ -33,13 +34,6 @@ struct LossGeom {
     long HW;
     int ignore;                   // label value whose pixels take no part in the loss (DC_and_CE_loss(ignore_label=...)); -1: none
 };
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // Partial sums leave the workgroup as ONE row [I(C) | P(C) | G(C) | ce] of `part` and are added up in a fixed order by
 // dice_ce_reduce_kernel: the first version accumulated them with float atomics (LDS, then global), which made the LOSS VALUE -- and

@@ -3,9 +3,7 @@
 // there, nnUNetTrainer.py:848), arithmetic stays fp32 in registers.  The element type is a runtime code (uniform branch per access:
 // these kernels wait on memory): MLAGG_DTYPE_F32 / _BF16 / _F16 of include/mlagg_hip.h.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
+#include "mfma.h"
 
 namespace mlagg_lpio {
 
@@ -19,12 +17,7 @@ __device__ __forceinline__ float from16(unsigned short u, int dt)
 
 __device__ __forceinline__ unsigned pack2(float a, float b, int dt)
 {
-    if (dt == 1) {
-        const __hip_bfloat162 v = __float22bfloat162_rn(make_float2(a, b));
-        return *reinterpret_cast<const unsigned *>(&v);
-    }
-    const __half2 v = __floats2half2_rn(a, b);
-    return *reinterpret_cast<const unsigned *>(&v);
+    return dt == 1 ? ::pack2<true>(a, b) : ::pack2<false>(a, b);
 }
 
 // 4 consecutive elements starting at element 4 * i4 of a plane whose first element is 8-byte (16-bit) / 16-byte (fp32) aligned

@@ -6,17 +6,10 @@
 // 16-bit modes run the SAME kernels as the fp32 step at a sixth of its matrix work and a third of its operand-preparation work -- no
 // cast kernels, no 16-bit copies of the maps.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
 #include "mlagg_hip.h"
 #include "bf16x3.h"
 
 namespace opmode {
-
-using bf16x3::f32x16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 template <int DT>
 struct Form {
@@ -33,14 +26,10 @@ inline bool valid(int dt) { return dt == MLAGG_DTYPE_BF16 || dt == MLAGG_DTYPE_F
 template <int DT>
 __device__ __forceinline__ void split(float a, float b, unsigned &hi, unsigned &mid, unsigned &lo)
 {
-    if constexpr (DT == MLAGG_DTYPE_BF16X3) {
+    if constexpr (DT == MLAGG_DTYPE_BF16X3)
         bf16x3::split3(a, b, hi, mid, lo);
-    } else if constexpr (DT == MLAGG_DTYPE_BF16) {
-        hi = bf16x3::pack2(a, b);
-    } else {
-        const __half2 v = __floats2half2_rn(a, b);
-        hi = *reinterpret_cast<const unsigned *>(&v);
-    }
+    else
+        hi = pack2<DT == MLAGG_DTYPE_BF16>(a, b);
 }
 
 template <int DT>
@@ -55,23 +44,17 @@ __device__ __forceinline__ void split8(const float (&f)[8], uint4 (&q)[3])
 template <int DT>
 __device__ __forceinline__ f32x16 mfma(const uint4 &a, const uint4 &b, f32x16 c)
 {
-    if constexpr (DT == MLAGG_DTYPE_F16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8 *>(&a), *reinterpret_cast<const f16x8 *>(&b), c, 0, 0, 0);
-    else
-        return bf16x3::mfma(a, b, c);
+    return mfma16<DT != MLAGG_DTYPE_F16>(a, b, c);
 }
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // the 16 x 16 x 32 shape: lane l holds A[row l & 15][k = 8 (l >> 4) ..+7], B[k = 8 (l >> 4) ..+7][col l & 15]; D[row 4 (l >> 4) + r][col l & 15]
 template <int DT>
-__device__ __forceinline__ f32x4 mfma16(const uint4 &a, const uint4 &b, f32x4 c)
+__device__ __forceinline__ f32x4 mfma_16x16x32(const uint4 &a, const uint4 &b, f32x4 c)
 {
     if constexpr (DT == MLAGG_DTYPE_F16)
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8 *>(&a), *reinterpret_cast<const f16x8 *>(&b), c, 0, 0, 0);
     else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x3::bf16x8 *>(&a),
-                                                       *reinterpret_cast<const bf16x3::bf16x8 *>(&b), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&a), *reinterpret_cast<const bf16x8 *>(&b), c, 0, 0, 0);
 }
 
 // acc[a][b] += A[a] . B[b], term-major (bf16x3.h: consecutive MFMAs never depend on each other)

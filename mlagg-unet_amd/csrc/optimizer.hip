@@ -18,6 +18,7 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "reduce.h"
 
 namespace {
 
@@ -58,7 +59,7 @@ adamw_sumsq_kernel(const TensorRow *__restrict__ table, const int2 *__restrict__
     __syncthreads();
     // one partial per work item, added up in a fixed order by adamw_sumsq_reduce_kernel (a double atomic add made the clip
     // coefficient -- hence every parameter -- depend on the arrival order in the last bit)
-    if (threadIdx.x == 0) sumsq[1 + blockIdx.x] = (double)((red[0] + red[1]) + (red[2] + red[3]));
+    if (threadIdx.x == 0) sumsq[1 + blockIdx.x] = (double)sum4(red);
 }
 
 __global__ void __launch_bounds__(OPT_TPB)

@@ -21,6 +21,8 @@
 #include "prof.h"
 #include "internal.h"
 #include "lpio.h"
+#include "activations.h"
+#include "reduce.h"
 
 namespace {
 
@@ -28,31 +30,26 @@ enum Act { ACT_NONE = 0, ACT_LEAKY = 1, ACT_SILU = 2 };
 
 __device__ __forceinline__ float block_sum(float v, float *red)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = wave_sum(v);
     __syncthreads();                                   // red may still be read from the previous reduction
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
+    return sum4(red);
 }
 
 __device__ __forceinline__ float act_fwd(float v, int act, float slope)
 {
     if (act == ACT_LEAKY) return v > 0.f ? v : v * slope;
-    if (act == ACT_SILU) return v / (1.f + __expf(-v));
+    if (act == ACT_SILU) return silu_f(v);
     return v;
 }
 
 __device__ __forceinline__ float act_bwd(float v, int act, float slope)      // d act / d v at pre-activation v
 {
     if (act == ACT_LEAKY) return v > 0.f ? 1.f : slope;
-    if (act == ACT_SILU) {
-        const float s = 1.f / (1.f + __expf(-v));
-        return s * (1.f + v * (1.f - s));
-    }
+    if (act == ACT_SILU) return dsilu_f(v);
     return 1.f;
 }
-
 
 using namespace mlagg_lpio;
 
@@ -216,8 +213,7 @@ plane_norm_bwd_kernel(PNB a)
 template <int NT>
 __device__ __forceinline__ float block_sum_nt(float v, float *red)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

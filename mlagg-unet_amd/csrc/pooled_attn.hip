@@ -23,6 +23,7 @@
 #include "mlagg_hip.h"
 #include "prof.h"
 #include "internal.h"
+#include "reduce.h"
 
 namespace {
 
@@ -38,11 +39,6 @@ struct Geom {
     int q_stride, kp_stride, vp_stride, out_stride;
     float scale;
 };
-
-__device__ __forceinline__ float dpp_xor1(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-}
 
 template <int NF>
 __device__ __forceinline__ void loadv(const float *__restrict__ p, float (&x)[NF])
@@ -133,14 +129,14 @@ pooled_attn_fwd_kernel(const float *__restrict__ q, const float *__restrict__ kp
     for (int e = 0; e < HD; ++e) o[e] = 0.f;
     for (int p = 0; p < g.P; ++p) {
         const float s = __expf(dotv<HD>(qv, sK + p * HD2 + HD * r) - lse_r);
-        const float so = dpp_xor1(s);
+        const float so = dpp_quad_xor1(s);
         const float w = r == 0 ? s - lam * so : so - lam * s;
         axpyv<HD>(o, w, sV + p * HD2 + HD * r);
     }
     float ss = 0.f;
 #pragma unroll
     for (int e = 0; e < HD; ++e) ss += o[e] * o[e];
-    ss += dpp_xor1(ss);
+    ss += dpp_quad_xor1(ss);
     const float rstd = rsqrtf(ss * (1.f / HD2) + RMS_EPS);
     if (o_pre) storev<HD>(o_pre + tok * g.d + h * HD2 + HD * r, o);
     if (lse) lse[(tok * g.nh + h) * 2 + r] = lse_r;
@@ -190,8 +186,8 @@ pooled_attn_bwd1_kernel(const float *__restrict__ q, const float *__restrict__ k
                 ss += ov[e] * ov[e];
                 dot += subln_w[HD * r + e] * dy[e] * ov[e];
             }
-            ss += dpp_xor1(ss);
-            dot += dpp_xor1(dot);
+            ss += dpp_quad_xor1(ss);
+            dot += dpp_quad_xor1(dot);
             const float rstd = rsqrtf(ss * (1.f / HD2) + RMS_EPS);
             dot *= (1.f / HD2) * rstd * rstd;
 #pragma unroll
@@ -213,7 +209,7 @@ pooled_attn_bwd1_kernel(const float *__restrict__ q, const float *__restrict__ k
             const float *kp = sK + p * HD2 + HD * r;
             const float s = __expf(dotv<HD>(qv, kp) - lse_r);
             float dw = dotv<HD>(dO, sV + p * HD2 + HD * r);
-            dw += dpp_xor1(dw);
+            dw += dpp_quad_xor1(dw);
             const float ds = r == 0 ? dw : -lam * dw;
             const float sds = s * ds;
             Dr += sds;
@@ -324,9 +320,9 @@ pooled_attn_bwd2_kernel(const float *__restrict__ q, const float *__restrict__ k
                 for (int j = 0; j < 4; ++j) { la[j] += qv[e + j] * kr[e + j]; da[j] += ov[e + j] * vh[e + j]; }
             const float l = (la[0] + la[1]) + (la[2] + la[3]);          // this lane's map logit
             float dw = (da[0] + da[1]) + (da[2] + da[3]);
-            dw += dpp_xor1(dw);                                          // d(o) . v over all 48 channels
+            dw += dpp_quad_xor1(dw);                                          // d(o) . v over all 48 channels
             const float s = __expf(l - (r ? st.y : st.x));
-            const float so = dpp_xor1(s);
+            const float so = dpp_quad_xor1(s);
             const float w = r ? so - lam * s : s - lam * so;             // s1 - lam s2 on both lanes
             const float dl = r ? s * (-lam * dw - st.w) : s * (dw - st.z);   // dL/d(logit of this lane's map)
 #pragma unroll
@@ -391,15 +387,7 @@ size_t kv_lds_bytes(const Geom &g, bool with_reduce)
     return fl * sizeof(float);
 }
 
-template <typename K>
-int allow_lds(K kernel, size_t bytes)
-{
-    if (bytes > 160 * 1024) return MLAGG_E_UNSUPPORTED;      // P > ~420 keys: not on the MLAgg path
-    if (bytes > 48 * 1024)
-        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return 0;
-}
+using mlagg_internal::allow_lds;
 
 }  // namespace
 

@@ -20,20 +20,14 @@
 //
 // Roofline: matrix-core / exp bound (6 * 48 * P flop and 4 P exponentials per token and head forward), not HBM.
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 #include <stdint.h>
 
 #include "internal.h"
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int HD = 24, HD2 = 48;
 constexpr int KP = 40;                  // u16 per row of a [row][32 k] operand image: 80 bytes, conflict-free 16-byte reads
@@ -47,45 +41,6 @@ struct LGeom {
     int q_stride, kp_stride, vp_stride, out_stride;
     float scale;
 };
-
-template <bool BF16>
-__device__ __forceinline__ unsigned pack2(float a, float b)
-{
-    if (BF16) {
-        const __hip_bfloat162 v = __float22bfloat162_rn(make_float2(a, b));
-        return *reinterpret_cast<const unsigned *>(&v);
-    }
-    const __half2 v = __floats2half2_rn(a, b);
-    return *reinterpret_cast<const unsigned *>(&v);
-}
-
-template <bool BF16>
-__device__ __forceinline__ u16 cvt1(float a) { return (u16)(pack2<BF16>(a, 0.f) & 0xffff); }
-
-template <bool BF16>
-__device__ __forceinline__ uint4 pack8(const float *v)
-{
-    return make_uint4(pack2<BF16>(v[0], v[1]), pack2<BF16>(v[2], v[3]), pack2<BF16>(v[4], v[5]), pack2<BF16>(v[6], v[7]));
-}
-
-template <bool BF16>
-__device__ __forceinline__ f32x16 mfma16(const uint4 &a, const uint4 &b, f32x16 c)
-{
-    if (BF16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8 *>(&a), *reinterpret_cast<const bf16x8 *>(&b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8 *>(&a), *reinterpret_cast<const f16x8 *>(&b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x16 zero16()
-{
-    f32x16 z;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) z[i] = 0.f;
-    return z;
-}
-
-// row index of accumulator register v in lane half kh (D layout of the 32x32 MFMA)
-__device__ __forceinline__ int acc_row(int v, int kh) { return (v & 3) + 8 * (v >> 2) + 4 * kh; }
 
 // position of contraction element `within` (0..31) of a 32-wide block in the PERMUTED operand images: instruction q (0, 1), lane
 // half h, element e (0..7) -- the order in which the accumulator registers 8q..8q+7 of half h hold their rows
@@ -589,14 +544,7 @@ int make_geom(LGeom &g, int batch, int N, int P, int nh, int qs, int kps, int vp
     return 0;
 }
 
-template <typename K>
-int allow_lds(K kernel, size_t bytes)
-{
-    if (bytes > 160 * 1024) return MLAGG_E_UNSUPPORTED;
-    if (bytes > 48 * 1024)
-        return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return 0;
-}
+using mlagg_internal::allow_lds;
 
 // tokens per workgroup of the key-side kernel: enough workgroups that batch * heads * chunks * key tiles (= waves) fill the chip
 // four times over (with 49 or 64 keys a workgroup is only two waves: 0.73 ms per step at 224 x 224 with 256-token chunks)

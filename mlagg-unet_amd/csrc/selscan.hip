@@ -26,8 +26,6 @@
 
 namespace {
 
-
-
 __device__ __forceinline__ float4 load4(const float *__restrict__ row, int t, int L, bool vec)
 {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -71,7 +69,6 @@ __device__ __forceinline__ float4 activate_delta(float4 raw, float bias, int sof
     }
     return make_float4(r[0], r[1], r[2], r[3]);
 }
-
 
 // Low-rank delta (LR kernels): the fused form of SS2D_skip's `einsum("b k r l, k d r -> b k d l", dts, dt_projs_weight)`
 // (reference MambaSkip.py:430-436).  The R rank rows dtr (B, G, R, L) of the workgroup's group are fetched per
@@ -280,7 +277,6 @@ __global__ void __launch_bounds__(128, 4) selscan_fwd_kernel(const float *__rest
         if (id.s == 0) cdsum[srow] = dsum;
     }
 }
-
 
 // ------------------------------------------------------------------------------------------
 // backward pass 1: reverse-local summaries.  q_l = a_l (q_{l+1} + dy_l C_l) run from q = 0 at the
@@ -1159,13 +1155,6 @@ selscan_bwd_group_kernel(const float *__restrict__ u, const float *__restrict__ 
     }
 }
 
-
-inline bool getenv_flag(const char *name)
-{
-    const char *v = getenv(name);
-    return v && v[0] == '1';
-}
-
 inline int block_threads(const ScanGeom &gm)
 {
     int t = ((4 * gm.CB + 63) / 64) * 64;
@@ -1242,7 +1231,7 @@ int scan_backward(const float *u, const float *delta, const float *Wdt, int R, c
     const dim3 gridb(gb.nchunks, G * gb.nblk, batch), blockb(block_threads(gb));
     // groups of up to 96 channels (every MLAgg-UNet shape: 96): the group-per-wave kernel; wider groups: the channel-block
     // kernel with float-atomic accumulation of dB / dC across the blocks of a group
-    const bool group_form = gm.Hc <= 96 && !getenv_flag("MLAGG_SELSCAN_BWD_BLOCKED");
+    const bool group_form = gm.Hc <= 96 && !mlagg_internal::getenv_flag("MLAGG_SELSCAN_BWD_BLOCKED");
     const int atomic_bc = !group_form && gb.nblk > 1;
     if (atomic_bc) {
         const size_t bytes = (size_t)batch * G * NS * L * sizeof(float);

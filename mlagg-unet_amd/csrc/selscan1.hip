@@ -22,6 +22,7 @@
 #include "internal.h"
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "activations.h"
 
 namespace {
 
@@ -44,16 +45,8 @@ inline int chunk_len(int B, int K, int L)
     return ch;
 }
 
+// not selscan_common.h's wave_lds_fence: this one also pins the machine scheduler (wave_barrier); exchanging them moves instructions
 __device__ __forceinline__ void wave_fence() { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); }
-
-// softplus and sigmoid of the raw delta from one exponential (csrc/selscan.hip softplus_f: series below e = 0.01)
-__device__ __forceinline__ float softplus1(float x, float &e)
-{
-    e = __expf(-fabsf(x));
-    const float small = e * (1.f - e * (0.5f - e * (1.f / 3.f)));
-    const float big = __builtin_amdgcn_logf(1.f + e) * 0.6931471805599453f;
-    return fmaxf(x, 0.f) + (e < 0.01f ? small : big);
-}
 
 // lanes 0..n-1 fetch the parameters of steps l0..l0+n-1 of (b, k) and park them in the wave's LDS tile (step-major rows)
 template <int R>

@@ -4,10 +4,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "internal.h"
+#include "activations.h"
+#include "reduce.h"
 
 namespace {
 
@@ -33,17 +35,6 @@ struct ScanGeom {
     int batch, dim, L, G, Hc, CB, nblk, nchunks;
 };
 
-// softplus(x) = max(x, 0) + log1p(exp(-|x|)).  e = exp(-|x|) is in (0, 1]; for small e the series
-// e - e^2/2 + e^3/3 (truncation < e^4/4 <= 2.5e-9 at e = 0.01) avoids the cancellation of log(1 + e),
-// elsewhere v_log_f32 on 1 + e is accurate to ~1 ulp of a value in [0.01, 0.69].  ~10 VALU ops instead
-// of the ~100 of libm's expf + log1pf, which were 45 % of the forward kernels' instructions (round-1 PMC).
-__device__ __forceinline__ float softplus_f(float x)
-{
-    const float e = __expf(-fabsf(x));
-    const float small = e * (1.f - e * (0.5f - e * (1.f / 3.f)));
-    const float big = __builtin_amdgcn_logf(1.f + e) * 0.6931471805599453f;   // bare v_log_f32 (log2): 1 + e >= 1, no denormal path needed
-    return fmaxf(x, 0.f) + (e < 0.01f ? small : big);
-}
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 // Keep a prefetched value where it is: a fake read-modify of the register.  Without it the compiler is free to SINK a load
 // of a `const __restrict__` row down to its use (it did, past barriers), which turns "all loads of the chunk up front" back
@@ -52,21 +43,6 @@ __device__ __forceinline__ void pin4(float4 &v) { asm volatile("" : "+v"(v.x), "
 // Workgroup barrier for kernels whose waves talk through LDS only: __syncthreads() also releases GLOBAL memory, i.e. waits
 // (vmcnt(0)) for every store of the sub-tile before the next one may start.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ float dpp_quad_xor1(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_quad_xor2(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float quad_sum(float v)
-{
-    v += dpp_quad_xor1(v);
-    v += dpp_quad_xor2(v);
-    return v;
-}
 
 // pass 2: exclusive prefix over chunks of h -> exp(A * dsum_c) h + s_c.  In place: s_c becomes the
 // state ENTERING chunk c.  reverse = true runs from the last chunk (backward's q carries).

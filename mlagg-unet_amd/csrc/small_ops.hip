@@ -13,6 +13,7 @@
 
 #include "mlagg_hip.h"
 #include "prof.h"
+#include "reduce.h"
 
 namespace {
 
@@ -302,7 +303,7 @@ plane_sum_kernel(const float *__restrict__ g, float *__restrict__ part, int C, l
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) part[(size_t)b * C + c] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) part[(size_t)b * C + c] = sum4(red);
 }
 
 }  // namespace
