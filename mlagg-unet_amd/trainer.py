@@ -142,19 +142,19 @@ class ClipAdamW(torch.optim.Optimizer):
 
     def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-4, weight_decay=3e-5, capturable=False):
         params = list(params)
-        if capturable:
-            # hipGraph form (GraphedTrainStep): the learning rate and the step counter live on the device, as torch's
-            # ``capturable`` optimizers keep them; the schedule writes the tensor between replays
-            lr = torch.tensor(float(lr), device=params[0].device, dtype=torch.float32)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=float(lr), betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) != 1:
             # the clip norm is the norm over ALL parameters (clip_grad_norm_(network.parameters(), 12), B:855): one group
             raise RuntimeError("ClipAdamW: one parameter group (the reference passes network.parameters(), T:138)")
         self.capturable = bool(capturable)
+        # hipGraph form (GraphedTrainStep): the step counter and a COPY of the learning rate live on the device.  ``param_groups``
+        # keeps the learning rate as the Python float that schedules assign and training loops log, round and pickle; ``sync_lr``
+        # carries it to the device copy before a replay
         self._step_dev = torch.zeros(1, dtype=torch.int32, device=params[0].device) if capturable else None
+        self._lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=params[0].device) if capturable else None
         self._steps = 0
         self._work = {}
-        self._tables = {}                             # capturable: per parameter set (pinned host table, device table)
+        self._tables = {}                             # capturable: per (parameter set, captured?) (pinned host table, device table)
         self._sumsq = None
         self._stepped = None                          # ids of the parameters of the first step
 
@@ -177,16 +177,33 @@ class ClipAdamW(torch.optim.Optimizer):
                 st["step"] = torch.tensor(n)
         return super().state_dict()
 
-    def load_state_dict(self, sd):
-        lr = self.param_groups[0]["lr"]
-        super().load_state_dict(sd)
+    def sync_lr(self):
+        """Capturable form: write ``param_groups[0]["lr"]`` into the device copy that the update kernel -- and a captured graph --
+        reads.  ``GraphedTrainStep`` calls this before every replay and an eager ``step`` calls it itself; whoever replays a graph
+        of their own calls it after changing the learning rate.  Never inside a capture: the fill would be recorded with the
+        value of that moment and every replay would write it back."""
         if self.capturable:
-            # the device-resident learning rate keeps its ADDRESS (a captured graph reads it): take the value, not the object
-            new = self.param_groups[0]["lr"]
-            lr.fill_(float(new))
-            self.param_groups[0]["lr"] = lr
-        self._work.clear()                            # the moment tensors were replaced: cached addresses are stale
-        self._tables.clear()
+            self._lr_dev.fill_(float(self.param_groups[0]["lr"]))
+
+    def load_state_dict(self, sd):
+        # capturable: a captured graph holds the ADDRESSES of the moment tensors, of the work list and of its pointer table, so
+        # the loaded moments are copied into the existing tensors and all of these stay in place
+        keep = {p: (st["exp_avg"], st["exp_avg_sq"]) for p, st in self.state.items() if st} if self.capturable else {}
+        super().load_state_dict(sd)
+        for g in self.param_groups:
+            g["lr"] = float(g["lr"])                  # a checkpoint written while the learning rate was a device tensor
+        for p, (m, v) in keep.items():
+            st = self.state[p]
+            if st:
+                m.copy_(st["exp_avg"])
+                v.copy_(st["exp_avg_sq"])
+            else:                                     # a checkpoint from before the first step
+                m.zero_()
+                v.zero_()
+                st["step"] = torch.tensor(0.0)
+            st["exp_avg"], st["exp_avg_sq"] = m, v
+        if not self.capturable:
+            self._work.clear()                        # the moment tensors were replaced: cached addresses are stale
         self._stepped = None
         steps = [int(st["step"]) for st in self.state.values() if st and "step" in st]
         self._steps = max(steps) if steps else 0
@@ -242,17 +259,28 @@ class ClipAdamW(torch.optim.Optimizer):
             if self.capturable:
                 # a table that OUTLIVES the call (a replayed graph reads it): one pinned host copy + one device copy per parameter
                 # set, re-uploaded only when a gradient address changed.  Inside a capture the upload becomes a copy node out of
-                # the pinned buffer, whose content then no longer changes (captured gradients sit at fixed addresses)
-                if key not in self._tables:
-                    self._tables[key] = (torch.full_like(host, -1).pin_memory(), torch.empty_like(host, device=dev))
-                pinned, table = self._tables[key]
+                # the pinned buffer, whose content then no longer changes (captured gradients sit at fixed addresses): captured
+                # steps have a pair of their own, which no eager step -- with its own gradient addresses -- ever writes.  Both
+                # pairs are allocated at the first step, whichever form it is: a capture that follows an eager or warm-up step then
+                # pins no memory (a first step INSIDE a capture still does, as it always did), at the price of one unused pair
+                # (40 bytes per parameter) in an optimizer that is never captured
+                capturing = torch.cuda.is_current_stream_capturing()
+                for c in (False, True):
+                    if (key, c) not in self._tables:
+                        self._tables[key, c] = (torch.full_like(host, -1).pin_memory(), torch.empty_like(host, device=dev))
+                pinned, table = self._tables[key, capturing]
                 if not torch.equal(pinned, host):
-                    if not torch.cuda.is_current_stream_capturing():
+                    if not capturing:
                         torch.cuda.current_stream().synchronize()      # an earlier upload may still be reading the pinned buffer
+                    elif int(pinned[0, 0]) != -1:      # column 0 holds parameter addresses; -1 is the fill of a table never written
+                        raise RuntimeError("ClipAdamW: a second capture with other gradient addresses would redirect the first "
+                                           "graph's update; one captured step per optimizer")
                     pinned.copy_(host)
                     table.copy_(pinned, non_blocking=True)
+                if not capturing:
+                    self.sync_lr()
                 _lib.launch("mlagg_adamw_clip_step_dev", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(),
-                            group["lr"].data_ptr(), self._step_dev.data_ptr(), float(b1), float(b2), float(group["eps"]),
+                            self._lr_dev.data_ptr(), self._step_dev.data_ptr(), float(b1), float(b2), float(group["eps"]),
                             float(group["weight_decay"]), float(max_norm))
                 continue
             table = host.pin_memory().to(dev, non_blocking=True)
@@ -268,7 +296,7 @@ class ClipAdamW(torch.optim.Optimizer):
 
 
 def configure_optimizers(model, initial_lr=5e-4, weight_decay=3e-5, fused=None, capturable=False):
-    """AdamW + cosine schedule of reference T:137-147.  ``capturable=True`` keeps the step counter and the
+    """AdamW + cosine schedule of reference T:137-147.  ``capturable=True`` keeps the step counter and a copy of the
     learning rate on the device so that the whole step can live inside one hipGraph (GraphedTrainStep)."""
     # every parameter, in module order, as the reference's ``AdamW(self.network.parameters(), ...)`` (T:138): the
     # frozen ``dummy_tensor`` keeps its slot, so parameter indices in optimizer checkpoints equal the reference's
@@ -303,9 +331,9 @@ class CosineLRSchedule:
     def step(self, epoch):
         for g, base in zip(self.opt.param_groups, self.base):
             if torch.is_tensor(g["lr"]):
-                g["lr"].fill_(self.lr_at(epoch, base))      # device-resident lr: visible to a captured graph
+                g["lr"].fill_(self.lr_at(epoch, base))      # torch's own capturable optimizers keep a tensor there
             else:
-                g["lr"] = self.lr_at(epoch, base)
+                g["lr"] = self.lr_at(epoch, base)           # ClipAdamW: a float in both forms (ClipAdamW.sync_lr)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -516,7 +544,10 @@ class GraphedTrainStep:
     Measured in round 3 with one RCCL rank (bench.py MLAGG_FORCE_DDP=1): the eager DDP step runs (44.7 vs 43.5 ms per step); capturing
     it -- PyTorch's documented DDP-in-graph recipe, 11 side-stream warm-ups -- ends in a segmentation fault inside the capture on this
     PyTorch 2.10 / ROCm 7.0 build (AccumulateGrad nodes stashed by DDP on another stream, then a crash in the RCCL work enqueue:
-    profiles/round3_ddp_graph_capture_segfault.log), so a DistributedDataParallel network is refused here."""
+    profiles/round3_ddp_graph_capture_segfault.log), so a DistributedDataParallel network is refused here.
+    One captured step per optimizer: the graph reads ClipAdamW's pointer table for captured steps, and a second capture whose
+    gradients sit at other addresses would redirect the first graph's update, so ClipAdamW refuses it.  Eager ``train_step``
+    calls with the same optimizer may be mixed with replays freely."""
 
     def __init__(self, network, optimizer, data, target, batch_dice=True, clip=12.0, warmup=3, loss_fn=None):
         if isinstance(network, torch.nn.parallel.DistributedDataParallel) or getattr(network, "_mlagg_grad_sync", None) is not None:
@@ -536,6 +567,7 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss = body()
+        self.optimizer = optimizer
 
     def __call__(self, data=None, target=None):
         if data is not None:
@@ -543,7 +575,13 @@ class GraphedTrainStep:
         if target is not None:
             for dst, src in zip(self.target, target):
                 dst.copy_(src, non_blocking=True)
+        if isinstance(self.optimizer, ClipAdamW):
+            self.optimizer.sync_lr()                  # the learning rate the host holds NOW governs this replay
         self.graph.replay()
+        # the replay rewrote the parameters through raw pointers and ran no host code: stacked weights and weight images that an
+        # eager forward built earlier are one step behind, and no version counter says so
+        from . import ops
+        ops.invalidate_weight_images()
         return self.loss
 
 

@@ -110,6 +110,59 @@ def test_cosine_schedule_matches_timm_formula():
     assert abs(opt.param_groups[0]["lr"] - 1e-6) < 1e-12
 
 
+@pytest.mark.parametrize("capturable", [False, True])
+def test_clip_adamw_learning_rate_is_a_host_float_a_training_loop_can_log(capturable):
+    """What the epoch-start hook of a host training loop does with ``param_groups[0]["lr"]`` after the schedule's step: round it
+    with numpy for the log line, keep it in a logger that is pickled with the checkpoint.  A device tensor there fails both; the
+    capturable form keeps its device copy outside ``param_groups``, so optimizer checkpoints hold no tensor hyper-parameter."""
+    import pickle
+    import numpy as np
+    from mlagg_unet_amd import trainer
+    p = torch.nn.Parameter(torch.zeros(3))
+    opt = trainer.ClipAdamW([p], 5e-4, eps=1e-4, weight_decay=3e-5, capturable=capturable)
+    sched = trainer.CosineLRSchedule(opt, t_initial=500, lr_min=1e-6, warmup_t=10, warmup_lr_init=1e-4)
+    log = []
+    for epoch in (0, 5, 250):
+        sched.step(epoch)
+        lr = opt.param_groups[0]["lr"]
+        assert type(lr) is float and float(lr) == sched.lr_at(epoch, 5e-4)
+        shown = np.round(lr, decimals=5)
+        assert isinstance(shown, float) and np.isfinite(shown) and abs(shown - lr) <= 5e-6
+        log.append(shown)
+        assert pickle.loads(pickle.dumps(log)) == log
+        groups = opt.state_dict()["param_groups"]
+        assert not any(torch.is_tensor(v) for g in groups for v in g.values())
+    opt.load_state_dict(opt.state_dict())
+    assert type(opt.param_groups[0]["lr"]) is float and opt.param_groups[0]["lr"] == sched.lr_at(250, 5e-4)
+
+
+def test_capturable_clip_adamw_loads_moments_into_the_tensors_it_has():
+    """A captured graph holds the addresses of the moment tensors: ``load_state_dict`` of the capturable form copies the loaded
+    values into the existing tensors (the launch-argument form takes the loaded tensors, as torch's optimizers do)."""
+    import copy
+    from mlagg_unet_amd import trainer
+    for capturable in (True, False):
+        ps = [torch.nn.Parameter(torch.zeros(4)), torch.nn.Parameter(torch.zeros(2, 3))]
+        opt = trainer.ClipAdamW(ps, 5e-4, capturable=capturable)
+        for i, p in enumerate(ps):
+            st = opt._state_of(p)
+            st["exp_avg"].fill_(1.0 + i)
+            st["exp_avg_sq"].fill_(10.0 + i)
+        sd = copy.deepcopy(opt.state_dict())
+        for i in range(2):
+            sd["state"][i]["step"] = torch.tensor(7.0)
+            sd["state"][i]["exp_avg"] += 0.5
+        sd["param_groups"][0]["lr"] = 3e-4
+        ptrs = [opt.state[p][k].data_ptr() for p in ps for k in ("exp_avg", "exp_avg_sq")]
+        opt.load_state_dict(sd)
+        assert ([opt.state[p][k].data_ptr() for p in ps for k in ("exp_avg", "exp_avg_sq")] == ptrs) == capturable
+        for i, p in enumerate(ps):
+            assert torch.equal(opt.state[p]["exp_avg"], torch.full_like(p, 1.5 + i))
+            assert torch.equal(opt.state[p]["exp_avg_sq"], torch.full_like(p, 10.0 + i))
+        assert opt.steps_done() == 7 and opt.param_groups[0]["lr"] == 3e-4
+        assert float(opt.state_dict()["state"][1]["step"]) == 7.0
+
+
 def test_product_loss_equals_oracle_loss_on_cpu():
     from mlagg_unet_amd import trainer
     from oracle import mlagg_oracle as O

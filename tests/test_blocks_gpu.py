@@ -604,7 +604,7 @@ def test_clip_adamw_matches_torch(max_norm):
 @gpu
 @pytest.mark.parametrize("max_norm", [12.0, 0.0])
 def test_capturable_clip_adamw_is_bit_identical_to_the_eager_form_and_replays(max_norm):
-    """The hipGraph form of K11 (learning rate and step counter device-resident, mlagg_adamw_clip_step_dev): bit-identical parameters to
+    """The hipGraph form of K11 (step counter and a copy of the learning rate device-resident, mlagg_adamw_clip_step_dev): bit-identical parameters to
     the launch-argument form over eager steps, a captured step replays with a NEW learning rate and advancing bias corrections, and the
     state_dict carries the device counter."""
     from mlagg_unet_amd import trainer as TR
@@ -614,7 +614,7 @@ def test_capturable_clip_adamw_is_bit_identical_to_the_eager_form_and_replays(ma
     pb = [torch.nn.Parameter(p.detach().clone()) for p in pa]
     oa = TR.ClipAdamW(pa, 5e-4, eps=1e-4, weight_decay=3e-5, capturable=True)
     ob = TR.ClipAdamW(pb, 5e-4, eps=1e-4, weight_decay=3e-5)
-    assert torch.is_tensor(oa.param_groups[0]["lr"]) and oa.param_groups[0]["lr"].is_cuda
+    assert type(oa.param_groups[0]["lr"]) is float                               # the device copy lives outside param_groups
     static = [torch.zeros(s, device=DEV) for s in shapes]                        # gradients at fixed addresses, as inside a graph
     for p, st in zip(pa, static):
         p.grad = st
@@ -625,7 +625,8 @@ def test_capturable_clip_adamw_is_bit_identical_to_the_eager_form_and_replays(ma
         for st, q, gr in zip(static, pb, grads[it]):
             st.copy_(gr)
             q.grad = gr.clone()
-        oa.param_groups[0]["lr"].fill_(lrs[it])
+        oa.param_groups[0]["lr"] = lrs[it]
+        oa.sync_lr()                                                             # a raw graph.replay() runs no host code of ours
         ob.param_groups[0]["lr"] = lrs[it]
 
     for it in range(2):                                                          # eager calls of the capturable form

@@ -79,7 +79,8 @@ def test_plugin_replays_the_step_as_a_hipgraph_after_three_eager_steps():
     """The plugin's train_step behind the reference loop (per-step loss read-back, B:863): three eager steps, then the whole step is
     captured and replayed (trainer.GraphedTrainStep, warm-up 0: no batch is trained on twice).  Deterministic mode, DropPath off
     (eval) so that both sides are comparable bit for bit: seven steps on seven different batches end on the losses and parameters of
-    seven eager ``trainer.train_step`` calls on a twin; a batch of another geometry falls back to an eager step."""
+    seven eager ``trainer.train_step`` calls on a twin; a batch of another geometry falls back to an eager step, and the replay
+    after it still lands on the twin's parameters."""
     from mlagg_unet_amd import nnunet_plugin, trainer
     assert nnunet_plugin.PLUGIN_GRAPH
     trainer.set_deterministic(True)
@@ -106,6 +107,10 @@ def test_plugin_replays_the_step_as_a_hipgraph_after_three_eager_steps():
         got = tr.train_step(b)
         want = trainer.train_step(twin, twin_opt, b["data"].cuda(), [t.cuda() for t in b["target"]], batch_dice=True)
         assert float(got["loss"]) == float(want) and tr.optimizer.steps_done() == 9
+        # the losses are computed BEFORE the update: only the parameters show whether the replay after the eager step applied its
+        # own gradients (the eager step uploads a pointer table with other gradient addresses)
+        for (k, a), q in zip(tr.network.state_dict().items(), twin.state_dict().values()):
+            assert torch.equal(a, q), k
     finally:
         trainer.set_deterministic(False)
 
