@@ -630,8 +630,8 @@ selscan_bwd_kernel(const float *__restrict__ u, const float *__restrict__ delta,
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float dlj = f4get(dv, j), gyj = f4get(gv, j), uj = f4get(uv, j);
-                    // d softplus(x)/dx = sigmoid(x) = 1 - exp(-softplus(x)); 1 when softplus is off
-                    const float sp = softplus ? (1.f - __expf(-dlj)) : 1.f;
+                    // d softplus(x)/dx = sigmoid(x), recovered from softplus(x); 1 when softplus is off
+                    const float sp = softplus ? softplus_grad_from_value(dlj) : 1.f;
                     const bool inr = (t0 + 4 * id.s + j) < L;
                     odd[j] = inr ? (odd[j] + uj * odu[j]) * sp : 0.f;           // (sT + u * sG) * softplus'
                     odu[j] = dlj * odu[j] + Dd * gyj;                           // delta' * sG + D * dy
@@ -1057,8 +1057,8 @@ selscan_bwd_group_kernel(const float *__restrict__ u, const float *__restrict__ 
             float ev[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};                  // this lane's part of dD, d(bias), dW[0..3]
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                // d softplus(x)/dx = sigmoid(x) = 1 - exp(-softplus(x)); 1 when softplus is off
-                const float sp = softplus ? (1.f - __expf(-dl2[e])) : 1.f;
+                // d softplus(x)/dx = sigmoid(x), recovered from softplus(x); 1 when softplus is off
+                const float sp = softplus ? softplus_grad_from_value(dl2[e]) : 1.f;
                 const bool inr = WHOLE || ((tm + 2 * s + e) < L && act);
                 odd2[e] = inr ? (Ts[e] + uu2[e] * Gs[e]) * sp : 0.f;        // (sT + u * sG) * softplus'
                 odu2[e] = dl2[e] * Gs[e] + Dd * gg2[e];                     // delta' * sG + D * dy

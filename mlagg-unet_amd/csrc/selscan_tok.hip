@@ -512,7 +512,7 @@ tok_bwd_group_kernel(const float *__restrict__ xc, const float *__restrict__ xdb
             float ev[2 + RK] = {0.f, 0.f, 0.f, 0.f, 0.f};                  // this lane's part of dD, d(bias), dW[0..2]
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                const float sp = 1.f - __expf(-dl2[e]);                     // d softplus(x)/dx = sigmoid(x) = 1 - exp(-softplus(x))
+                const float sp = softplus_grad_from_value(dl2[e]);          // d softplus(x)/dx = sigmoid(x), recovered from softplus(x)
                 odd2[e] = inr2 ? (Ts[e] + uu2[e] * Gs[e]) * sp : 0.f;       // (sT + u * sG) * softplus'
                 odu2[e] = dl2[e] * Gs[e] + Dd * gg2[e];                     // delta' * sG + D * dy
                 ev[1] += odd2[e];

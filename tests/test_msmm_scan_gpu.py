@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import c_oracle as CO
+from tests._selscan_regime_cases import msmm_oracle, reference_orders as _reference_orders
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -25,19 +25,6 @@ def _inputs(b, HW, seed):
     bias = torch.randn(K * HC, generator=g) - 3.0
     dy = torch.randn(b, L, HC, generator=g)
     return xc, xdbl, Wdt, A, D, bias, dy, L
-
-
-def _reference_orders(HW):
-    """The four scan orders as the reference builds them (M:414-422): per scale x (C, H, W) -> stack([x.flatten(), x.transpose(H, W)
-    .flatten()]) and their flips, scales concatenated per direction.  Returned as token indices (4, L)."""
-    rows, off = [[], [], [], []], 0
-    for H, W in HW:
-        tok = torch.arange(H * W).view(H, W)
-        hw, wh = tok.flatten(), tok.t().contiguous().flatten()
-        for k, t in enumerate((hw, wh, hw.flip(0), wh.flip(0))):
-            rows[k].append(t + off)
-        off += H * W
-    return torch.stack([torch.cat(r) for r in rows])
 
 
 CASES = [
@@ -62,36 +49,12 @@ def test_msmm_scan_matches_oracle(b, HW):
     idx = _reference_orders(HW)                                   # (4, L) int64
     leaves = [t.to(DEV).requires_grad_(True) for t in (xc, xdbl, Wdt, A, D, bias)]
     y = ops.msmm_scan(leaves[0], leaves[1], ops.msmm_scan_index(HW, DEV), *leaves[2:])
-    # the oracle's inputs: scan sequences gathered the way forward_corev0 lays them out
-    xv = xdbl.view(b, L, K, XB)
-    xs = torch.stack([xc[:, idx[k]] for k in range(K)], 1).permute(0, 1, 3, 2).reshape(b, K * HC, L).contiguous()
-    dtr = torch.stack([xv[:, idx[k], k, :R] for k in range(K)], 1).permute(0, 1, 3, 2).contiguous()            # (b, K, R, L)
-    Bs = torch.stack([xv[:, idx[k], k, 4:4 + N] for k in range(K)], 1).permute(0, 1, 3, 2).contiguous()        # (b, K, N, L)
-    Cs = torch.stack([xv[:, idx[k], k, 4 + N:] for k in range(K)], 1).permute(0, 1, 3, 2).contiguous()
-    delta = torch.einsum("bkrl,kdr->bkdl", dtr, Wdt.view(K, HC, R)).reshape(b, K * HC, L).contiguous()
-    npf = lambda t: t.numpy()                                                                                   # noqa: E731
-    y_seq = CO.selscan_fwd(npf(xs), npf(delta), npf(A), npf(Bs), npf(Cs), npf(D), npf(bias), True)              # (b, 384, L)
-    y_ref = np.zeros((b, L, HC))
-    for k in range(K):
-        y_ref[:, idx[k].numpy()] += np.asarray(y_seq, dtype=np.float64).reshape(b, K, HC, L)[:, k].transpose(0, 2, 1)
+    # the oracle's inputs are the scan sequences gathered the way forward_corev0 lays them out; its gradients are folded back
+    y_ref, refs = msmm_oracle(xc, xdbl, Wdt, A, D, bias, dy, idx)
     scale = np.abs(y_ref).max()
     np.testing.assert_allclose(y.detach().cpu().numpy(), y_ref, atol=1e-4 * scale, rtol=1e-4)
     y.backward(dy.to(DEV))
-    dout = torch.stack([dy[:, idx[k]] for k in range(K)], 1).permute(0, 1, 3, 2).reshape(b, K * HC, L).contiguous()
-    du, ddelta, dA, dB, dC, dD, dbias = CO.selscan_bwd(npf(xs), npf(delta), npf(A), npf(Bs), npf(Cs), npf(D), npf(bias), npf(dout), True)
-    dd = np.asarray(ddelta, dtype=np.float64).reshape(b, K, HC, L)
-    ddtr = np.einsum("bkdl,kdr->bkrl", dd, Wdt.double().numpy().reshape(K, HC, R))
-    dW = np.einsum("bkdl,bkrl->kdr", dd, dtr.double().numpy()).reshape(K * HC, R)
-    dxc = np.zeros((b, L, HC))
-    dxd = np.zeros((b, L, K, XB))
-    du4 = np.asarray(du, dtype=np.float64).reshape(b, K, HC, L)
-    for k in range(K):
-        ik = idx[k].numpy()
-        dxc[:, ik] += du4[:, k].transpose(0, 2, 1)
-        dxd[:, ik, k, :R] = ddtr[:, k].transpose(0, 2, 1)
-        dxd[:, ik, k, 4:4 + N] = np.asarray(dB, dtype=np.float64)[:, k].transpose(0, 2, 1)
-        dxd[:, ik, k, 4 + N:] = np.asarray(dC, dtype=np.float64)[:, k].transpose(0, 2, 1)
-    for name, t, r in zip(("dxc", "dxdbl", "dWdt", "dA", "dD", "dbias"), leaves, (dxc, dxd.reshape(b, L, K * XB), dW, dA, dD, dbias)):
+    for name, t, r in zip(("dxc", "dxdbl", "dWdt", "dA", "dD", "dbias"), leaves, refs):
         got = t.grad.cpu().numpy()
         s = max(np.abs(r).max(), 1e-6)
         np.testing.assert_allclose(got, r, atol=3e-4 * s, rtol=1e-3, err_msg=name)

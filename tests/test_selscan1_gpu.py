@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import c_oracle as CO
+from tests._selscan_regime_cases import selscan1_oracle as _oracle
 
 gpu = pytest.mark.gpu
 
@@ -25,32 +25,6 @@ def _case(B, L, C, K, R, seed=0):
     bias = torch.randn(K * C, generator=g) * 1.5 - 3.0
     dout = torch.randn(B, L, C, generator=g)
     return tok, idx, dtr, Bs, Cs, Wdt, A, D, bias, dout
-
-
-def _oracle(tok, idx, dtr, Bs, Cs, Wdt, A, D, bias, dout):
-    """Explicit scan-order tensors -> C oracle -> gradients folded back to the kernel's operands (float64 host algebra)."""
-    B, L, C = tok.shape
-    K, R = idx.shape[0], dtr.shape[2]
-    ix = idx.long()
-    xs = torch.stack([tok[:, ix[k], :].transpose(1, 2) for k in range(K)], 1).reshape(B, K * C, L)       # (B, K*C, L)
-    delta = torch.einsum("bkrl,kcr->bkcl", dtr.double(), Wdt.view(K, C, R).double()).reshape(B, K * C, L).float()
-    A2, B4, C4 = A.view(-1, 1), Bs.view(B, K, 1, L), Cs.view(B, K, 1, L)
-    n = lambda t: t.contiguous().numpy()
-    out = torch.from_numpy(CO.selscan_fwd(n(xs), n(delta), n(A2), n(B4), n(C4), n(D), n(bias), True)).view(B, K, C, L)
-    y = torch.zeros(B, L, C, dtype=torch.float64)
-    for k in range(K):
-        y[:, ix[k], :] += out[:, k].transpose(1, 2).double()
-    douts = torch.stack([dout[:, ix[k], :].transpose(1, 2) for k in range(K)], 1).reshape(B, K * C, L)
-    du, ddelta, dA, dB, dC, dD, dbias = (torch.from_numpy(v) for v in
-                                         CO.selscan_bwd(n(xs), n(delta), n(A2), n(B4), n(C4), n(D), n(bias), n(douts), True))
-    dtok = torch.zeros(B, L, C, dtype=torch.float64)
-    du = du.view(B, K, C, L)
-    for k in range(K):
-        dtok[:, ix[k], :] += du[:, k].transpose(1, 2).double()
-    dd = ddelta.view(B, K, C, L).double()
-    ddtr = torch.einsum("bkcl,kcr->bkrl", dd, Wdt.view(K, C, R).double())
-    dW = torch.einsum("bkcl,bkrl->kcr", dd, dtr.double()).reshape(K * C, R)
-    return y, dict(tok=dtok, dtr=ddtr, Bs=dB.view(B, K, L), Cs=dC.view(B, K, L), Wdt=dW, A=dA.view(-1), D=dD, bias=dbias)
 
 
 CASES = [
