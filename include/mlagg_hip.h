@@ -915,6 +915,30 @@ int mlagg_cells_overlap(const int *g, const int *p, int h, int w, int n_true, in
 int mlagg_cells_match(const int *overlap, const int *area_t, const int *area_p, int n_true, int n_pred, const double *thresholds,
                       int n_thresholds, double *iou, int *degrees, int *stats, int *edges, int edge_cap, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K28: ensembling and model selection (reference ensembling/ensemble.py and evaluation/evaluate_predictions.py).
+ *
+ * mlagg_ensemble_mean: average_probabilities (ensemble.py:17-29) and the argmax that merge_files (:32-46) takes of it, in one pass.
+ *   table (DEVICE, M x 2 int64): per member the device address of its contiguous (K, N) array and its element size in bytes, 4 (fp32)
+ *   or 2 (fp16); the address is a multiple of the element size.  M >= 1 (unbounded), 2 <= K <= MLAGG_ENSEMBLE_MAX_CLASSES, N >= 1.
+ *   Per voxel and class: acc = float(m_0); acc = acc + float(m_i), i = 1 .. M - 1 in table order; acc = acc / float(M) (IEEE fp32
+ *   division): numpy's arithmetic to the bit.  labels (N uint8) = the first class whose mean is the maximum; a NaN counts as a maximum
+ *   and the first NaN wins (numpy's argmax).  mean (optional, NULL: not written; (K, N) fp32) = the means.  No atomics, no LDS.
+ *
+ * mlagg_label_confusion: the counting of compute_metrics (evaluate_predictions.py:77-120).  ref, pred (N uint8); table (DEVICE, 256
+ *   uint8) maps a label value to a bin 0 .. L, where L (<= MLAGG_CONFUSION_MAX_LABELS) stands for "any other value" (entries above L
+ *   count as L).  ignore (-1: none): voxels whose REFERENCE value equals it are dropped (ignore_mask = seg_ref == ignore_label).
+ *   counts ((L + 1) x (L + 1) int64, zeroed here) = voxels per (reference bin, prediction bin).  tp / fp / fn / tn of a label or a
+ *   region R are sums over it: tp = sum cm[a in R, b in R], fn = sum cm[a in R, b not in R], fp = sum cm[a not in R, b in R], tn =
+ *   the rest.  int32 counters in LDS per workgroup, flushed with 64-bit integer atomic adds: independent of the schedule.
+ * Inference only: no graph capture is needed, though neither entry allocates or synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_ENSEMBLE_MAX_CLASSES 256
+#define MLAGG_CONFUSION_MAX_LABELS 63
+int mlagg_ensemble_mean(const long long *table, int M, int K, long long N, unsigned char *labels, float *mean, void *stream);
+int mlagg_label_confusion(const unsigned char *ref, const unsigned char *pred, long long N, const unsigned char *table, int L,
+                          int ignore, long long *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

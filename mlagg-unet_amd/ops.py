@@ -3237,3 +3237,55 @@ def cells_edges(overlap, area_t, area_p, threshold, count):
     _launch("mlagg_cells_match", _ptr(overlap), _ptr(area_t), _ptr(area_p), rows - 1, pitch - 1, th.ctypes.data, 1, None, None,
             _ptr(stats), _ptr(edges), count)
     return edges
+
+
+# ------------------------------------------------------------------------------------------------
+# K28: ensembling and model selection (csrc/ensemble.hip).  ensembling.py and evaluation.py compose these.  Inference only.
+# ------------------------------------------------------------------------------------------------
+ENSEMBLE_MAX_CLASSES = _C["MLAGG_ENSEMBLE_MAX_CLASSES"]
+CONFUSION_MAX_LABELS = _C["MLAGG_CONFUSION_MAX_LABELS"]
+
+
+def ensemble_mean(members, want_mean=False):
+    """members: M >= 1 contiguous fp32 or fp16 device tensors of one shape (K, ...), 2 <= K <= ENSEMBLE_MAX_CLASSES (views into larger
+    buffers are fine) -> (labels (...) uint8: the first class whose mean is the maximum, a NaN counting as one; mean (K, ...) fp32 or
+    None).  The mean is ((m_0 + m_1) + ...) / M in fp32, numpy's arithmetic to the bit.  Without want_mean no (K, N) buffer exists."""
+    members = list(members)
+    if not members:
+        raise RuntimeError("ensemble_mean: at least one member must be given")
+    first = members[0]
+    for i, m in enumerate(members):
+        if not (isinstance(m, torch.Tensor) and m.dtype in (torch.float32, torch.float16)):
+            raise RuntimeError(f"members[{i}]: expected an fp32 or fp16 tensor, got {getattr(m, 'dtype', type(m))}")
+        _expect(m, f"members[{i}]", m.dtype, like=first)
+        if m.dim() < 2 or tuple(m.shape) != tuple(first.shape):
+            raise RuntimeError(f"members[{i}]: shape {tuple(m.shape)}, expected (K, ...) = {tuple(first.shape)} as members[0]")
+    K = int(first.shape[0])
+    N = first.numel() // max(K, 1)
+    if K < 2 or K > ENSEMBLE_MAX_CLASSES:
+        raise RuntimeError(f"ensemble_mean: {K} classes, 2 to {ENSEMBLE_MAX_CLASSES} are supported (labels are uint8)")
+    if N < 1:
+        raise RuntimeError(f"ensemble_mean: empty members {tuple(first.shape)}")
+    table = torch.tensor([[m.data_ptr(), m.element_size()] for m in members], dtype=torch.int64).to(first.device)
+    labels = torch.empty(first.shape[1:], dtype=torch.uint8, device=first.device)
+    mean = torch.empty(first.shape, dtype=torch.float32, device=first.device) if want_mean else None
+    _launch("mlagg_ensemble_mean", _ptr(table), len(members), K, N, _ptr(labels), _ptr(mean))
+    return labels, mean
+
+
+def label_confusion(reference, prediction, table, n_labels, ignore_label=None):
+    """reference, prediction: contiguous uint8 device tensors of one shape; table: 256 uint8 on the device, label value -> bin 0 ..
+    n_labels (n_labels = "any other value", at most CONFUSION_MAX_LABELS) -> (n_labels + 1, n_labels + 1) int64 device tensor of voxel
+    counts, row = reference bin, column = prediction bin.  Voxels whose reference value is ignore_label are left out."""
+    _expect(reference, "reference", torch.uint8)
+    _expect(prediction, "prediction", torch.uint8, shape=reference.shape, like=reference)
+    _expect(table, "table", torch.uint8, shape=(256,), like=reference)
+    L = int(n_labels)
+    if L < 0 or L > CONFUSION_MAX_LABELS:
+        raise RuntimeError(f"label_confusion: {L} labels, at most {CONFUSION_MAX_LABELS} are supported")
+    if reference.numel() < 1:
+        raise RuntimeError(f"label_confusion: empty volume {tuple(reference.shape)}")
+    ignore = -1 if ignore_label is None or not 0 <= int(ignore_label) <= 255 else int(ignore_label)
+    counts = torch.empty((L + 1, L + 1), dtype=torch.int64, device=reference.device)
+    _launch("mlagg_label_confusion", _ptr(reference), _ptr(prediction), reference.numel(), _ptr(table), L, ignore, _ptr(counts))
+    return counts
