@@ -712,6 +712,14 @@ int mlagg_resample_linear(const float *in, int C, int X, int Y, int Z, long long
 int mlagg_export_segmentation(const float *logits, int K, int X, int Y, int Z, long long sc, long long sx, long long sy, long long sz,
                               const int *tap_idx, const double *tap_w, int Xc, int Yc, int Zc, const int *box_lo, const int *shape,
                               const int *perm, unsigned char *labels, float *probs, void *stream);
+/* export_segmentation_regions: the same resampling, paste and transpose for the K <= 32 sigmoid heads of a region-based label manager
+ * (label_handling.py:46-47, 166-173): per voxel the fp32 sigmoid of every resampled logit; the label starts at 0 and takes
+ * regions_class_order[i] where sigmoid_i > 0.5, for i = 0 .. K-1 in order (the last match wins; a logit of exactly 0 does not fire).
+ * regions_class_order is a HOST array of K values in 0 .. 255; probs (optional) are the sigmoids, 0 outside the box. */
+int mlagg_export_segmentation_regions(const float *logits, int K, int X, int Y, int Z, long long sc, long long sx, long long sy,
+                                      long long sz, const int *tap_idx, const double *tap_w, int Xc, int Yc, int Zc, const int *box_lo,
+                                      const int *shape, const int *perm, const int *regions_class_order, unsigned char *labels,
+                                      float *probs, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * K22: case preprocessing on the device (reference nnunetv2/preprocessing/preprocessors/default_preprocessor.py:38-124 for a
@@ -925,6 +933,11 @@ int mlagg_cells_match(const int *overlap, const int *area_t, const int *area_p, 
  *   division): numpy's arithmetic to the bit.  labels (N uint8) = the first class whose mean is the maximum; a NaN counts as a maximum
  *   and the first NaN wins (numpy's argmax).  mean (optional, NULL: not written; (K, N) fp32) = the means.  No atomics, no LDS.
  *
+ * mlagg_ensemble_mean_regions: the same mean, in the same order, of the sigmoid probabilities of a region-based label manager; the
+ *   label is what convert_probabilities_to_segmentation paints from it (label_handling.py:166-173): 0, then order[k] where mean_k > 0.5
+ *   for k = 0 .. K-1 in order (the last match wins).  table (DEVICE, (2 M + K) int64): the M member rows, then the K labels of
+ *   regions_class_order (0 .. 255).  1 <= K <= MLAGG_ENSEMBLE_MAX_CLASSES.
+ *
  * mlagg_label_confusion: the counting of compute_metrics (evaluate_predictions.py:77-120).  ref, pred (N uint8); table (DEVICE, 256
  *   uint8) maps a label value to a bin 0 .. L, where L (<= MLAGG_CONFUSION_MAX_LABELS) stands for "any other value" (entries above L
  *   count as L).  ignore (-1: none): voxels whose REFERENCE value equals it are dropped (ignore_mask = seg_ref == ignore_label).
@@ -936,8 +949,37 @@ int mlagg_cells_match(const int *overlap, const int *area_t, const int *area_p, 
 #define MLAGG_ENSEMBLE_MAX_CLASSES 256
 #define MLAGG_CONFUSION_MAX_LABELS 63
 int mlagg_ensemble_mean(const long long *table, int M, int K, long long N, unsigned char *labels, float *mean, void *stream);
+int mlagg_ensemble_mean_regions(const long long *table, int M, int K, long long N, unsigned char *labels, float *mean, void *stream);
 int mlagg_label_confusion(const unsigned char *ref, const unsigned char *pred, long long N, const unsigned char *table, int L,
                           int ignore, long long *counts, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K29: Dice + binary cross-entropy statistics and gradient of one deep-supervision level of a region-based dataset (sigmoid heads).
+ * Replaces sigmoid, the masked products and spatial sums, BCEWithLogitsLoss and all their backward kernels of DC_and_BCE_loss
+ * (loss/compound_losses.py:60-100 with MemoryEfficientSoftDiceLoss(do_bg=True), loss/dice.py:73-117), as the trainer builds it for
+ * label managers with regions (nnUNetTrainer.py:330-336).
+ * logits (B, R, HW) fp32, 1 <= R <= mlagg_dice_bce_max_regions() (otherwise MLAGG_E_UNSUPPORTED).  The target has two forms:
+ *   member != NULL  target (B, HW) float labels; member (DEVICE, 256 uint32): bit r of member[v] says that label v belongs to region r
+ *                   (np.isin: a label outside 0 .. 255 or in no region has no bits).  ignore_label >= 0: pixels carrying that label
+ *                   have the mask m = 0; -1: none (every pixel counts, also one with a negative label, which is in no region).  What ConvertSegmentationToRegionsTransform would write is never materialised.
+ *   member == NULL  target (B, R, HW) float region planes, or (B, R + 1, HW) when ignore_label >= 0: the last plane is then the
+ *                   ignore indicator and m = (1 - t_last) != 0 (compound_losses.py:85-89).
+ * stats: stats_ip[b][0][r] = sum_p m s_r t_r, stats_ip[b][1][r] = sum_p m s_r, stats_g[b][r] = sum_p m t_r with s = sigmoid(z);
+ * sums[0] = sum_{b,r,p} m (softplus(z_r) - z_r t_r) (BCEWithLogitsLoss, unreduced), sums[1] = sum_{b,p} m (the denominator of
+ * compound_losses.py:96, without a factor R).  Every value is finite for any finite logit.
+ * grad: dlogits = m [ s (1 - s) (g_ip[b][0][r] t_r + g_ip[b][1][r]) + g_bce[0] (s - t_r) ] for upstream gradients g_ip (B, 2, R) of
+ * stats_ip and g_bce[0] of sums[0] (device scalars: no host synchronisation).
+ */
+int mlagg_dice_bce_max_regions(void);
+/*
+ * stats OVERWRITES its outputs: per-workgroup partial rows in `workspace` (mlagg_dice_bce_stats_workspace_floats floats) are summed in
+ * a fixed order, no float atomics -- the value of the loss is bit-reproducible from run to run.
+ * ------------------------------------------------------------------------------------------ */
+size_t mlagg_dice_bce_stats_workspace_floats(int B, int R, long HW);
+int mlagg_dice_bce_stats(const float *logits, const float *target, const unsigned int *member, float *stats_ip, float *stats_g,
+                         float *sums, float *workspace, int B, int R, long HW, int ignore_label, void *stream);
+int mlagg_dice_bce_grad(const float *logits, const float *target, const unsigned int *member, const float *g_ip, const float *g_bce,
+                        float *dlogits, int B, int R, long HW, int ignore_label, void *stream);
 
 #ifdef __cplusplus
 }

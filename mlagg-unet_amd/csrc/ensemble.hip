@@ -13,6 +13,11 @@
 //                              is aligned to that and 4 voxels remain, with scalar loads otherwise; the test is made per member and per
 //                              plane (N % 4 != 0 misaligns every other plane) and is the same in every lane.  Two planes are in flight
 //                              per lane.  The mean is written only when its buffer is given.
+//   mlagg_ensemble_mean_regions
+//     ens_mean_kernel<true>    the same mean, in the same order, for the sigmoid heads of a region-based label manager; the label is
+//                              painted from it as convert_probabilities_to_segmentation does (label_handling.py:166-173): 0, then
+//                              order[k] wherever mean_k > 0.5 for k = 0 .. K-1, the last match winning (a NaN mean does not fire).  The
+//                              K entries of regions_class_order follow the member table in device memory.
 //   mlagg_label_confusion
 //     label_confusion_kernel   the (L + 1) x (L + 1) matrix of (reference bin, prediction bin) voxel counts, from which tp / fp / fn / tn
 //                              of every label and region follow on the host (compute_tp_fp_fn_tn :77-86 with ignore_mask = seg_ref ==
@@ -66,8 +71,10 @@ struct Best {
     int index[ENS_RUN];
 };
 
-// the sum of one plane -> its mean, stored if asked, and the running argmax
-__device__ __forceinline__ void finish_plane(f32x4 acc, float fm, int k, long long o, int n, float *__restrict__ mean, Best &best)
+// the sum of one plane -> its mean, stored if asked, and the running argmax (REGIONS: the label `paint` wherever the mean is above 0.5)
+template <bool REGIONS>
+__device__ __forceinline__ void finish_plane(f32x4 acc, float fm, int k, long long o, int n, float *__restrict__ mean, Best &best,
+                                             int paint)
 {
 #pragma unroll
     for (int j = 0; j < ENS_RUN; ++j) acc[j] = acc[j] / fm;
@@ -79,6 +86,11 @@ __device__ __forceinline__ void finish_plane(f32x4 acc, float fm, int k, long lo
             for (int j = 0; j < ENS_RUN; ++j)
                 if (j < n) p[j] = acc[j];
         }
+    }
+    if constexpr (REGIONS) {
+#pragma unroll
+        for (int j = 0; j < ENS_RUN; ++j) best.index[j] = acc[j] > 0.5f ? paint : best.index[j];
+        return;
     }
     if (k == 0) {
         best.value = acc;
@@ -94,10 +106,12 @@ __device__ __forceinline__ void finish_plane(f32x4 acc, float fm, int k, long lo
     }
 }
 
+template <bool REGIONS>
 __global__ void __launch_bounds__(ENS_BLOCK) ens_mean_kernel(const long long *__restrict__ table, int M, int K, long long N,
                                                              uint8_t *__restrict__ labels, float *__restrict__ mean)
 {
     const float fm = (float)M;
+    const long long *order = table + 2 * (long long)M;          // REGIONS: regions_class_order behind the member table
     const long long runs = (N + ENS_RUN - 1) / ENS_RUN;
     for (long long r = (long long)blockIdx.x * ENS_BLOCK + threadIdx.x; r < runs; r += (long long)gridDim.x * ENS_BLOCK) {
         const long long v0 = r * ENS_RUN;
@@ -117,14 +131,14 @@ __global__ void __launch_bounds__(ENS_BLOCK) ens_mean_kernel(const long long *__
                 a = a + x;
                 b = b + y;
             }
-            finish_plane(a, fm, k, o0, n, mean, best);
-            finish_plane(b, fm, k + 1, o1, n, mean, best);
+            finish_plane<REGIONS>(a, fm, k, o0, n, mean, best, REGIONS ? (int)order[k] : 0);
+            finish_plane<REGIONS>(b, fm, k + 1, o1, n, mean, best, REGIONS ? (int)order[k + 1] : 0);
         }
         if (k < K) {
             const long long o0 = (long long)k * N + v0;
             f32x4 a = load_run(table[0], (int)table[1], o0, n);
             for (int m = 1; m < M; ++m) a = a + load_run(table[2 * m], (int)table[2 * m + 1], o0, n);
-            finish_plane(a, fm, k, o0, n, mean, best);
+            finish_plane<REGIONS>(a, fm, k, o0, n, mean, best, REGIONS ? (int)order[k] : 0);
         }
         uint8_t *out = labels + v0;
         if (n == ENS_RUN && !(reinterpret_cast<uintptr_t>(out) & 3))
@@ -189,11 +203,10 @@ __global__ void __launch_bounds__(LC_BLOCK) label_confusion_kernel(const uint8_t
         if (cnt[e]) atomicAdd(&counts[e], (unsigned long long)cnt[e]);
 }
 
-}  // namespace
-
-extern "C" int mlagg_ensemble_mean(const long long *table, int M, int K, long long N, unsigned char *labels, float *mean, void *stream)
+template <bool REGIONS>
+int ensemble_any(const long long *table, int M, int K, long long N, unsigned char *labels, float *mean, void *stream)
 {
-    if (M < 1 || K < 2 || K > MLAGG_ENSEMBLE_MAX_CLASSES || N < 1) return MLAGG_E_UNSUPPORTED;
+    if (M < 1 || K < (REGIONS ? 1 : 2) || K > MLAGG_ENSEMBLE_MAX_CLASSES || N < 1) return MLAGG_E_UNSUPPORTED;
     if (N > LLONG_MAX / ((long long)K * 4)) return MLAGG_E_UNSUPPORTED;
     if (!table || !labels) return MLAGG_E_NULLPTR;
     if (reinterpret_cast<uintptr_t>(table) & 7 || reinterpret_cast<uintptr_t>(mean) & 3) return MLAGG_E_UNSUPPORTED;
@@ -201,9 +214,22 @@ extern "C" int mlagg_ensemble_mean(const long long *table, int M, int K, long lo
     const long long runs = (N + ENS_RUN - 1) / ENS_RUN;
     const long long blocks = (runs + ENS_BLOCK - 1) / ENS_BLOCK;
     MLAGG_TIMED(K_ENS_MEAN, st);
-    hipLaunchKernelGGL(ens_mean_kernel, dim3((unsigned)(blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS)), dim3(ENS_BLOCK), 0, st, table, M, K, N,
-                       labels, mean);
+    hipLaunchKernelGGL(ens_mean_kernel<REGIONS>, dim3((unsigned)(blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS)), dim3(ENS_BLOCK), 0, st, table,
+                       M, K, N, labels, mean);
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int mlagg_ensemble_mean(const long long *table, int M, int K, long long N, unsigned char *labels, float *mean, void *stream)
+{
+    return ensemble_any<false>(table, M, K, N, labels, mean, stream);
+}
+
+extern "C" int mlagg_ensemble_mean_regions(const long long *table, int M, int K, long long N, unsigned char *labels, float *mean,
+                                           void *stream)
+{
+    return ensemble_any<true>(table, M, K, N, labels, mean, stream);
 }
 
 extern "C" int mlagg_label_confusion(const unsigned char *ref, const unsigned char *pred, long long N, const unsigned char *table, int L,

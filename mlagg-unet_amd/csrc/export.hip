@@ -11,7 +11,10 @@
 //   and transposes them by transpose_backward.
 //   resample_linear_kernel   the resampling alone: (C, X, Y, Z) -> (C, X', Y', Z') fp32 (export.resample_logits_to_shape, and the
 //                            first step of the export for more than 32 classes);
-//   export_kernel<KB>        everything at once for K <= KB classes, without materialising the resampled logits.
+//   export_kernel<KB>        everything at once for K <= KB classes, without materialising the resampled logits.  REGIONS: the
+//                            heads of a region-based label manager -- fp32 sigmoid per head instead of the softmax, and the label
+//                            painted in regions_class_order (label 0, then order[i] wherever sigmoid_i > 0.5 for i = 0 .. K-1: the
+//                            last match wins, label_handling.py:166-173) instead of the argmax.
 //
 // The coordinates are not computed here: the host builds one table per output axis in float64 with the reference's expressions
 // (export._axis_taps) -- two source indices and their two weights -- and the kernels only gather and blend.  An order-0 or unchanged
@@ -115,9 +118,13 @@ struct Geometry {
 
 __device__ __forceinline__ int pick(int q0, int q1, int q2, int i) { return i == 0 ? q0 : (i == 1 ? q1 : q2); }
 
+struct Order {
+    uint8_t label[32];                 // regions_class_order: the label head i paints (REGIONS only)
+};
+
 // flat output voxel f = 4 * lane + j of the transposed, uncropped volume Q; KB >= K logits live in registers
-template <int KB>
-__global__ void __launch_bounds__(EX_BLOCK) export_kernel(Src s, Taps t, Geometry g, int K, uint8_t *__restrict__ labels,
+template <int KB, bool REGIONS>
+__global__ void __launch_bounds__(EX_BLOCK) export_kernel(Src s, Taps t, Geometry g, Order order, int K, uint8_t *__restrict__ labels,
                                                           float *__restrict__ probs, long long N)
 {
 #pragma clang fp contract(off)
@@ -136,39 +143,54 @@ __global__ void __launch_bounds__(EX_BLOCK) export_kernel(Src s, Taps t, Geometr
         if ((unsigned)ox < (unsigned)g.ext[0] && (unsigned)oy < (unsigned)g.ext[1] && (unsigned)oz < (unsigned)g.ext[2]) {
             const int2 ix = tap_idx(t, ox), iy = tap_idx(t, t.yoff + oy), iz = tap_idx(t, t.zoff + oz);
             const double2 wx = tap_w(t, ox), wy = tap_w(t, t.yoff + oy), wz = tap_w(t, t.zoff + oz);
-            float l[KB];
-            float m = -INFINITY;
+            if constexpr (REGIONS) {
+                // torch.sigmoid per head in fp32 (label_handling.py:46-47, 128-144); a logit of exactly 0 gives 0.5, which does not fire
+                uint32_t lab = 0;
 #pragma unroll
-            for (int k = 0; k < KB; ++k) {
-                if (k < K) {
-                    l[k] = interp(s.p + (long long)k * s.sc, s.sx, s.sy, s.sz, ix, iy, iz, wx, wy, wz);
-                    m = fmaxf(m, l[k]);
-                }
-            }
-            // softmax over the classes in fp32 (torch.softmax(x, 0) of label_handling.py:128-144), then the first maximum of the
-            // probabilities (numpy's argmax(0), :172)
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < KB; ++k) {
-                if (k < K) {
-                    l[k] = expf(l[k] - m);
-                    sum = sum + l[k];
-                }
-            }
-            float best = 0.f;
-            int arg = 0;
-#pragma unroll
-            for (int k = 0; k < KB; ++k) {
-                if (k < K) {
-                    l[k] = l[k] / sum;
-                    if (k == 0 || l[k] > best) {
-                        best = l[k];
-                        arg = k;
+                for (int k = 0; k < KB; ++k) {
+                    if (k < K) {
+                        const float z = interp(s.p + (long long)k * s.sc, s.sx, s.sy, s.sz, ix, iy, iz, wx, wy, wz);
+                        const float p = 1.f / (1.f + expf(-z));
+                        lab = p > 0.5f ? (uint32_t)order.label[k] : lab;
+                        if (probs) probs[(long long)k * N + f] = p;
                     }
-                    if (probs) probs[(long long)k * N + f] = l[k];
                 }
+                packed |= lab << (8 * j);
+            } else {
+                float l[KB];
+                float m = -INFINITY;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    if (k < K) {
+                        l[k] = interp(s.p + (long long)k * s.sc, s.sx, s.sy, s.sz, ix, iy, iz, wx, wy, wz);
+                        m = fmaxf(m, l[k]);
+                    }
+                }
+                // softmax over the classes in fp32 (torch.softmax(x, 0) of label_handling.py:128-144), then the first maximum of the
+                // probabilities (numpy's argmax(0), :172)
+                float sum = 0.f;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    if (k < K) {
+                        l[k] = expf(l[k] - m);
+                        sum = sum + l[k];
+                    }
+                }
+                float best = 0.f;
+                int arg = 0;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    if (k < K) {
+                        l[k] = l[k] / sum;
+                        if (k == 0 || l[k] > best) {
+                            best = l[k];
+                            arg = k;
+                        }
+                        if (probs) probs[(long long)k * N + f] = l[k];
+                    }
+                }
+                packed |= (uint32_t)arg << (8 * j);
             }
-            packed |= (uint32_t)arg << (8 * j);
         } else if (probs) {
             for (int k = 0; k < K; ++k) probs[(long long)k * N + f] = 0.f;          // revert_cropping: zeros in every channel
         }
@@ -187,11 +209,11 @@ __global__ void __launch_bounds__(EX_BLOCK) export_kernel(Src s, Taps t, Geometr
     }
 }
 
-template <int KB>
-void launch_export(dim3 grid, hipStream_t st, const Src &s, const Taps &t, const Geometry &g, int K, uint8_t *labels, float *probs,
-                   long long N)
+template <int KB, bool REGIONS>
+void launch_export(dim3 grid, hipStream_t st, const Src &s, const Taps &t, const Geometry &g, const Order &order, int K, uint8_t *labels,
+                   float *probs, long long N)
 {
-    hipLaunchKernelGGL(export_kernel<KB>, grid, dim3(EX_BLOCK), 0, st, s, t, g, K, labels, probs, N);
+    hipLaunchKernelGGL((export_kernel<KB, REGIONS>), grid, dim3(EX_BLOCK), 0, st, s, t, g, order, K, labels, probs, N);
 }
 
 int check_source(const float *in, int C, int X, int Y, int Z, long long sc, long long sx, long long sy, long long sz, const int *idx,
@@ -222,10 +244,12 @@ extern "C" int mlagg_resample_linear(const float *in, int C, int X, int Y, int Z
     return (int)hipGetLastError();
 }
 
-extern "C" int mlagg_export_segmentation(const float *logits, int K, int X, int Y, int Z, long long sc, long long sx, long long sy,
-                                         long long sz, const int *tap_idx, const double *tap_w, int Xc, int Yc, int Zc,
-                                         const int *box_lo, const int *shape, const int *perm, unsigned char *labels, float *probs,
-                                         void *stream)
+namespace {
+
+// regions_class_order == NULL: softmax + argmax; else K labels in 0..255, sigmoid + painting
+int export_any(const float *logits, int K, int X, int Y, int Z, long long sc, long long sx, long long sy, long long sz,
+               const int *tap_idx, const double *tap_w, int Xc, int Yc, int Zc, const int *box_lo, const int *shape, const int *perm,
+               const int *regions_class_order, unsigned char *labels, float *probs, void *stream)
 {
     if (int rc = check_source(logits, K, X, Y, Z, sc, sx, sy, sz, tap_idx, tap_w)) return rc;
     if (!box_lo || !shape || !perm || !labels) return MLAGG_E_NULLPTR;
@@ -253,9 +277,41 @@ extern "C" int mlagg_export_segmentation(const float *logits, int K, int X, int 
     const Taps t{tap_idx, tap_w, Xc, Xc + Yc};
     const dim3 grid((unsigned)blocks);
     uint8_t *lab = reinterpret_cast<uint8_t *>(labels);
-    if (K <= 4) launch_export<4>(grid, st, s, t, g, K, lab, probs, N);
-    else if (K <= 8) launch_export<8>(grid, st, s, t, g, K, lab, probs, N);
-    else if (K <= 16) launch_export<16>(grid, st, s, t, g, K, lab, probs, N);
-    else launch_export<32>(grid, st, s, t, g, K, lab, probs, N);
+    Order order{};
+    if (regions_class_order) {
+        for (int k = 0; k < K; ++k) {
+            if (regions_class_order[k] < 0 || regions_class_order[k] > 255) return MLAGG_E_UNSUPPORTED;
+            order.label[k] = (uint8_t)regions_class_order[k];
+        }
+        if (K <= 4) launch_export<4, true>(grid, st, s, t, g, order, K, lab, probs, N);
+        else if (K <= 8) launch_export<8, true>(grid, st, s, t, g, order, K, lab, probs, N);
+        else if (K <= 16) launch_export<16, true>(grid, st, s, t, g, order, K, lab, probs, N);
+        else launch_export<32, true>(grid, st, s, t, g, order, K, lab, probs, N);
+    } else {
+        if (K <= 4) launch_export<4, false>(grid, st, s, t, g, order, K, lab, probs, N);
+        else if (K <= 8) launch_export<8, false>(grid, st, s, t, g, order, K, lab, probs, N);
+        else if (K <= 16) launch_export<16, false>(grid, st, s, t, g, order, K, lab, probs, N);
+        else launch_export<32, false>(grid, st, s, t, g, order, K, lab, probs, N);
+    }
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int mlagg_export_segmentation(const float *logits, int K, int X, int Y, int Z, long long sc, long long sx, long long sy,
+                                         long long sz, const int *tap_idx, const double *tap_w, int Xc, int Yc, int Zc,
+                                         const int *box_lo, const int *shape, const int *perm, unsigned char *labels, float *probs,
+                                         void *stream)
+{
+    return export_any(logits, K, X, Y, Z, sc, sx, sy, sz, tap_idx, tap_w, Xc, Yc, Zc, box_lo, shape, perm, nullptr, labels, probs, stream);
+}
+
+extern "C" int mlagg_export_segmentation_regions(const float *logits, int K, int X, int Y, int Z, long long sc, long long sx, long long sy,
+                                                 long long sz, const int *tap_idx, const double *tap_w, int Xc, int Yc, int Zc,
+                                                 const int *box_lo, const int *shape, const int *perm, const int *regions_class_order,
+                                                 unsigned char *labels, float *probs, void *stream)
+{
+    if (!regions_class_order) return MLAGG_E_NULLPTR;
+    return export_any(logits, K, X, Y, Z, sc, sx, sy, sz, tap_idx, tap_w, Xc, Yc, Zc, box_lo, shape, perm, regions_class_order, labels,
+                      probs, stream);
 }

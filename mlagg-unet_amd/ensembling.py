@@ -18,7 +18,10 @@ Two deliberate deviations from the reference:
     wins (numpy's argmax; a NaN counts as a maximum).
   - With save_probabilities the .pkl holds the first member's properties, as every other .pkl of the pipeline does; the reference
     pickles the probabilities into it (:46).
-Region-based label managers raise NotImplementedError, as in export.py.
+Region-based label managers (sigmoid probabilities): the mean is the same and the label is painted from it in regions_class_order
+(label_handling.py:166-173: 0, then regions_class_order[k] wherever mean_k > 0.5, the last match winning), which is what the reference
+computes with its second nonlinearity left out -- there merge_files applies the sigmoid again to the averaged probabilities, so that
+every head fires wherever its mean is positive.
 """
 import json
 import os
@@ -29,6 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .export import region_order_of
 
 MAX_CLASSES = ops.ENSEMBLE_MAX_CLASSES
 
@@ -44,9 +48,9 @@ def _load(member):
     return member
 
 
-def _members(members):
+def _members(members, min_classes=2):
     """The members as a list of arrays / tensors that all live in one place (files join the others: the device if any member is a
-    device tensor), checked for a common shape (K, ...) with 2 <= K <= 256 and a floating dtype."""
+    device tensor), checked for a common shape (K, ...) with 2 <= K <= 256 (regions: 1 <= K) and a floating dtype."""
     members = [_load(m) for m in members]
     if not members:
         raise RuntimeError("At least one member must be given")
@@ -59,8 +63,8 @@ def _members(members):
             raise RuntimeError(f"members[{i}] has shape {tuple(m.shape)}, members[0] {tuple(members[0].shape)}")
         if m.ndim < 2:
             raise RuntimeError(f"members[{i}]: expected probabilities of shape (K, ...), got {tuple(m.shape)}")
-        if not 2 <= m.shape[0] <= MAX_CLASSES:
-            raise RuntimeError(f"members[{i}]: {m.shape[0]} classes, 2 to {MAX_CLASSES} are supported (labels are uint8)")
+        if not min_classes <= m.shape[0] <= MAX_CLASSES:
+            raise RuntimeError(f"members[{i}]: {m.shape[0]} classes, {min_classes} to {MAX_CLASSES} are supported (labels are uint8)")
         if device is not None:
             if not isinstance(m, torch.Tensor):
                 m = torch.from_numpy(np.ascontiguousarray(m))
@@ -96,16 +100,28 @@ def _wrap(members_in, x):
     return x
 
 
-def ensemble_probabilities(members, return_probabilities=False):
+def _paint_regions(mean, regions_class_order):
+    """label_handling.py:166-173 on the mean: 0, then regions_class_order[k] wherever mean[k] > 0.5, in order."""
+    order = [int(v) for v in regions_class_order]
+    if len(order) != mean.shape[0] or any(not 0 <= v <= 255 for v in order):
+        raise RuntimeError(f"regions_class_order {order} for {mean.shape[0]} heads (one uint8 label per head)")
+    labels = np.zeros(mean.shape[1:], dtype=np.uint8)
+    for k, c in enumerate(order):
+        labels[mean[k] > 0.5] = c
+    return labels
+
+
+def ensemble_probabilities(members, return_probabilities=False, regions_class_order=None):
     """members: a list of probability volumes (K, ...) as tensors, numpy arrays or .npz paths -> (uint8 labels (...): the first class
     whose mean is the maximum, the fp32 mean (K, ...) or None).  Without return_probabilities the device path allocates no (K, N)
-    buffer."""
+    buffer.  regions_class_order (one label per head): the members are the sigmoid probabilities of a region-based label manager and
+    the labels are painted from the mean in that order."""
     members_in = list(members)
-    members, device = _members(members_in)
+    members, device = _members(members_in, 2 if regions_class_order is None else 1)
     if device is not None:
-        return ops.ensemble_mean(members, want_mean=return_probabilities)
+        return ops.ensemble_mean(members, want_mean=return_probabilities, regions_class_order=regions_class_order)
     mean = _host_mean(members)
-    labels = mean.argmax(0).astype(np.uint8)
+    labels = mean.argmax(0).astype(np.uint8) if regions_class_order is None else _paint_regions(mean, regions_class_order)
     return _wrap(members_in, labels), _wrap(members_in, mean if return_probabilities else None)
 
 
@@ -122,9 +138,9 @@ def merge_files(list_of_files, output_filename_truncated, output_file_ending, im
                 save_probabilities=False, device=None):
     """Drop-in for the reference's merge_files (:32-46): averages the .npz files, writes the segmentation through
     image_reader_writer.write_seg(seg, file, properties) with the properties of the first file's .pkl, and with save_probabilities
-    the mean as .npz and those properties as .pkl.  device: where to ensemble (default: the MI355X when there is one)."""
-    if getattr(label_manager, "has_regions", False):
-        raise NotImplementedError("region-based label managers (sigmoid / regions_class_order) are not supported by the ensembling")
+    the mean as .npz and those properties as .pkl.  device: where to ensemble (default: the MI355X when there is one).  A region-based
+    label manager has its labels painted from the mean in its regions_class_order."""
+    regions_class_order = region_order_of(label_manager)       # a region-based manager without an order is refused here
     if not len(list_of_files):
         raise RuntimeError("At least one file must be given in list_of_files")
     with open(list_of_files[0][:-4] + ".pkl", "rb") as f:
@@ -134,7 +150,8 @@ def merge_files(list_of_files, output_filename_truncated, output_file_ending, im
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if torch.device(device).type == "cuda":
         members = [torch.from_numpy(np.ascontiguousarray(m)).to(device) for m in members]
-    seg, probabilities = ensemble_probabilities(members, return_probabilities=save_probabilities)
+    seg, probabilities = ensemble_probabilities(members, return_probabilities=save_probabilities,
+                                                regions_class_order=regions_class_order)
     image_reader_writer.write_seg(_to_numpy(seg), output_filename_truncated + output_file_ending, properties)
     if save_probabilities:
         np.savez_compressed(output_filename_truncated + ".npz", probabilities=_to_numpy(probabilities))
@@ -163,8 +180,7 @@ def _io(plans, dataset_json, image_reader_writer, label_manager):
         plans_manager = PlansManager(plans)
         image_reader_writer = image_reader_writer or plans_manager.image_reader_writer_class()
         label_manager = label_manager or plans_manager.get_label_manager(dataset_json)
-    if getattr(label_manager, "has_regions", False):
-        raise NotImplementedError("region-based label managers (sigmoid / regions_class_order) are not supported by the ensembling")
+    region_order_of(label_manager)                             # refuses a region-based manager without regions_class_order
     return image_reader_writer, label_manager
 
 

@@ -55,19 +55,46 @@ def hard_tp_fp_fn(logits, target, ignore_label=None):
     return tp[1:], (cm.sum(0) - tp)[1:], (cm.sum(1) - tp)[1:]
 
 
+def hard_tp_fp_fn_regions(logits, target, has_ignore_plane=False):
+    """tp / fp / fn per sigmoid head of ``sigmoid(logits) > 0.5`` against region planes (reference B:906-927 with
+    get_tp_fp_fn_tn(axes=(0, 2, ...), mask=1 - ignore plane)); every head is kept (B:932-939 drops the background of label datasets
+    only).  target (B, R, ...) or, with an ignore plane, (B, R + 1, ...).  Torch ops on the inputs' device, no host synchronisation."""
+    pred = torch.sigmoid(logits) > 0.5
+    if has_ignore_plane:
+        keep = target[:, -1:] != 1                          # mask = 1 - target[:, -1:]: the planes are 0 / 1
+        target = target[:, :-1]
+    else:
+        keep = None
+    if target.shape != logits.shape:
+        raise RuntimeError(f"region planes of shape {tuple(target.shape)} for logits of shape {tuple(logits.shape)}")
+    gt = target != 0
+    axes = [0] + list(range(2, logits.ndim))
+    tp, fp, fn = pred & gt, pred & ~gt, ~pred & gt
+    if keep is not None:
+        tp, fp, fn = tp & keep, fp & keep, fn & keep
+    return tp.sum(axes), fp.sum(axes), fn.sum(axes)
+
+
 @torch.no_grad()
-def validation_step(network, data, target, batch_dice=True, ddp=False, ignore_label=None, loss_fn=None):
+def validation_step(network, data, target, batch_dice=True, ddp=False, ignore_label=None, loss_fn=None, regions=False):
     """reference validation_step: {'loss', 'tp_hard', 'fp_hard', 'fn_hard'} (device tensors, no host sync).  ``loss_fn``:
     the trainer's own loss (B:897 ``self.loss(output, target)``); default: the fused Dice + CE deep-supervision loss with
-    ``ignore_label`` masked inside K9."""
+    ``ignore_label`` masked inside K9.  ``regions``: the heads are the sigmoid regions of a region-based label manager and the targets
+    are region planes (the ignore plane last when ``ignore_label`` is not None): the default loss is the fused Dice + BCE loss (K29)
+    and the counts are per head, none dropped (B:906-939)."""
     output = network(data)
     if not isinstance(output, (list, tuple)):
         output, target = [output], target if isinstance(target, (list, tuple)) else [target]
     if loss_fn is not None:
         loss = loss_fn(output, target)
+    elif regions:
+        loss = trainer.region_deep_supervision_loss(output, target, None, batch_dice=batch_dice, ddp=ddp, ignore_label=ignore_label)
     else:
         loss = trainer.deep_supervision_loss(output, target, batch_dice=batch_dice, ddp=ddp, ignore_label=ignore_label)
-    tp, fp, fn = hard_tp_fp_fn(output[0], target[0], ignore_label)
+    if regions:
+        tp, fp, fn = hard_tp_fp_fn_regions(output[0], target[0], ignore_label is not None)
+    else:
+        tp, fp, fn = hard_tp_fp_fn(output[0], target[0], ignore_label)
     return {"loss": loss.detach(), "tp_hard": tp, "fp_hard": fp, "fn_hard": fn}
 
 

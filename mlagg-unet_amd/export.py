@@ -14,7 +14,11 @@ Every coordinate comes from one table per output axis (_axis_taps), built in flo
 indices and their two weights.  A device tensor takes K21 (csrc/export.hip): one fused kernel for up to 32 classes that never
 materialises the resampled logits, or the resampling kernel followed by torch's softmax / argmax for more.  A CPU tensor or numpy
 array takes the host path: the same separable blend in torch float64, then the same fp32 softmax, argmax and paste.  Both give the
-same fp32 resampled logits bit for bit.  Region-based label managers are not supported.
+same fp32 resampled logits bit for bit.
+
+Region-based label managers (sigmoid heads, dataset.json with tuple-valued labels and a regions_class_order) take step 2 in the form of
+label_handling.py:46-47, 166-173: the fp32 sigmoid of every head, and a label that starts at 0 and takes regions_class_order[i] wherever
+sigmoid_i > 0.5, for i in order -- the last match wins.  K21 has a region mode for it (mlagg_export_segmentation_regions).
 """
 import json
 import os
@@ -200,12 +204,29 @@ def _geometry(logits, properties, transpose_backward):
     return crop, full, tuple(b[0] for b in bbox), perm
 
 
-def _finish(resampled, crop, full, lo, perm, return_probabilities):
-    """Softmax, argmax, paste and transpose of resampled logits (K, *crop), on their device (host path and K > 32)."""
-    probs = torch.softmax(resampled, 0)
+def paint_regions(probabilities, regions_class_order):
+    """convert_probabilities_to_segmentation of a region-based label manager (label_handling.py:166-173): probabilities (K, ...) ->
+    uint8 labels (...), 0 and then regions_class_order[i] wherever probabilities[i] > 0.5, in order (the last match wins)."""
+    order = [int(v) for v in regions_class_order]
+    if len(order) != probabilities.shape[0] or any(not 0 <= v <= 255 for v in order):
+        raise RuntimeError(f"regions_class_order {order} for {probabilities.shape[0]} heads (one uint8 label per head)")
+    seg = torch.zeros(probabilities.shape[1:], dtype=torch.uint8, device=probabilities.device)
+    for i, c in enumerate(order):
+        seg[probabilities[i] > 0.5] = c
+    return seg
+
+
+def _finish(resampled, crop, full, lo, perm, return_probabilities, regions_class_order=None):
+    """Softmax, argmax, paste and transpose of resampled logits (K, *crop), on their device (host path and K > 32); with
+    regions_class_order: sigmoid and the painting of the regions instead of softmax and argmax."""
     sl = tuple(slice(a, a + c) for a, c in zip(lo, crop))
     seg = torch.zeros(full, dtype=torch.uint8, device=resampled.device)
-    seg[sl] = probs.argmax(0).to(torch.uint8)
+    if regions_class_order is not None:
+        probs = torch.sigmoid(resampled)
+        seg[sl] = paint_regions(probs, regions_class_order)
+    else:
+        probs = torch.softmax(resampled, 0)
+        seg[sl] = probs.argmax(0).to(torch.uint8)
     seg = seg.permute(perm).contiguous()
     if not return_probabilities:
         return seg, None
@@ -215,11 +236,14 @@ def _finish(resampled, crop, full, lo, perm, return_probabilities):
 
 
 def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properties, configuration_spacing, transpose_backward=(0, 1, 2),
-                                                                 return_probabilities=False, order=1, order_z=0, force_separate_z=None):
+                                                                 return_probabilities=False, order=1, order_z=0, force_separate_z=None,
+                                                                 regions_class_order=None):
     """logits (K, x, y, z) in the preprocessed geometry (any strides) -> (segmentation uint8 in the original geometry, probabilities
     (K, *original) fp32 or None), on the logits' device: export_prediction.py:28-63 with the default probability resampler.
     properties: the preprocessing's dict (spacing, shape_before_cropping, bbox_used_for_cropping,
-    shape_after_cropping_and_before_resampling); configuration_spacing: the plan configuration's spacing (2 or 3 values)."""
+    shape_after_cropping_and_before_resampling); configuration_spacing: the plan configuration's spacing (2 or 3 values).
+    regions_class_order (one label per head): the logits are the sigmoid heads of a region-based label manager; the probabilities are
+    their sigmoids and the segmentation is painted in that order (label_handling.py:166-173)."""
     logits = _as_logits(logits)
     crop, full, lo, perm = _geometry(logits, properties, transpose_backward)
     cur = current_spacing_for(configuration_spacing, properties)
@@ -228,11 +252,22 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properti
     if logits.is_cuda:
         from . import ops
         if logits.shape[0] <= ops.EXPORT_MAX_CLASSES:
-            return ops.export_segmentation(logits, taps, crop, lo, full, perm, return_probabilities)
+            return ops.export_segmentation(logits, taps, crop, lo, full, perm, return_probabilities, regions_class_order)
         resampled = logits if kinds is None else ops.resample_linear(logits, taps, crop)
     else:
         resampled = logits if kinds is None else _resample_host(logits, taps, crop)
-    return _finish(resampled, crop, full, lo, perm, return_probabilities)
+    return _finish(resampled, crop, full, lo, perm, return_probabilities, regions_class_order)
+
+
+def region_order_of(label_manager):
+    """regions_class_order of a region-based label manager, None for a label-based one."""
+    if not getattr(label_manager, "has_regions", False):
+        return None
+    order = getattr(label_manager, "regions_class_order", None)
+    if order is None:
+        raise NotImplementedError("a region-based label manager without regions_class_order is not supported: the labels are "
+                                  "painted in that order (label_handling.py:158-173)")
+    return [int(v) for v in order]
 
 
 def export_prediction_from_softmax(predicted_array_or_file, properties_dict, configuration_manager, plans_manager,
@@ -240,7 +275,7 @@ def export_prediction_from_softmax(predicted_array_or_file, properties_dict, con
     """Drop-in for the reference's export_prediction_from_softmax (export_prediction.py:10-69), same arguments and files.  The logits
     are exported where they live: a device tensor through K21, a CPU tensor or numpy array (or a .npy / .npz file, removed after
     loading) through the host path.  Duck-typed: configuration_manager.spacing, plans_manager.transpose_backward,
-    plans_manager.get_label_manager(dataset_json) (region-based managers raise NotImplementedError) and
+    plans_manager.get_label_manager(dataset_json) (a region-based manager gives its regions_class_order) and
     plans_manager.image_reader_writer_class().write_seg(seg, file, properties)."""
     if isinstance(predicted_array_or_file, str):
         path = predicted_array_or_file
@@ -255,15 +290,14 @@ def export_prediction_from_softmax(predicted_array_or_file, properties_dict, con
         with open(dataset_json_dict_or_file) as f:
             dataset_json_dict_or_file = json.load(f)
     label_manager = plans_manager.get_label_manager(dataset_json_dict_or_file)
-    if getattr(label_manager, "has_regions", False):
-        raise NotImplementedError("region-based label managers (sigmoid / regions_class_order) are not supported by the export")
+    regions_class_order = region_order_of(label_manager)
     kwargs = dict(getattr(configuration_manager, "configuration", {}).get("resampling_fn_probabilities_kwargs", {}) or {})
     if kwargs.pop("is_seg", False):
         raise NotImplementedError("the probability resampler must not be a segmentation resampler")
     kwargs = {k: kwargs[k] for k in ("order", "order_z", "force_separate_z") if k in kwargs}
     seg, probs = convert_predicted_logits_to_segmentation_with_correct_shape(
         predicted_array_or_file, properties_dict, configuration_manager.spacing, plans_manager.transpose_backward,
-        return_probabilities=save_probabilities, **kwargs)
+        return_probabilities=save_probabilities, regions_class_order=regions_class_order, **kwargs)
     if save_probabilities:
         np.savez_compressed(output_file_truncated + ".npz", probabilities=probs.cpu().numpy())
         with open(output_file_truncated + ".pkl", "wb") as f:

@@ -17,8 +17,9 @@ What the class overrides, and why the inherited method cannot stay (B = nnUNetTr
   * ``initialize``  B:193-215 wraps with a plain ``DDP(...)``; here ``trainer.wrap_ddp`` (bucket views, no buffer
                     broadcast) and the loss is rebuilt so that it knows about DDP.
   * ``_build_loss`` T:106-129: the fused Dice + CE deep-supervision loss (K9) with the batch-dice exchange as one
-                    all-reduce; the ignore label of partially annotated datasets is handled in K9; region datasets keep the
-                    reference's own loss classes.
+                    all-reduce; the ignore label of partially annotated datasets is handled in K9; region datasets
+                    (sigmoid heads, B:330-336) get the fused Dice + BCE loss (K29) on the region planes nnU-Net delivers; a
+                    label manager that says ``has_regions`` without naming its ``foreground_regions`` keeps the reference's classes.
 """
 import os
 
@@ -34,6 +35,27 @@ PRECISIONS = ("fp32", "bf16", "fp16")
 # the read-back.  Single-process fp32 / bf16 training only; MLAGG_PLUGIN_GRAPH=0 keeps every step eager.
 PLUGIN_GRAPH = os.environ.get("MLAGG_PLUGIN_GRAPH", "1") == "1"
 GRAPH_AFTER = 3
+
+
+def _describes_regions(label_manager):
+    """A region-based label manager as nnU-Net's LabelManager is one: it names its ``foreground_regions``, one per segmentation head
+    (label_handling.py:214-227).  An object that only says ``has_regions`` keeps the reference's own loss classes, its validation
+    body and eager steps."""
+    regions = getattr(label_manager, "foreground_regions", None)
+    return bool(regions) and len(regions) == getattr(label_manager, "num_segmentation_heads", len(regions))
+
+
+def _region_loss(batch_dice, ddp, ignore_label):
+    """The loss of a region-based label manager (reference B:330-352: DeepSupervisionWrapper(DC_and_BCE_loss)): the fused K29 loss on
+    the region planes that ConvertSegmentationToRegionsTransform delivers, the ignore plane last when there is an ignore label."""
+
+    def loss(output, target):
+        if not isinstance(output, (list, tuple)):                                   # deep supervision off
+            output, target = [output], [target if torch.is_tensor(target) else target[0]]
+        return trainer.region_deep_supervision_loss(list(output), list(target[:len(output)]), None, batch_dice, ddp,
+                                                    ignore_label=ignore_label)
+
+    return loss
 
 
 def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32"):
@@ -92,12 +114,10 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32"):
 
         def _build_loss(self):                                                      # reference T:106-129
             lm = self.label_manager
-            if getattr(lm, "has_regions", False):
-                # DC_and_BCE_loss on region targets (T:107-112): not on the MLAgg-UNet benchmark path; the reference's own
-                # torch loss classes run unchanged on the device logits
-                return super()._build_loss()
             batch_dice, ddp = bool(self.configuration_manager.batch_dice), bool(self.is_ddp)
             ignore = getattr(lm, "ignore_label", None)                              # T:116: partially annotated datasets
+            if getattr(lm, "has_regions", False):                                   # DC_and_BCE_loss on region planes (T:107-112)
+                return _region_loss(batch_dice, ddp, ignore) if _describes_regions(lm) else super()._build_loss()
 
             def loss(output, target):
                 if not isinstance(output, (list, tuple)):                           # deep supervision off (validation of
@@ -109,8 +129,9 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32"):
 
         def _graph_ok(self):
             """The step may be replayed as a hipGraph: one process, no GradScaler, the fused device loss, a device network."""
+            lm = self.label_manager
             return bool(PLUGIN_GRAPH and self._graph_failed is None and not self.is_ddp and self.grad_scaler is None
-                        and self.device.type == "cuda" and not getattr(self.label_manager, "has_regions", False))
+                        and self.device.type == "cuda" and (not getattr(lm, "has_regions", False) or _describes_regions(lm)))
 
         def configure_optimizers(self):                                             # reference T:137-147
             # capturable: learning rate and step counter live on the device, so the same optimizer serves eager and replayed steps
@@ -150,12 +171,14 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32"):
             return {"loss": loss.cpu().numpy()}                                     # the reference's per-step host copy
 
         def validation_step(self, batch):                                           # reference B:880-942
-            if getattr(self.label_manager, "has_regions", False):
-                return super().validation_step(batch)        # sigmoid regions (B:899-905): the reference's own body
+            lm = self.label_manager
+            if getattr(lm, "has_regions", False) and not _describes_regions(lm):
+                return super().validation_step(batch)        # the reference's loss classes: the reference's own body too
             data, target = self._to_device(batch)
-            # B:897 evaluates self.loss; B:917-929 masks the ignore label out of tp / fp / fn
+            # B:897 evaluates self.loss; B:917-929 masks the ignore label out of tp / fp / fn; sigmoid regions: B:906-907, 920-923
             return evaluation.validation_step(self.network, data, target, self.configuration_manager.batch_dice,
-                                              self.is_ddp, getattr(self.label_manager, "ignore_label", None), self.loss)
+                                              self.is_ddp, getattr(self.label_manager, "ignore_label", None), self.loss,
+                                              regions=bool(getattr(self.label_manager, "has_regions", False)))
 
         def on_validation_epoch_end(self, val_outputs):                             # reference B:944-978
             res = evaluation.validation_epoch_end(val_outputs)
@@ -211,10 +234,10 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer):
 
         def _build_loss(self):                                                       # reference B:330-352
             lm = self.label_manager
-            if getattr(lm, "has_regions", False):
-                return super()._build_loss()
             batch_dice, ddp = bool(self.configuration_manager.batch_dice), bool(self.is_ddp)
             ignore = getattr(lm, "ignore_label", None)
+            if getattr(lm, "has_regions", False):
+                return _region_loss(batch_dice, ddp, ignore) if _describes_regions(lm) else super()._build_loss()
 
             def loss(output, target):
                 if not isinstance(output, (list, tuple)):

@@ -1754,6 +1754,98 @@ def dice_ce_stats(logits, targets, ignore_label=None):
     return DiceCEStatsFn.apply(len(logits), -1 if ignore_label is None else int(ignore_label), *logits, *targets)
 
 
+_REGION_TABLES = {}
+_REGION_WORKSPACES = {}
+REGION_LOSS_MAX_REGIONS = 16       # heads held in registers by K29 (mlagg_dice_bce_max_regions)
+
+
+def region_member_table(regions, device):
+    """The K29 membership table of a label manager's ``foreground_regions`` (ints or tuples of ints) as 256 int32 (uint32 bits) on
+    `device`: bit r of entry v says that label v belongs to region r -- ``np.isin(seg, regions[r])`` for every r at once.  Uploaded
+    once per (regions, device)."""
+    key = (tuple(tuple(int(v) for v in r) if isinstance(r, (tuple, list)) else (int(r),) for r in regions), str(device))
+    if key not in _REGION_TABLES:
+        if not 1 <= len(key[0]) <= 32:
+            raise RuntimeError(f"region_member_table: {len(key[0])} regions, 1 to 32 fit the table")
+        table = np.zeros(256, dtype=np.uint32)
+        for r, labels in enumerate(key[0]):
+            for v in labels:
+                if 0 <= v < 256:
+                    table[v] |= np.uint32(1 << r)
+        _REGION_TABLES[key] = torch.from_numpy(table.view(np.int32)).to(device)
+    return _REGION_TABLES[key]
+
+
+class DiceBCEStatsFn(torch.autograd.Function):
+    """K29: per-level Dice / binary cross-entropy statistics of ALL deep-supervision levels of a region-based dataset (one kernel per
+    level each way).
+
+    ``DiceBCEStatsFn.apply(n_levels, ignore_label, member, *logits, *targets)`` -> (ip (L, B, 2, R): intersect and sum_pred per sample
+    and head, gt (L, B, R): masked target sums, sums (L, 2): the summed binary cross-entropy and the mask sum); gradients flow to the
+    logits from ip and sums[:, 0].  ``member``: the table of ``region_member_table`` when the targets are label maps (B, 1, ...), None
+    when they are region planes (B, R, ...) -- (B, R + 1, ...) with the ignore plane last when ``ignore_label`` >= 0.
+    The per-level workspaces are cached per shape and device; nothing here synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, n, ignore_label, member, *tensors):
+        logits, targets = tensors[:n], tensors[n:]
+        ctx.ignore = int(ignore_label)
+        B, R = logits[0].shape[:2]
+        dev = logits[0].device
+        lib = _lib.lib()
+        if not 1 <= R <= REGION_LOSS_MAX_REGIONS:
+            raise RuntimeError(f"dice_bce_stats: {R} heads, 1 to {REGION_LOSS_MAX_REGIONS} are supported")
+        if member is not None and not (member.is_cuda and member.dtype == torch.int32 and member.numel() == 256
+                                       and member.is_contiguous() and member.device == dev):
+            raise RuntimeError("dice_bce_stats: the member table is region_member_table(regions, device)")
+        planes = 1 if member is not None else R + (1 if ctx.ignore >= 0 else 0)
+        buf = torch.empty(n * B * 3 * R + 2 * n, device=dev, dtype=torch.float32)   # every entry is written by the level's reduce
+        ip = buf[:n * B * 2 * R].view(n, B, 2, R)
+        gt = buf[n * B * 2 * R:n * B * 3 * R].view(n, B, R)
+        sums = buf[n * B * 3 * R:].view(n, 2)
+        saved = []
+        for i, (z, t) in enumerate(zip(logits, targets)):
+            z = _require(z.contiguous(), "logits")
+            t = _require(t.contiguous(), "target")
+            hw = z.numel() // (B * R)
+            if z.shape[:2] != (B, R) or t.shape[0] != B or t.numel() != B * planes * hw:
+                raise RuntimeError(f"dice_bce_stats: logits {tuple(z.shape)} / target {tuple(t.shape)} of level {i} do not match "
+                                   f"({planes} target plane(s) expected)")
+            key = (B, R, hw, str(dev))
+            ws = _REGION_WORKSPACES.get(key)
+            if ws is None:
+                ws = _REGION_WORKSPACES[key] = torch.empty(lib.mlagg_dice_bce_stats_workspace_floats(B, R, hw), device=dev,
+                                                           dtype=torch.float32)
+            _launch("mlagg_dice_bce_stats", _ptr(z), _ptr(t), _ptr(member), _ptr(ip[i]), _ptr(gt[i]), sums.data_ptr() + 8 * i, _ptr(ws),
+                    B, R, hw, ctx.ignore)
+            saved += [z, t]
+        ctx.save_for_backward(*saved)
+        ctx.n, ctx.member = n, member
+        ctx.mark_non_differentiable(gt)
+        return ip, gt, sums
+
+    @staticmethod
+    def backward(ctx, g_ip, g_gt, g_sums):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        B, R = saved[0].shape[:2]
+        g_ip = torch.zeros(n, B, 2, R, device=saved[0].device) if g_ip is None else _require(g_ip.contiguous(), "g_ip")
+        g_sums = torch.zeros(n, 2, device=saved[0].device) if g_sums is None else _require(g_sums.contiguous(), "g_sums")
+        grads = []
+        for i in range(n):
+            z, t = saved[2 * i], saved[2 * i + 1]
+            dz = torch.empty_like(z)
+            _launch("mlagg_dice_bce_grad", _ptr(z), _ptr(t), _ptr(ctx.member), _ptr(g_ip[i]), g_sums.data_ptr() + 8 * i, _ptr(dz), B, R,
+                    z.numel() // (B * R), ctx.ignore)
+            grads.append(dz)
+        return (None, None, None, *grads, *([None] * n))
+
+
+def dice_bce_stats(logits, targets, member_table=None, ignore_label=None):
+    """K29 over all levels in one apply: see DiceBCEStatsFn.  member_table None: the targets are region planes."""
+    return DiceBCEStatsFn.apply(len(logits), -1 if ignore_label is None else int(ignore_label), member_table, *logits, *targets)
+
+
 def transpose_2d(src):
     """(B, R, C) -> (B, C, R) contiguous on the tiled transpose kernel (K8).  The source matrices must be contiguous;
     their batch stride may be larger than R * C (a channel slice of an NCHW map), anything else is copied first."""
@@ -2732,9 +2824,12 @@ def resample_linear(logits, taps, out_shape):
 EXPORT_MAX_CLASSES = 32        # classes held in registers by the fused export kernel
 
 
-def export_segmentation(logits, taps, crop_shape, box_lo, shape_before_cropping, transpose_backward, return_probabilities=False):
+def export_segmentation(logits, taps, crop_shape, box_lo, shape_before_cropping, transpose_backward, return_probabilities=False,
+                        regions_class_order=None):
     """The fused export of K <= 32 classes: resample logits (K, X, Y, Z) to crop_shape with the tap tables, fp32 softmax over K,
     first-maximum argmax, pasted at box_lo into shape_before_cropping (zeros outside) and transposed by transpose_backward.
+    regions_class_order (K labels in 0 .. 255): the heads are the sigmoid regions of a region-based label manager -- fp32 sigmoid
+    per head, and the label is 0, then regions_class_order[i] wherever sigmoid_i > 0.5, i = 0 .. K-1 in order.
     Returns (labels uint8, probabilities (K, ...) fp32 or None), contiguous."""
     shape, st = _strided_volume(logits, "logits")
     K = shape[0]
@@ -2752,6 +2847,13 @@ def export_segmentation(logits, taps, crop_shape, box_lo, shape_before_cropping,
     out_shape = tuple(full[p] for p in perm)
     labels = torch.empty(out_shape, device=logits.device, dtype=torch.uint8)
     probs = torch.empty((K,) + out_shape, device=logits.device, dtype=torch.float32) if return_probabilities else None
+    if regions_class_order is not None:
+        order = [int(v) for v in regions_class_order]
+        if len(order) != K or any(not 0 <= v <= 255 for v in order):
+            raise RuntimeError(f"export_segmentation: regions_class_order {order} for {K} heads (one uint8 label per head)")
+        _launch("mlagg_export_segmentation_regions", _ptr(logits), *shape, *st, _ptr(idx), _ptr(w), *crop, _int_array(lo),
+                _int_array(full), _int_array(perm), _int_array(order), _ptr(labels), _ptr(probs))
+        return labels, probs
     _launch("mlagg_export_segmentation", _ptr(logits), *shape, *st, _ptr(idx), _ptr(w), *crop, _int_array(lo), _int_array(full),
             _int_array(perm), _ptr(labels), _ptr(probs))
     return labels, probs
@@ -3246,10 +3348,12 @@ ENSEMBLE_MAX_CLASSES = _C["MLAGG_ENSEMBLE_MAX_CLASSES"]
 CONFUSION_MAX_LABELS = _C["MLAGG_CONFUSION_MAX_LABELS"]
 
 
-def ensemble_mean(members, want_mean=False):
+def ensemble_mean(members, want_mean=False, regions_class_order=None):
     """members: M >= 1 contiguous fp32 or fp16 device tensors of one shape (K, ...), 2 <= K <= ENSEMBLE_MAX_CLASSES (views into larger
     buffers are fine) -> (labels (...) uint8: the first class whose mean is the maximum, a NaN counting as one; mean (K, ...) fp32 or
-    None).  The mean is ((m_0 + m_1) + ...) / M in fp32, numpy's arithmetic to the bit.  Without want_mean no (K, N) buffer exists."""
+    None).  The mean is ((m_0 + m_1) + ...) / M in fp32, numpy's arithmetic to the bit.  Without want_mean no (K, N) buffer exists.
+    regions_class_order (K labels in 0 .. 255, K >= 1): the members are sigmoid probabilities of a region-based label manager; the
+    mean is the same and the label is 0, then regions_class_order[k] wherever mean_k > 0.5, k = 0 .. K-1 in order."""
     members = list(members)
     if not members:
         raise RuntimeError("ensemble_mean: at least one member must be given")
@@ -3262,14 +3366,22 @@ def ensemble_mean(members, want_mean=False):
             raise RuntimeError(f"members[{i}]: shape {tuple(m.shape)}, expected (K, ...) = {tuple(first.shape)} as members[0]")
     K = int(first.shape[0])
     N = first.numel() // max(K, 1)
-    if K < 2 or K > ENSEMBLE_MAX_CLASSES:
-        raise RuntimeError(f"ensemble_mean: {K} classes, 2 to {ENSEMBLE_MAX_CLASSES} are supported (labels are uint8)")
+    order = None
+    if regions_class_order is not None:
+        order = [int(v) for v in regions_class_order]
+        if len(order) != K or any(not 0 <= v <= 255 for v in order):
+            raise RuntimeError(f"ensemble_mean: regions_class_order {order} for {K} heads (one uint8 label per head)")
+    if K < (2 if order is None else 1) or K > ENSEMBLE_MAX_CLASSES:
+        raise RuntimeError(f"ensemble_mean: {K} classes, {2 if order is None else 1} to {ENSEMBLE_MAX_CLASSES} are supported "
+                           "(labels are uint8)")
     if N < 1:
         raise RuntimeError(f"ensemble_mean: empty members {tuple(first.shape)}")
-    table = torch.tensor([[m.data_ptr(), m.element_size()] for m in members], dtype=torch.int64).to(first.device)
+    rows = [v for m in members for v in (m.data_ptr(), m.element_size())]
+    table = torch.tensor(rows + (order or []), dtype=torch.int64).to(first.device)
     labels = torch.empty(first.shape[1:], dtype=torch.uint8, device=first.device)
     mean = torch.empty(first.shape, dtype=torch.float32, device=first.device) if want_mean else None
-    _launch("mlagg_ensemble_mean", _ptr(table), len(members), K, N, _ptr(labels), _ptr(mean))
+    _launch("mlagg_ensemble_mean" if order is None else "mlagg_ensemble_mean_regions", _ptr(table), len(members), K, N, _ptr(labels),
+            _ptr(mean))
     return labels, mean
 
 

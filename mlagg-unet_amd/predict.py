@@ -7,16 +7,35 @@ one chain of this package's functions:
 
 On a CUDA device every step runs on the device (K22, the sliding window with K20 for 3-D tiles, K21); the only read-back on the way
 is K22's crop box.  The result is a uint8 label volume in the original geometry, which evaluation.abdomen_case_dsc scores directly.
+A region-based dataset.json (tuple-valued labels with a regions_class_order) has one sigmoid head per region; its labels are painted in
+that order by the export.
 """
 import torch
 
 from . import export, inference, postprocessing as pp, preprocessing
 
 
+def _regions_class_order(dataset_json):
+    """regions_class_order of a region-based dataset.json (a label with more than one value, label_handling.py:32-33), else None."""
+    if not any(isinstance(v, (list, tuple)) and len(v) > 1 for v in dataset_json["labels"].values()):
+        return None
+    if dataset_json.get("regions_class_order") is None:
+        raise NotImplementedError("a dataset.json with region labels and no regions_class_order is not supported "
+                                  "(label_handling.py:81-82)")
+    return [int(v) for v in dataset_json["regions_class_order"]]
+
+
 def _num_segmentation_heads(dataset_json):
     labels = dataset_json["labels"]
-    if "regions_class_order" in dataset_json or any(isinstance(v, (list, tuple)) and len(v) > 1 for v in labels.values()):
-        raise NotImplementedError("region-based label managers are not supported")
+    order = _regions_class_order(dataset_json)
+    if order is not None:
+        # one sigmoid head per foreground region: every entry but 'ignore' and those that are background only (label_handling.py:77-99)
+        regions = [v for k, v in labels.items() if k != "ignore"
+                   and not (set(v) == {0} if isinstance(v, (list, tuple)) else int(v) == 0)]
+        if len(regions) != len(order):
+            raise NotImplementedError(f"regions_class_order has {len(order)} entries for {len(regions)} regions: one label per "
+                                      "region is supported (label_handling.py:96-98)")
+        return len(regions)
     values = sorted({int(v[0] if isinstance(v, (list, tuple)) else v) for v in labels.values()})
     if "ignore" in labels:                               # the ignore label is not a segmentation head (label_handling.py)
         values.remove(int(labels["ignore"]))
@@ -52,7 +71,8 @@ def predict_case(network, image, properties, plans, configuration_name, dataset_
     if parameters is not None and len(parameters) > 1:
         logits = logits / len(parameters)
     seg, probs = export.convert_predicted_logits_to_segmentation_with_correct_shape(
-        logits, props, cfg["spacing"], plans.get("transpose_backward", [0, 1, 2]), return_probabilities=return_probabilities)
+        logits, props, cfg["spacing"], plans.get("transpose_backward", [0, 1, 2]), return_probabilities=return_probabilities,
+        regions_class_order=_regions_class_order(dataset_json))
     if postprocessing is not None:
         seg = pp.apply_postprocessing(seg, *postprocessing)
     return seg, probs

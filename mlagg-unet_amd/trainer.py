@@ -7,6 +7,8 @@ Mirrors the reference's trainer surface on the hot path:
                               timm CosineLRScheduler restated: t_initial 500, lr_min 1e-6, warmup 10 @ 1e-4)
   * ``deep_supervision_loss`` reference loss/deep_supervision.py:17-34 over DC_and_CE_loss
                               (loss/compound_losses.py:31-57, loss/dice.py:73-117, loss/robust_ce_loss.py:12-16)
+  * ``region_deep_supervision_loss``  the same wrapper over DC_and_BCE_loss (loss/compound_losses.py:60-100), the loss of
+                              region-based datasets with sigmoid heads (nnUNetTrainer.py:330-336)
   * ``wrap_ddp``              reference nnUNetTrainer.py:205-207, without its ``dummy_tensor`` hazard
   * ``split_batch_size``      reference nnUNetTrainer.py:283-328 with the zero/negative per-rank sizes fixed (7c)
 One process per GPU; ``torch.distributed`` backend "nccl" is RCCL on ROCm (xGMI inside a node).
@@ -130,6 +132,93 @@ def deep_supervision_loss(outputs, targets, batch_dice=True, ddp=False, smooth=1
         # level has ce = 0 and contributes nothing, like the reference's `num_fg > 0` test
         w_ce = w_dice / gt.sum((1, 2)).clamp(min=1.0)
     return (w_ce * ce + w_dice * dice).sum()
+
+
+# ------------------------------------------------------------------------------------------------
+# loss of region-based datasets (sigmoid heads)
+# ------------------------------------------------------------------------------------------------
+def regions_from_label_map(target, regions, ignore_label=None):
+    """A label map (B, 1, ...) as the float region planes (B, R, ...) that nnU-Net's ConvertSegmentationToRegionsTransform writes --
+    plane r is ``np.isin(seg, regions[r])`` -- followed, with an ignore label, by the plane of the pixels that carry it."""
+    planes = []
+    for r in regions:
+        values = torch.as_tensor([int(v) for v in (r if isinstance(r, (tuple, list)) else (r,))], device=target.device).to(target.dtype)
+        planes.append(torch.isin(target, values))
+    if ignore_label is not None:
+        planes.append(target == ignore_label)
+    return torch.cat(planes, 1).to(target.dtype)
+
+
+def dc_and_bce_loss(logits, target, batch_dice=True, ddp=False, use_ignore_label=False, smooth=1e-5):
+    """DC_and_BCE_loss.forward (loss/compound_losses.py:84-100) as nnUNetTrainer.py:330-336 builds it, in torch ops, one level:
+    MemoryEfficientSoftDiceLoss(apply_nonlin=sigmoid, do_bg=True, smooth=1e-5) + BCEWithLogitsLoss.  target: region planes
+    (B, R, ...); with use_ignore_label the ignore plane follows them (B, R + 1, ...) and masks both terms."""
+    axes = tuple(range(2, logits.ndim))
+    probs = torch.sigmoid(logits)
+    if use_ignore_label:
+        mask = (1 - target[:, -1:]).bool()
+        target = target[:, :-1]
+        with torch.no_grad():
+            sum_gt = (target * mask).sum(axes)
+        intersect = (probs * target * mask).sum(axes)
+        sum_pred = (probs * mask).sum(axes)
+    else:
+        mask = None
+        with torch.no_grad():
+            sum_gt = target.sum(axes)
+        intersect = (probs * target).sum(axes)
+        sum_pred = probs.sum(axes)
+    if batch_dice:
+        stats = torch.stack([intersect.sum(0), sum_pred.sum(0), sum_gt.sum(0)])
+        if ddp:
+            stats = _AllGatherSum.apply(stats)
+        intersect, sum_pred, sum_gt = stats[0], stats[1], stats[2]
+    dc = -((2 * intersect + smooth) / torch.clip(sum_gt + sum_pred + smooth, 1e-8)).mean()
+    if mask is None:
+        return F.binary_cross_entropy_with_logits(logits, target) + dc
+    bce = (F.binary_cross_entropy_with_logits(logits, target, reduction="none") * mask).sum() / torch.clip(mask.sum(), min=1e-8)
+    return bce + dc
+
+
+def region_deep_supervision_loss_eager(outputs, targets, regions=None, batch_dice=True, ddp=False, smooth=1e-5, ignore_label=None):
+    """The region loss as the reference composes it, level by level in torch ops (host tensors, CPU tests, more than 16 heads)."""
+    if regions is not None:
+        targets = [regions_from_label_map(t, regions, ignore_label) for t in targets]
+    ws = deep_supervision_weights(len(outputs))
+    total = None
+    for w, o, t in zip(ws, outputs, targets):
+        level = w * dc_and_bce_loss(o, t, batch_dice, ddp, ignore_label is not None, smooth)
+        total = level if total is None else total + level
+    return total
+
+
+def region_deep_supervision_loss(outputs, targets, regions=None, batch_dice=True, ddp=False, smooth=1e-5, ignore_label=None):
+    """DeepSupervisionWrapper(DC_and_BCE_loss) of reference nnUNetTrainer.py:330-352, the loss of region-based datasets.
+    regions: the label manager's ``foreground_regions`` -- the targets are then LABEL MAPS (B, 1, ...) and ``ignore_label`` is the label
+    value that masks a pixel; None: the targets are REGION PLANES (B, R, ...) as ConvertSegmentationToRegionsTransform delivers them,
+    and ``ignore_label is not None`` says that the ignore plane follows them (B, R + 1, ...).
+    On the MI355X: K29 reads every logit map once for the statistics and once for the gradient; the (levels, heads)-sized algebra
+    below is torch, vectorised over the levels, and the batch-dice statistics of all levels cross the ranks in ONE all-reduce each way.
+    Dice keeps all R heads (do_bg=True).  Without an ignore label the cross-entropy is the mean over B R HW elements; with one it is
+    the masked sum over clip(mask sum, 1e-8) -- the mask sum has no factor R and is local to the rank (compound_losses.py:96) -- so a
+    fully ignored level gives 0 there and -1 from the dice.  CPU tensors, and more than 16 heads, take the eager composition."""
+    from . import ops
+    if not outputs[0].is_cuda or outputs[0].shape[1] > ops.REGION_LOSS_MAX_REGIONS:
+        return region_deep_supervision_loss_eager(outputs, targets, regions, batch_dice, ddp, smooth, ignore_label)
+    member = None if regions is None else ops.region_member_table(regions, outputs[0].device)
+    ip, gt, sums = ops.dice_bce_stats(list(outputs), list(targets), member, ignore_label)     # (L, B, 2, R), (L, B, R), (L, 2)
+    inter, pred = ip[:, :, 0], ip[:, :, 1]
+    if batch_dice:
+        stats = torch.stack([inter.sum(1), pred.sum(1), gt.sum(1)])             # (3, L, R)
+        if ddp:
+            stats = _AllGatherSum.apply(stats)
+        inter, pred, gt = stats[0], stats[1], stats[2]
+    dc = (2 * inter + smooth) / torch.clip(gt + pred + smooth, 1e-8)
+    dice = -dc.flatten(1).mean(1)                                               # (L,)
+    w_bce, w_dice = _level_constants(tuple(o.numel() for o in outputs), sums.device)      # BCE mean over B * R * HW elements
+    if ignore_label is not None:
+        w_bce = w_dice / sums[:, 1].clamp(min=1e-8)
+    return (w_bce * sums[:, 0] + w_dice * dice).sum()
 
 
 # ------------------------------------------------------------------------------------------------
