@@ -70,6 +70,21 @@ __device__ __forceinline__ float dotv(const float (&a)[NF], const float *__restr
     return acc;
 }
 
+// d(o) . v of backward-1 AND backward-2: four strided FMA chains, then (0 + 1) + (2 + 3).  Both kernels call this one function on
+// the same bits, so the row sums D that backward-1 hands on are sums of the very numbers backward-2 subtracts them from:
+// s (d(o) . v - D) then cancels as in exact arithmetic (to zero for a single key) instead of leaving the difference of two roundings.
+// Change the order here and both kernels follow; give either kernel an order of its own and the difference comes back.
+template <int NF>
+__device__ __forceinline__ float dot_strided(const float (&a)[NF], const float (&b)[NF])
+{
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < NF; e += 4)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = fmaf(a[e + j], b[e + j], acc[j]);
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+
 template <int NF>
 __device__ __forceinline__ void axpyv(float (&acc)[NF], float w, const float *__restrict__ lds)
 {
@@ -208,7 +223,9 @@ pooled_attn_bwd1_kernel(const float *__restrict__ q, const float *__restrict__ k
         for (int p = 0; p < g.P; ++p) {
             const float *kp = sK + p * HD2 + HD * r;
             const float s = __expf(dotv<HD>(qv, kp) - lse_r);
-            float dw = dotv<HD>(dO, sV + p * HD2 + HD * r);
+            float vrow[HD];
+            loadv<HD>(sV + p * HD2 + HD * r, vrow);
+            float dw = dot_strided<HD>(dO, vrow);                       // bit for bit backward-2's d(o) . v
             dw += dpp_quad_xor1(dw);
             const float ds = r == 0 ? dw : -lam * dw;
             const float sds = s * ds;
@@ -218,8 +235,13 @@ pooled_attn_bwd1_kernel(const float *__restrict__ q, const float *__restrict__ k
             axpyv<HD>(Vv, s, kp);
         }
         float dqv[HD];
+        {
+            // no FMA here: U - D V is a difference of two rounded sums of the same kind; fusing the product would subtract an
+            // exact D V from a rounded U and leave the rounding of U where the two cancel
+#pragma clang fp contract(off)
 #pragma unroll
-        for (int e = 0; e < HD; ++e) dqv[e] = g.scale * (U[e] - Dr * Vv[e]);
+            for (int e = 0; e < HD; ++e) dqv[e] = g.scale * (U[e] - Dr * Vv[e]);
+        }
         storev<HD>(dq + tok * dq_stride + h * HD2 + HD * r, dqv);
         float *wrow = ws + (tok * g.nh + h) * WS_PER_UNIT;
         storev<HD>(wrow + HD * r, dO);
@@ -305,7 +327,7 @@ pooled_attn_bwd2_kernel(const float *__restrict__ q, const float *__restrict__ k
         for (int tt = 0; tt < nt; ++tt) {
             const float4 st = *reinterpret_cast<const float4 *>(sS + 4 * tt);
             const float *qt = sQ + tt * HD2 + HD * r, *ot = sO + tt * HD2 + HD * r;
-            float la[4] = {0.f, 0.f, 0.f, 0.f}, da[4] = {0.f, 0.f, 0.f, 0.f};
+            float la[4] = {0.f, 0.f, 0.f, 0.f};
             float qv[HD], ov[HD];
 #pragma unroll
             for (int e = 0; e < HD; e += 4) {
@@ -317,14 +339,20 @@ pooled_attn_bwd2_kernel(const float *__restrict__ q, const float *__restrict__ k
 #pragma unroll
             for (int e = 0; e < HD; e += 4)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { la[j] += qv[e + j] * kr[e + j]; da[j] += ov[e + j] * vh[e + j]; }
+                for (int j = 0; j < 4; ++j) la[j] += qv[e + j] * kr[e + j];
             const float l = (la[0] + la[1]) + (la[2] + la[3]);          // this lane's map logit
-            float dw = (da[0] + da[1]) + (da[2] + da[3]);
+            float dw = dot_strided<HD>(ov, vh);                         // bit for bit backward-1's d(o) . v
             dw += dpp_quad_xor1(dw);                                          // d(o) . v over all 48 channels
             const float s = __expf(l - (r ? st.y : st.x));
             const float so = dpp_quad_xor1(s);
             const float w = r ? so - lam * s : s - lam * so;             // s1 - lam s2 on both lanes
-            const float dl = r ? s * (-lam * dw - st.w) : s * (dw - st.z);   // dL/d(logit of this lane's map)
+            float dl;                                                    // dL/d(logit of this lane's map) = s (ds - D)
+            {
+                // ds rounded as backward-1 rounded it before it summed D (no FMA of -lam dw with D): the difference is then exact
+#pragma clang fp contract(off)
+                const float ds = r ? -lam * dw : dw;
+                dl = s * (ds - (r ? st.w : st.z));
+            }
 #pragma unroll
             for (int e = 0; e < HD; ++e) {
                 dk[e] += dl * qv[e];        // q tile is pre-scaled: d(logit)/dk = scaled q row
