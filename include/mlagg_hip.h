@@ -879,6 +879,7 @@ int mlagg_surface_reduce(const unsigned char *codes, const int *ft, const long l
  *                     >= 0.5, 0 where none is or outside.
  *   cropped sample:   out / out_lab = the centre crop starting at ((Xi - Xo) / 2, (Yi - Yo) / 2, (Zi - Zo) / 2); needs Xo <= Xi ...
  * out (B, C, Xo, Yo, Zo) fp32, out_lab (B, 1, Xo, Yo, Zo) fp32 (required with lab).  All contiguous.  No atomics: bit-reproducible.
+ * C = 0 with lab: labels only (vol and out are not read or written, and may be NULL): a further seg channel of the same batch.
  * ------------------------------------------------------------------------------------------ */
 int mlagg_aug3d_resample(const float *vol, const short *lab, int B, int C, int Xi, int Yi, int Zi, const double *affine,
                          const int *resample, float *out, float *out_lab, int Xo, int Yo, int Zo, void *stream);
@@ -980,6 +981,56 @@ int mlagg_dice_bce_stats(const float *logits, const float *target, const unsigne
                          float *sums, float *workspace, int B, int R, long HW, int ignore_label, void *stream);
 int mlagg_dice_bce_grad(const float *logits, const float *target, const unsigned int *member, const float *g_ip, const float *g_bce,
                         float *dlogits, int B, int R, long HW, int ignore_label, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K30: the cascade training transforms on bit planes (reference training/data_augmentation/custom_transforms/cascade_transforms.py,
+ * as nnUNetTrainer.get_training_transforms chains them, nnUNetTrainer.py:703-718).  A plane is (X, Y, W) 64-bit words, W =
+ * ceil(Z / 64): bit k of word w of row (x, y) is voxel (x, y, 64 w + k).  The padding bits of a row's last word are 0 on input and
+ * on output of every entry.  X * Y * Z <= 2^31 - 1.  Integer atomics only: every result is independent of the schedule.
+ *
+ * mlagg_cascade_pack: MoveSegAsOneHotToData (cascade_transforms.py:23-31) without the fp32 one-hot.  seg: B label maps (X, Y, Z) of
+ *   elem_bytes 2 (int16) or 4 (fp32), sample b at seg + b * sample_stride elements; labels: HOST array of L <=
+ *   MLAGG_CASCADE_MAX_LABELS ints.  planes (B, L, X, Y, W): plane i = (seg == labels[i]).
+ * mlagg_cascade_unpack: planes (B, L, X, Y, W) -> out[:, c0 .. c0 + L - 1] of out (B, C_total, X, Y, Z) fp32, as 0 / 1 (:31).
+ *
+ * mlagg_cascade_morph: binary dilation / erosion with an arbitrary small footprint (ApplyRandomBinaryOperatorTransform's
+ *   skimage.morphology.binary_* calls, :118-124).  pool: n_planes planes; jobs: HOST array of n_jobs x 5 ints (source plane, destination
+ *   plane, first run, number of runs, complement), all jobs in parallel: no job's destination is a source or destination of another,
+ *   or its own source.  runs (DEVICE, n_runs_total x 4 int32): (dx, dy, lo, len) = the offsets (dx, dy, lo .. lo + len - 1), |dx|,
+ *   |dy| <= MLAGG_CASCADE_MAX_REACH, |lo| < 64, 1 <= len <= 64, lo + len <= 64: the 128 bits a lane aligns per run (a run outside that is
+ *   skipped).
+ *     complement == 0: dst[p] = OR over the offsets d of src[p + d], 0 outside the volume.  With d = -(i - c) over the set entries
+ *                      i of a footprint S (centre c = n // 2): scipy.ndimage.binary_dilation(src, S).
+ *     complement != 0: dst[p] = AND over the offsets d of src[p + d], 1 outside.  With d = i - c:
+ *                      binary_erosion(src, S, border_value=True).
+ *   Closing = the erosion of the dilation, opening = the dilation of the erosion: two calls.
+ * mlagg_cascade_commit: the "was added" rule (:126-134).  jobs: HOST array of n_jobs x 3 ints (result plane, target plane, first
+ *   plane of the target's sample), one job per sample: the target takes the result, and result & ~(the target before) is cleared
+ *   in the other L - 1 planes first .. first + L - 1.  The result plane lies outside the sample.
+ *
+ * mlagg_cascade_cc_stats: RemoveRandomConnectedComponentFromOneHotEncodingTransform's labelling (:65-72) of P <= 65535 planes, 26-
+ *   connected.  parent (P x X Y Z int32) = the minimum linear index of the voxel's component (its rank among the roots is skimage's
+ *   label order), -1 where the plane is 0; size (P x X Y Z int32) = at a root its component's voxel count; blockcnt (P x
+ *   mlagg_cascade_cc_blocks(X, Y, Z) int32) workspace; table (P x 2 int32, DEVICE) = (plane non-empty, number of components with
+ *   (double)size < thresh).  Five launches.
+ * mlagg_cascade_cc_remove: with the arrays of mlagg_cascade_cc_stats and the same thresh: rank (DEVICE, P int32) = per plane -1 or k:
+ *   the k-th component with size < thresh in root order is cleared (:77-78); fill (DEVICE, P int32): when non-zero, the same voxels
+ *   are set in plane p + fill[p] (:79-83).  target (P int32) workspace.  Two launches.
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_CASCADE_MAX_LABELS 64
+#define MLAGG_CASCADE_MAX_REACH 8
+int mlagg_cascade_pack(const void *seg, int elem_bytes, long long sample_stride, int B, int X, int Y, int Z, const int *labels, int L,
+                       unsigned long long *planes, void *stream);
+int mlagg_cascade_unpack(const unsigned long long *planes, int B, int L, int X, int Y, int Z, float *out, int C_total, int c0,
+                         void *stream);
+int mlagg_cascade_morph(unsigned long long *pool, int n_planes, int X, int Y, int Z, const int *runs, int n_runs_total, const int *jobs,
+                        int n_jobs, void *stream);
+int mlagg_cascade_commit(unsigned long long *pool, int n_planes, int X, int Y, int Z, int L, const int *jobs, int n_jobs, void *stream);
+size_t mlagg_cascade_cc_blocks(int X, int Y, int Z);
+int mlagg_cascade_cc_stats(const unsigned long long *planes, int P, int X, int Y, int Z, double thresh, int *parent, int *size,
+                           int *blockcnt, int *table, void *stream);
+int mlagg_cascade_cc_remove(unsigned long long *planes, int P, int X, int Y, int Z, double thresh, const int *parent, const int *size,
+                            const int *blockcnt, const int *rank, const int *fill, int *target, void *stream);
 
 #ifdef __cplusplus
 }

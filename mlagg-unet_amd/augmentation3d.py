@@ -12,10 +12,15 @@ Parameters are drawn on the host in batchgenerators' 3-D order (`draw_params_3d`
   * SimulateLowResolution: nearest-exact down-sampling, 12-voxel edge padding, prefilter, K25 with a diagonal affine on the
     half-pixel grid, clip to the small image's range.
   * Noise, brightness, contrast, both gammas (reductions over the three spatial axes) and mirroring on (0, 1, 2): torch.
-CPU tensors take a torch composition of the same arithmetic (the sampler as one gather of all taps), for tests at small sizes.
+  * The cascade transforms of a 3d_cascade_fullres configuration (B:703-718, `GpuAugmenter3D(cascade_labels=...)`): the previous
+    stage's segmentation travels as a second seg channel through the spatial transform and the mirroring, then K30
+    (csrc/cascade_aug.hip) packs its one-hot channels into bit planes, applies the drawn binary morphology with skimage's ball
+    footprints and the "was added" rule, removes the drawn connected components and writes the planes as fp32 input channels.
+CPU tensors take a torch composition of the same arithmetic (the sampler as one gather of all taps; scipy.ndimage for the cascade
+transforms), for tests at small sizes.
 
-Out of scope: dummy-2-D augmentation of anisotropic patches (NotImplementedError), the cascade / region / mask transforms
-(B:697-727), as in the 2-D augmenter.
+Out of scope: dummy-2-D augmentation of anisotropic patches (NotImplementedError), the region / mask transforms (B:697-699,
+B:722-726), as in the 2-D augmenter.
 """
 import math
 
@@ -142,8 +147,19 @@ def _prefiltered(data, do):
 
 
 def spatial_transform_3d(data, seg, patch_size, p, labels=None):
-    """augment_spatial, 3-D, with the nnU-Net arguments: data (B, C, Xi, Yi, Zi) fp32, seg (B, 1, Xi, Yi, Zi) (int16 on the
-    device path; any integral-valued type on the host) -> (B, C, *patch) fp32 and (B, 1, *patch) fp32 labels."""
+    """augment_spatial, 3-D, with the nnU-Net arguments: data (B, C, Xi, Yi, Zi) fp32, seg (B, S, Xi, Yi, Zi) (int16 on the
+    device path; any integral-valued type on the host) -> (B, C, *patch) fp32 and (B, S, *patch) fp32 labels.  Every seg channel
+    is resampled with the same affines and the same indicator rule (`labels` names the values of channel 0 on the host path)."""
+    if seg.shape[1] > 1:
+        out_d, first = spatial_transform_3d(data, seg[:, :1], patch_size, p, labels)
+        if data.is_cuda:                                              # K25 without a volume: the labels only
+            from . import ops
+            A, do = affines(p, tuple(data.shape[2:]), tuple(int(v) for v in patch_size))
+            rest = [ops.aug3d_resample(None, seg[:, c:c + 1].to(torch.int16).contiguous(), A, do, patch_size)[1]
+                    for c in range(1, seg.shape[1])]
+        else:
+            rest = [spatial_transform_3d(data[:, :1], seg[:, c:c + 1], patch_size, p)[1] for c in range(1, seg.shape[1])]
+        return out_d, torch.cat([first] + rest, 1)
     in_shape, out_shape = tuple(data.shape[2:]), tuple(int(v) for v in patch_size)
     A, do = affines(p, in_shape, out_shape)
     vol = _prefiltered(data.contiguous(), do)
@@ -207,13 +223,250 @@ def simulate_low_resolution_3d(data, do, zoom):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# the cascade transforms (cascade_transforms.py; B:703-718 and B:744-745)
+# ------------------------------------------------------------------------------------------------
+CASCADE_OPERATIONS = ("dilation", "erosion", "closing", "opening")      # any_of_these of ApplyRandomBinaryOperatorTransform (:92)
+
+
+def ball(radius):
+    """skimage.morphology.ball(radius) as a boolean array: n = 2 r + 1 points per axis on [-r, r] (mgrid truncates n), set where
+    x^2 + y^2 + z^2 <= r^2.  skimage's own when it is importable."""
+    try:
+        from skimage.morphology import ball as skimage_ball
+        return np.asarray(skimage_ball(radius)).astype(bool)
+    except ImportError:
+        n = 2 * radius + 1
+        Z, Y, X = np.mgrid[-radius:radius:n * 1j, -radius:radius:n * 1j, -radius:radius:n * 1j]
+        return (X ** 2 + Y ** 2 + Z ** 2) <= radius * radius
+
+
+def draw_cascade_params(rng, batch, n_labels, order, p_per_sample=0.4, p_per_label=1.0, strel_size=(1, 8)):
+    """The draws of ApplyRandomBinaryOperatorTransform.__call__ (cascade_transforms.py:111-119), which do not depend on the data:
+    per sample uniform() < p_per_sample, then shuffle(order) IN PLACE (the caller keeps `order`, a list of the n_labels plane
+    indices, across batches as the transform keeps self.channel_idx), then per channel in that order uniform() < p_per_label,
+    choice(4) over CASCADE_OPERATIONS and uniform(*strel_size).  Returns per sample the list of (plane, operation, radius)."""
+    if sorted(order) != list(range(n_labels)):
+        raise RuntimeError(f"order {list(order)}: a permutation of the {n_labels} plane indices expected")
+    params = []
+    for _ in range(batch):
+        steps = []
+        if rng.uniform() < p_per_sample:
+            rng.shuffle(order)
+            for c in order:
+                if rng.uniform() < p_per_label:
+                    operation = int(rng.choice(len(CASCADE_OPERATIONS)))
+                    steps.append((int(c), operation, float(rng.uniform(*strel_size))))
+        params.append(steps)
+    return params
+
+
+def _footprint(strel):
+    """A step's third entry: a radius (skimage's ball) or the footprint itself."""
+    return ball(float(strel)) if np.ndim(strel) == 0 else np.asarray(strel).astype(bool)
+
+
+def binary_operation_host(mask, operation, footprint):
+    """skimage.morphology.binary_dilation / erosion / closing / opening as scipy.ndimage calls (closing = erosion of the dilation,
+    opening = dilation of the erosion, erosion with border_value True)."""
+    from scipy import ndimage as ndi
+    dilate = lambda m: ndi.binary_dilation(m, structure=footprint)                             # noqa: E731
+    erode = lambda m: ndi.binary_erosion(m, structure=footprint, border_value=True)            # noqa: E731
+    return (dilate, erode, lambda m: erode(dilate(m)), lambda m: dilate(erode(m)))[operation](mask)
+
+
+def _cascade_host(seg_prev, labels, params, rng, p_per_sample, fill_p, frac, p_per_label):
+    """(B, X, Y, Z) integral label maps -> (B, L, X, Y, Z) boolean one-hot channels after both transforms, literally."""
+    from scipy import ndimage as ndi
+    onehot = np.stack([seg_prev == lab for lab in labels], 1)
+    B, L = onehot.shape[:2]
+    for b in range(B):
+        for c, operation, strel in params[b]:
+            workon = onehot[b, c].copy()
+            if not workon.any():
+                continue
+            res = binary_operation_host(workon, operation, _footprint(strel))
+            onehot[b, c] = res
+            added = res & ~workon
+            for oc in range(L):
+                if oc != c:
+                    onehot[b, oc] &= ~added
+    num_voxels = np.prod(onehot.shape[2:], dtype=np.uint64)
+    for b in range(B):
+        if rng.uniform() < p_per_sample:
+            for c in range(L):
+                if rng.uniform() < p_per_label:
+                    workon = onehot[b, c]
+                    if not workon.any():
+                        continue
+                    lab, n = ndi.label(workon, structure=np.ones((3, 3, 3)))
+                    sizes = np.bincount(lab.ravel(), minlength=n + 1)[1:]
+                    valid = [i + 1 for i in range(n) if sizes[i] < num_voxels * frac]
+                    if len(valid) > 0:
+                        component = lab == valid[rng.choice(len(valid))]
+                        workon[component] = False
+                        if rng.uniform() < fill_p:
+                            other = [i for i in range(L) if i != c]
+                            if len(other) > 0:
+                                onehot[b, rng.choice(other)][component] = True
+    return onehot
+
+
+def cascade_plan(params):
+    """The host half of the morphology: per sample the steps as (plane, holds its centre, [(kind, first run, runs), ...]) and the
+    run table (a list of (dx, dy, lo, len)) of every distinct (footprint, kind) among them."""
+    from . import ops
+    table, where, todo = [], {}, []
+    for steps in params:
+        todo.append([])
+        for c, operation, strel in steps:
+            S = _footprint(strel)
+            parts = {"dilation": (0,), "erosion": (1,), "closing": (0, 1), "opening": (1, 0)}[CASCADE_OPERATIONS[operation]]
+            sig = (S.shape, S.tobytes())
+            for kind in parts:
+                if sig + (kind,) not in where:
+                    runs = ops.cascade_footprint_runs(S, kind)
+                    where[sig + (kind,)] = (len(table), len(runs))
+                    table += runs
+            todo[-1].append((int(c), bool(S[tuple(n // 2 for n in S.shape)]), [(kind,) + where[sig + (kind,)] for kind in parts]))
+    return todo, table
+
+
+def _cascade_device(seg_prev, labels, params, rng, p_per_sample, fill_p, frac, p_per_label):
+    """The same on bit planes (K30): returns (planes (B, L, X, Y, W) int64, Z)."""
+    from . import ops
+    B, X, Y, Z = (int(v) for v in seg_prev.shape)
+    L, dev = len(labels), seg_prev.device
+    pool = torch.empty((B * L + 2 * B, X, Y, ops.cascade_words(Z)), dtype=torch.int64, device=dev)     # the planes, two scratch per sample
+    planes = pool[:B * L]
+    ops.cascade_pack(seg_prev, labels, out=planes.view(B, L, *pool.shape[1:]))
+    # morphology: step s of every sample in one launch sequence
+    todo, table = cascade_plan(params)
+    if table:
+        runs = torch.tensor(table, dtype=torch.int32).to(dev)
+        for s in range(max(len(t) for t in todo)):
+            first, second, commit = [], [], []
+            for b in range(B):
+                if s < len(todo[b]):
+                    c, centre, parts = todo[b][s]
+                    target, t0, t1 = b * L + c, B * L + 2 * b, B * L + 2 * b + 1
+                    # the reference skips an empty plane.  A footprint holding its centre (every ball) maps an empty plane to an
+                    # empty plane; any other is asked now, when its step is due
+                    if not centre and not bool(planes[target].any()):
+                        continue
+                    first.append((target, t0, parts[0][1], parts[0][2], parts[0][0]))
+                    if len(parts) > 1:
+                        second.append((t0, t1, parts[1][1], parts[1][2], parts[1][0]))
+                    commit.append((t1 if len(parts) > 1 else t0, target, b * L))
+            if first:
+                ops.cascade_morph(pool, Z, first, runs)
+                if second:
+                    ops.cascade_morph(pool, Z, second, runs)
+                ops.cascade_commit(pool, Z, L, commit)
+    # component removal: the host draws need (non-empty, n_valid) of a sample's planes once its p_per_sample draw has fired
+    thresh = float(np.prod((X, Y, Z), dtype=np.uint64) * frac)
+    state = None                                                      # the labelling's workspace, shared by the samples of the batch
+    for b in range(B):
+        if rng.uniform() < p_per_sample:
+            sample = planes[b * L:(b + 1) * L]
+            if fill_p == 0:                                           # independent channels: one read-back, one removal launch
+                state, stats = ops.cascade_cc_stats(sample, Z, thresh, state)
+                stats = stats.cpu().numpy()
+                rank = [-1] * L
+            for c in range(L):
+                if rng.uniform() < p_per_label:
+                    if fill_p != 0:                                   # an earlier channel's fill may have changed this plane
+                        state, one = ops.cascade_cc_stats(sample[c:c + 1], Z, thresh, state)
+                        nonempty, n_valid = (int(v) for v in one.cpu().numpy()[0])
+                    else:
+                        nonempty, n_valid = (int(v) for v in stats[c])
+                    if not nonempty or n_valid == 0:
+                        continue
+                    k = int(rng.choice(n_valid))
+                    fill = 0
+                    if rng.uniform() < fill_p:
+                        other = [i for i in range(L) if i != c]
+                        if len(other) > 0:
+                            fill = int(rng.choice(other)) - c
+                    if fill_p != 0:
+                        ops.cascade_cc_remove(sample[c:c + 1], Z, state, [k], [fill])
+                    else:
+                        rank[c] = k
+            if fill_p == 0 and max(rank) >= 0:
+                ops.cascade_cc_remove(sample, Z, state, rank)
+    return planes.view(B, L, *pool.shape[1:]), Z
+
+
+def _label_map(seg_prev):
+    """(B, 1, X, Y, Z) or (B, X, Y, Z) -> (B, X, Y, Z)"""
+    if seg_prev.ndim == 5:
+        if seg_prev.shape[1] != 1:
+            raise RuntimeError(f"seg_prev {tuple(seg_prev.shape)}: one channel expected")
+        seg_prev = seg_prev[:, 0]
+    if seg_prev.ndim != 4:
+        raise RuntimeError(f"seg_prev {tuple(seg_prev.shape)}: (B, 1, X, Y, Z) or (B, X, Y, Z) expected")
+    return seg_prev
+
+
+def _append_channels(data, onehot):
+    if isinstance(data, torch.Tensor):
+        return torch.cat([data, torch.as_tensor(onehot).to(data.dtype)], 1)
+    return np.concatenate([data, onehot.astype(data.dtype)], 1)
+
+
+def cascade_transforms(data, seg_prev, labels, params, rng, p_per_sample=0.2, fill_with_other_class_p=0.0,
+                       dont_do_if_covers_more_than_x_percent=0.15, p_per_label=1.0):
+    """MoveSegAsOneHotToData(1, labels), ApplyRandomBinaryOperatorTransform with the drawn `params` (draw_cascade_params; a step's
+    third entry may be a footprint instead of a radius) and RemoveRandomConnectedComponentFromOneHotEncodingTransform with the
+    trainer's arguments (B:705-718), whose draws are taken from `rng` in the reference's order.  data (B, C, X, Y, Z), seg_prev
+    (B, 1, X, Y, Z) or (B, X, Y, Z): the previous stage's labels -> data (B, C + L, X, Y, Z).  CUDA tensors run K30; CPU tensors and
+    numpy arrays run scipy.ndimage."""
+    labels = [int(v) for v in labels]
+    seg_prev = _label_map(seg_prev)
+    if len(params) != data.shape[0] or tuple(seg_prev.shape) != (data.shape[0], *data.shape[2:]):
+        raise RuntimeError(f"cascade_transforms: data {tuple(data.shape)}, seg_prev {tuple(seg_prev.shape)}, {len(params)} parameter lists")
+    args = (labels, params, rng, float(p_per_sample), float(fill_with_other_class_p), float(dont_do_if_covers_more_than_x_percent),
+            float(p_per_label))
+    if isinstance(data, torch.Tensor) and data.is_cuda:
+        return _append_planes(data, *_cascade_device(_device_labels(seg_prev), *args))
+    host = seg_prev.numpy() if isinstance(seg_prev, torch.Tensor) else np.asarray(seg_prev)
+    return _append_channels(data, _cascade_host(host, *args))
+
+
+def _device_labels(seg_prev):
+    return seg_prev if seg_prev.dtype in (torch.int16, torch.float32) else seg_prev.to(torch.float32)
+
+
+def _append_planes(data, planes, Z):
+    """data (B, C, X, Y, Z) and planes (B, L, X, Y, W) -> the fp32 network input (B, C + L, X, Y, Z)"""
+    from . import ops
+    C = data.shape[1]
+    out = torch.empty((data.shape[0], C + planes.shape[1], *data.shape[2:]), dtype=torch.float32, device=data.device)
+    out[:, :C] = data
+    return ops.cascade_unpack(planes, Z, out, C)
+
+
+def move_seg_as_one_hot(data, seg, labels):
+    """MoveSegAsOneHotToData(1, labels, "seg", "data") of the validation chain (get_validation_transforms, B:744-745): seg (B, 2, ...)
+    -> (data (B, C + L, ...), seg (B, 1, ...))."""
+    if seg.ndim != 5 or seg.shape[1] != 2:
+        raise RuntimeError(f"move_seg_as_one_hot: seg {tuple(seg.shape)}: the target and the previous stage's segmentation expected")
+    labels = [int(v) for v in labels]
+    prev = seg[:, 1]
+    if isinstance(data, torch.Tensor) and data.is_cuda:
+        from . import ops
+        return _append_planes(data, ops.cascade_pack(_device_labels(prev), labels), prev.shape[-1]), seg[:, :1]
+    host = prev.numpy() if isinstance(prev, torch.Tensor) else np.asarray(prev)
+    return _append_channels(data, np.stack([host == lab for lab in labels], 1)), seg[:, :1]
+
+
 class GpuAugmenter3D:
     """(loader batch on the device) -> augmented (data, seg): the reference's 3-D training transform chain behind
     `dataloading.DataLoader3D`.  `patch_size`: the network's; the loader delivers `initial_patch_size()`."""
 
     takes_int16_seg = True                      # dataloading.to_device hands over the loader's int16 labels as they are
 
-    def __init__(self, patch_size, device, rotation=None, mirror_axes=(0, 1, 2), seed=None, labels=None):
+    def __init__(self, patch_size, device, rotation=None, mirror_axes=(0, 1, 2), seed=None, labels=None, cascade_labels=None):
         self.patch_size = tuple(int(v) for v in patch_size)
         if len(self.patch_size) != 3:
             raise RuntimeError(f"GpuAugmenter3D: a 3-D patch, got {self.patch_size}")
@@ -223,13 +476,21 @@ class GpuAugmenter3D:
         # every value the loader's segmentation can hold (label_manager.all_labels and the -1 padding), ascending (host path)
         self.labels = None if labels is None else torch.tensor(sorted(set(labels) | {-1}), dtype=torch.float32)
         self.rng = np.random.RandomState(seed)
+        # 3d_cascade_fullres: the foreground labels of the previous stage's segmentation, the loader's second seg channel
+        self.cascade_labels = None if cascade_labels is None else tuple(int(v) for v in cascade_labels)
+        self.cascade_order = None if cascade_labels is None else list(range(len(self.cascade_labels)))
 
     def initial_patch_size(self):
         """get_patch_size with the rotation ranges and the (0.85, 1.25) scale range of B:389-391."""
         return tuple(int(v) for v in get_patch_size(self.patch_size, *self.rotation, (0.85, 1.25)))
 
-    def apply(self, data, seg, p, noise=None):
-        """The transform chain with given parameters (`draw_params_3d` layout); data (B, C, Xi, Yi, Zi) fp32, seg (B, 1, Xi, Yi, Zi)."""
+    def apply(self, data, seg, p, noise=None, cascade=None, rng=None):
+        """The transform chain with given parameters (`draw_params_3d` layout); data (B, C, Xi, Yi, Zi) fp32, seg (B, 1, Xi, Yi, Zi).
+        With `cascade_labels`: seg (B, 2, Xi, Yi, Zi), `cascade` the draw_cascade_params lists, `rng` the stream of the component
+        removal's draws (the augmenter's own by default); returns data (B, C + L, *patch) and the one-channel target."""
+        if (self.cascade_labels is not None) != (seg.shape[1] == 2) or seg.shape[1] > 2:
+            raise RuntimeError(f"GpuAugmenter3D: seg {tuple(seg.shape)} with cascade_labels {self.cascade_labels}: the previous "
+                               "stage's segmentation is the second seg channel of a cascade batch, and of no other")
         dev = data.device
         T = lambda a, dt=torch.float32: torch.as_tensor(np.asarray(a), device=dev).to(dt)      # noqa: E731
         data, seg = spatial_transform_3d(data, seg, self.patch_size, p, self.labels)
@@ -245,14 +506,24 @@ class GpuAugmenter3D:
         data = simulate_low_resolution_3d(data, p["lowres_ch"] & p["do_lowres"][:, None], p["lowres_zoom"])
         data = gamma_transform(data, T(p["do_gamma_inv"], torch.bool), T(p["gamma_inv"]), invert=True)
         data = gamma_transform(data, T(p["do_gamma"], torch.bool), T(p["gamma"]), invert=False)
-        return mirror_transform(data, seg, T(p["mirror"], torch.bool))
+        data, seg = mirror_transform(data, seg, T(p["mirror"], torch.bool))
+        if self.cascade_labels is None:
+            return data, seg
+        if cascade is None:
+            raise RuntimeError("GpuAugmenter3D.apply: a cascade augmenter needs the draw_cascade_params lists")
+        # RemoveLabelTransform(-1, 0) (B:701) changes no plane: no listed label is -1 or 0
+        data = cascade_transforms(data, seg[:, 1], self.cascade_labels, cascade, self.rng if rng is None else rng)
+        return data, seg[:, :1]
 
     def clone(self, seed):
-        """The same chain with its own parameter stream (one per loader worker)."""
-        twin = GpuAugmenter3D(self.patch_size, self.device, self.rotation, self.mirror_axes, seed)
+        """The same chain with its own parameter stream (one per loader worker) and its own channel order."""
+        twin = GpuAugmenter3D(self.patch_size, self.device, self.rotation, self.mirror_axes, seed, cascade_labels=self.cascade_labels)
         twin.labels = self.labels
         return twin
 
     def __call__(self, data, seg):
         p = draw_params_3d(self.rng, data.shape[0], data.shape[1], self.rotation, self.mirror_axes)
-        return self.apply(data, seg, p)
+        if self.cascade_labels is None:
+            return self.apply(data, seg, p)
+        cascade = draw_cascade_params(self.rng, data.shape[0], len(self.cascade_labels), self.cascade_order)
+        return self.apply(data, seg, p, cascade=cascade)

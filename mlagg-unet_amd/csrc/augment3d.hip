@@ -149,8 +149,8 @@ __global__ void __launch_bounds__(A3_BLOCK) aug3d_resample_kernel(const float *_
 extern "C" int mlagg_aug3d_resample(const float *vol, const short *lab, int B, int C, int Xi, int Yi, int Zi, const double *affine,
                                     const int *resample, float *out, float *out_lab, int Xo, int Yo, int Zo, void *stream)
 {
-    if (!vol || !out || !affine || !resample || (lab && !out_lab)) return MLAGG_E_NULLPTR;
-    if (B < 1 || C < 1 || Xi < 1 || Yi < 1 || Zi < 1 || Xo < 1 || Yo < 1 || Zo < 1) return MLAGG_E_UNSUPPORTED;
+    if ((C > 0 && (!vol || !out)) || !affine || !resample || (lab && !out_lab)) return MLAGG_E_NULLPTR;
+    if (B < 1 || C < 0 || (C == 0 && !lab) || Xi < 1 || Yi < 1 || Zi < 1 || Xo < 1 || Yo < 1 || Zo < 1) return MLAGG_E_UNSUPPORTED;
     for (int b = 0; b < B; ++b)                            // a cropped sample reads the centre of its input
         if (!resample[b] && (Xo > Xi || Yo > Yi || Zo > Zi)) return MLAGG_E_UNSUPPORTED;
     if ((long long)A3_MAX_B * Xo * Yo * Zo > (1LL << 38)) return MLAGG_E_UNSUPPORTED;

@@ -14,7 +14,11 @@ batches bit for bit -- but
 `DataLoader3D` is the reference's nnUNetDataLoader3D (training/dataloading/data_loader_3d.py:7-52 on get_bbox,
 base_data_loader.py:63-139) on the same case folder and pinned buffers; `to_device` / `PrefetchLoader` take the trainer's
 per-axis deep-supervision scales for its batches (`ds_scales`).  The augmentation transforms live in augmentation.py (2-D)
-and augmentation3d.py (3-D)."""
+and augmentation3d.py (3-D).
+
+A cascade's second stage (3d_cascade_fullres) gives `Dataset` the folder with the previous stage's predictions
+(nnunet_dataset.py:48-49, 104-109): every case then has a second seg channel, which the loaders crop with the same box and
+pad with -1, and which augmentation3d turns into one-hot input channels on the device."""
 import os
 import pickle
 import queue
@@ -24,15 +28,39 @@ import numpy as np
 import torch
 
 
+class _SegChannels:
+    """np.vstack((seg, seg_prev[None])) (nnunet_dataset.py:109) for arrays that are only read through crops: the index is
+    applied to both parts, so a memory-mapped case is not copied as a whole."""
+
+    def __init__(self, seg, prev):
+        if tuple(prev.shape) != tuple(seg.shape[1:]):
+            raise RuntimeError(f"segmentation of the previous stage {tuple(prev.shape)} does not match the case {tuple(seg.shape)}")
+        self.parts = (seg, prev[None])
+        self.shape, self.dtype, self.ndim = (seg.shape[0] + 1, *seg.shape[1:]), seg.dtype, seg.ndim
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, idx):
+        idx = idx if isinstance(idx, tuple) else (idx,)
+        return np.concatenate([p[(slice(None),) + idx[1:]] for p in self.parts], 0)[idx[0]]
+
+    def __array__(self, dtype=None, copy=None):
+        out = np.concatenate(self.parts, 0)
+        return out if dtype is None else out.astype(dtype)
+
+
 class Dataset:
     """Case folder index (reference nnUNetDataset).  Properties (.pkl) are read once and cached: they hold the sampled
-    foreground locations used for every oversampled patch."""
+    foreground locations used for every oversampled patch.  `folder_with_segs_from_previous_stage`: the cascade's
+    predicted_next_stage/<configuration> folder; its <case>.npz['seg'] (or unpacked <case>.npy) becomes a second seg channel."""
 
-    def __init__(self, folder, case_identifiers=None):
+    def __init__(self, folder, case_identifiers=None, folder_with_segs_from_previous_stage=None):
+        self.prev_folder = folder_with_segs_from_previous_stage
         ids = case_identifiers if case_identifiers is not None else \
             [i[:-4] for i in os.listdir(folder) if i.endswith("npz") and i.find("segFromPrevStage") == -1]
         self.folder, self.ids = folder, sorted(ids)
-        self._props, self._open = {}, {}
+        self._props, self._open, self._prev = {}, {}, {}
         if not self.ids:
             raise RuntimeError(f"no <case>.npz in {folder}")
 
@@ -50,15 +78,26 @@ class Dataset:
 
     def arrays(self, key):
         """(data (C, D, H, W), seg (1, D, H, W)): memory maps of the unpacked .npy files when they exist (kept open),
-        else the decompressed .npz members."""
+        else the decompressed .npz members.  With a previous-stage folder seg is (2, D, H, W) (nnunet_dataset.py:104-109)."""
         if key not in self._open:
             base = os.path.join(self.folder, key)
             if os.path.isfile(base + ".npy") and os.path.isfile(base + "_seg.npy"):
                 self._open[key] = (np.load(base + ".npy", "r"), np.load(base + "_seg.npy", "r"))
             else:
                 z = np.load(base + ".npz")
-                return z["data"], z["seg"]                    # not cached: a decompressed case can be large
-        return self._open[key]
+                return z["data"], self._with_previous_stage(key, z["seg"])    # not cached: a decompressed case can be large
+        data, seg = self._open[key]
+        return data, self._with_previous_stage(key, seg)
+
+    def _with_previous_stage(self, key, seg):
+        if self.prev_folder is None:
+            return seg
+        if key not in self._prev:
+            base = os.path.join(self.prev_folder, key)
+            if not os.path.isfile(base + ".npy"):
+                return _SegChannels(seg, np.load(base + ".npz")["seg"])
+            self._prev[key] = np.load(base + ".npy", "r")
+        return _SegChannels(seg, self._prev[key])
 
 
 class DataLoader2D:
@@ -145,6 +184,7 @@ class DataLoader2D:
         return {"data": data_t, "seg": seg_t, "keys": keys}
 
     def _check_labels(self, seg_all, keys):
+        seg_all = seg_all[:, 0]                           # the target; a cascade's second channel holds the previous stage's labels
         if self.max_label is not None and int(seg_all.max()) > self.max_label:
             # torch's nll_loss (the reference's CE) fails on a label >= C; the fused loss kernel would quietly count such a
             # pixel as "no class hit", so a corrupt case is stopped here, on the host, where the check costs nothing
@@ -232,10 +272,12 @@ def targets_from_seg(seg, n_levels=5, ds_scales=None):
     return targets
 
 
-def to_device(batch, device, n_levels=5, stream=None, augmenter=None, ds_scales=None):
+def to_device(batch, device, n_levels=5, stream=None, augmenter=None, ds_scales=None, cascade_labels=None):
     """Host batch -> (data (B, C, *spatial) fp32, [target_s (B, 1, *spatial_s) fp32 labels]) on `device`; with an
     `augmenter` (augmentation.GpuAugmenter / augmentation3d.GpuAugmenter3D) the training transforms run on the device in
-    between.  2-D: n_levels halvings; `ds_scales`: per-axis scales (targets_from_seg), for 3-D batches."""
+    between.  2-D: n_levels halvings; `ds_scales`: per-axis scales (targets_from_seg), for 3-D batches.  A cascade batch
+    (two seg channels) goes through an augmenter built with `cascade_labels`, or, without an augmenter (validation), through
+    augmentation3d.move_seg_as_one_hot with the `cascade_labels` given here: data gains one input channel per label."""
     device = torch.device(device)
     ctx = torch.cuda.stream(stream) if stream is not None else _Null()
     with ctx:
@@ -245,6 +287,11 @@ def to_device(batch, device, n_levels=5, stream=None, augmenter=None, ds_scales=
         seg = seg if getattr(augmenter, "takes_int16_seg", False) else seg.float()
         if augmenter is not None:
             data, seg = augmenter(data, seg)
+        elif seg.shape[1] == 2:
+            if cascade_labels is None:
+                raise RuntimeError("to_device: a cascade batch (two seg channels) needs an augmenter or cascade_labels")
+            from .augmentation3d import move_seg_as_one_hot
+            data, seg = move_seg_as_one_hot(data, seg, cascade_labels)
         targets = targets_from_seg(seg.float(), n_levels, ds_scales)
     return data, targets
 
@@ -262,7 +309,9 @@ class PrefetchLoader:
     (numpy's slicing / copies release the GIL); batches arrive on the device through a side stream, and `next()` makes the
     caller's current stream wait for that copy only."""
 
-    def __init__(self, loader, device, num_workers=4, depth=6, seed=1234, n_levels=5, augmenter=None, ds_scales=None):
+    def __init__(self, loader, device, num_workers=4, depth=6, seed=1234, n_levels=5, augmenter=None, ds_scales=None,
+                 cascade_labels=None):
+        self.cascade_labels = cascade_labels
         self.device = torch.device(device)
         self.q = queue.Queue(maxsize=depth)
         self.stop = threading.Event()
@@ -282,11 +331,12 @@ class PrefetchLoader:
             try:
                 b = loader.generate_train_batch()
                 if self.copy_stream is not None:
-                    data, targets = to_device(b, self.device, self.n_levels, self.copy_stream, augmenter, self.ds_scales)
+                    data, targets = to_device(b, self.device, self.n_levels, self.copy_stream, augmenter, self.ds_scales,
+                                              self.cascade_labels)
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
                 else:
-                    data, targets = to_device(b, self.device, self.n_levels, None, augmenter, self.ds_scales)
+                    data, targets = to_device(b, self.device, self.n_levels, None, augmenter, self.ds_scales, self.cascade_labels)
                     ev = None
                 item = (data, targets, ev, b)                 # keep the pinned host batch alive until consumed
             except BaseException as e:                        # missing .pkl, bad .npz, out of memory on the copy stream ...

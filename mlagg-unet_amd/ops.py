@@ -3210,9 +3210,15 @@ def surface_reduce(state, tol, area, spacing, pairs_total=None):
 def aug3d_resample(vol, lab, affine, resample, out_shape):
     """vol (B, C, Xi, Yi, Zi) fp32 (spline coefficients of the resampled samples, raw data of the cropped ones), lab (B, 1, Xi, Yi, Zi)
     int16 or None, affine (B, 3, 4) float64 host array (output voxel index -> input coordinate), resample (B,) host bools ->
-    (out (B, C, *out_shape) fp32, out_lab (B, 1, *out_shape) fp32 or None).  See include/mlagg_hip.h, K25."""
-    _expect(vol, "vol", dim=5)
-    B, C, Xi, Yi, Zi = (int(v) for v in vol.shape)
+    (out (B, C, *out_shape) fp32, out_lab (B, 1, *out_shape) fp32 or None).  vol None with lab: the labels only (a further seg
+    channel of a batch whose volume is already resampled), out is None.  See include/mlagg_hip.h, K25."""
+    if vol is None:
+        _expect(lab, "lab", torch.int16, dim=5)
+        B, C, (Xi, Yi, Zi) = int(lab.shape[0]), 0, (int(v) for v in lab.shape[2:])
+        vol = lab                                         # shape and device of the checks below
+    else:
+        _expect(vol, "vol", dim=5)
+        B, C, Xi, Yi, Zi = (int(v) for v in vol.shape)
     Xo, Yo, Zo = (int(v) for v in out_shape)
     if min(Xo, Yo, Zo) < 1:
         raise RuntimeError(f"aug3d_resample: output shape {tuple(out_shape)}")
@@ -3224,9 +3230,9 @@ def aug3d_resample(vol, lab, affine, resample, out_shape):
         raise RuntimeError(f"aug3d_resample: {rs.shape[0]} resample flags for {B} samples")
     if (~rs).any() and (Xo > Xi or Yo > Yi or Zo > Zi):
         raise RuntimeError(f"aug3d_resample: a cropped sample needs an input ({Xi}, {Yi}, {Zi}) at least the output ({Xo}, {Yo}, {Zo})")
-    out = torch.empty((B, C, Xo, Yo, Zo), device=vol.device, dtype=torch.float32)
+    out = torch.empty((B, C, Xo, Yo, Zo), device=vol.device, dtype=torch.float32) if C else None
     out_lab = torch.empty((B, 1, Xo, Yo, Zo), device=vol.device, dtype=torch.float32) if lab is not None else None
-    _launch("mlagg_aug3d_resample", _ptr(vol), _ptr(lab), B, C, Xi, Yi, Zi, A.ctypes.data, _int_array(rs.astype(int)), _ptr(out),
+    _launch("mlagg_aug3d_resample", _ptr(vol) if C else None, _ptr(lab), B, C, Xi, Yi, Zi, A.ctypes.data, _int_array(rs.astype(int)), _ptr(out),
             _ptr(out_lab), Xo, Yo, Zo)
     return out, out_lab
 
@@ -3401,3 +3407,149 @@ def label_confusion(reference, prediction, table, n_labels, ignore_label=None):
     counts = torch.empty((L + 1, L + 1), dtype=torch.int64, device=reference.device)
     _launch("mlagg_label_confusion", _ptr(reference), _ptr(prediction), reference.numel(), _ptr(table), L, ignore, _ptr(counts))
     return counts
+
+
+# ------------------------------------------------------------------------------------------------
+# K30: the cascade training transforms on bit planes (csrc/cascade_aug.hip; augmentation3d.cascade_transforms composes them).
+# A plane is (X, Y, W) int64 words, W = ceil(Z / 64): bit k of word w is voxel z = 64 w + k; the padding bits are 0.
+# ------------------------------------------------------------------------------------------------
+CASCADE_MAX_LABELS = _C["MLAGG_CASCADE_MAX_LABELS"]
+CASCADE_MAX_REACH = _C["MLAGG_CASCADE_MAX_REACH"]
+CASCADE_MAX_VOXELS = 2 ** 31 - 1
+CASCADE_DILATION, CASCADE_EROSION = 0, 1
+
+
+def cascade_words(Z):
+    return (int(Z) + 63) // 64
+
+
+def _cascade_planes(planes, name, Z, dim):
+    _expect(planes, name, torch.int64, dim=dim)
+    X, Y, W = (int(v) for v in planes.shape[-3:])
+    if min(planes.shape) < 1 or W != cascade_words(Z):
+        raise RuntimeError(f"{name}: planes {tuple(planes.shape)} for Z = {Z}: {cascade_words(Z)} words per row expected")
+    if X * Y * int(Z) > CASCADE_MAX_VOXELS:
+        raise RuntimeError(f"{name}: {X * Y * int(Z)} voxels per plane, at most {CASCADE_MAX_VOXELS} are supported")
+    return X, Y, int(Z)
+
+
+def cascade_pack(seg, labels, out=None):
+    """seg (B, X, Y, Z) int16 or fp32 label maps on the device, each sample contiguous (the channel slice seg5[:, 1] of a contiguous
+    (B, 2, X, Y, Z) batch is accepted as it is); labels: L ints -> planes (B, L, X, Y, W) int64, plane i = (seg == labels[i])
+    (written into `out` when given)."""
+    if not (isinstance(seg, torch.Tensor) and seg.is_cuda and seg.dtype in (torch.int16, torch.float32) and seg.dim() == 4):
+        raise RuntimeError(f"seg: expected a (B, X, Y, Z) int16 or float32 tensor on the MI355X device, got "
+                           f"{getattr(seg, 'dtype', type(seg))} {tuple(getattr(seg, 'shape', ()))} on {getattr(seg, 'device', '?')}")
+    labels = [int(v) for v in labels]
+    B, X, Y, Z = (int(v) for v in seg.shape)
+    if min(B, X, Y, Z) < 1 or X * Y * Z > CASCADE_MAX_VOXELS:
+        raise RuntimeError(f"cascade_pack: label maps {tuple(seg.shape)}: 1 to {CASCADE_MAX_VOXELS} voxels per sample are supported")
+    if not 1 <= len(labels) <= CASCADE_MAX_LABELS:
+        raise RuntimeError(f"cascade_pack: {len(labels)} labels, 1 to {CASCADE_MAX_LABELS} are supported")
+    if not seg[0].is_contiguous() or (B > 1 and seg.stride(0) < X * Y * Z):
+        seg = seg.contiguous()
+    shape = (B, len(labels), X, Y, cascade_words(Z))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int64, device=seg.device)
+    _expect(out, "out", torch.int64, shape=shape, like=seg)
+    _launch("mlagg_cascade_pack", _ptr(seg), seg.element_size(), seg.stride(0) if B > 1 else X * Y * Z, B, X, Y, Z, _int_array(labels),
+            len(labels), _ptr(out))
+    return out
+
+
+def cascade_unpack(planes, Z, out, c0):
+    """planes (B, L, X, Y, W) -> out[:, c0:c0 + L] of the contiguous fp32 network input out (B, C, X, Y, Z), as 0 / 1."""
+    X, Y, Z = _cascade_planes(planes, "planes", Z, 5)
+    B, L = int(planes.shape[0]), int(planes.shape[1])
+    _expect(out, "out", dim=5, like=planes)
+    C, c0 = int(out.shape[1]), int(c0)
+    if tuple(out.shape) != (B, C, X, Y, Z) or c0 < 0 or c0 + L > C:
+        raise RuntimeError(f"cascade_unpack: out {tuple(out.shape)} does not take {L} planes of ({X}, {Y}, {Z}) at channel {c0}")
+    _launch("mlagg_cascade_unpack", _ptr(planes), B, L, X, Y, Z, _ptr(out), C, c0)
+    return out
+
+
+def cascade_footprint_runs(footprint, operation):
+    """The run table of one footprint S (boolean, (n0, n1, n2), each n <= 2 MAX_REACH + 1, centre n // 2) for a dilation
+    (offsets -(i - c)) or an erosion (offsets i - c): a list of (dx, dy, lo, len), one per run of set offsets along z."""
+    S = np.asarray(footprint).astype(bool)
+    if S.ndim != 3 or min(S.shape) < 1 or max(S.shape) > 2 * CASCADE_MAX_REACH + 1:
+        raise RuntimeError(f"footprint of shape {S.shape}: three axes of 1 to {2 * CASCADE_MAX_REACH + 1} entries are supported")
+    if operation not in (CASCADE_DILATION, CASCADE_EROSION):
+        raise RuntimeError(f"operation {operation!r}: CASCADE_DILATION or CASCADE_EROSION")
+    c = [n // 2 for n in S.shape]
+    edge = np.diff(np.pad(S, ((0, 0), (0, 0), (1, 1))).astype(np.int8), axis=2)       # +1 where a run starts, -1 one past its end
+    i0, i1, start = np.nonzero(edge == 1)
+    end = np.nonzero(edge == -1)[2]                                                   # the same row-major order: run for run
+    if operation == CASCADE_EROSION:
+        table = np.stack([i0 - c[0], i1 - c[1], start - c[2], end - start], 1)
+    else:                                                                             # the reflected footprint
+        table = np.stack([c[0] - i0, c[1] - i1, c[2] - (end - 1), end - start], 1)
+    return [tuple(row) for row in table.tolist()]
+
+
+def _cascade_jobs(jobs, width, what):
+    rows = [[int(v) for v in j] for j in jobs]
+    if not rows or any(len(r) != width for r in rows):
+        raise RuntimeError(f"{what}: a non-empty list of {width}-tuples expected")
+    return _int_array([v for r in rows for v in r]), len(rows)
+
+
+def cascade_morph(pool, Z, jobs, runs):
+    """pool (P, X, Y, W) planes; runs (R, 4) int32 device table of cascade_footprint_runs rows; jobs: (source plane, destination
+    plane, first run, number of runs, operation) each, all run in one launch.  See include/mlagg_hip.h, K30."""
+    X, Y, Z = _cascade_planes(pool, "pool", Z, 4)
+    _expect(runs, "runs", torch.int32, dim=2, like=pool)
+    if runs.shape[1] != 4 or runs.shape[0] < 1:
+        raise RuntimeError(f"runs: expected (R, 4) with R >= 1, got {tuple(runs.shape)}")
+    arr, n = _cascade_jobs(jobs, 5, "cascade_morph")
+    _launch("mlagg_cascade_morph", _ptr(pool), int(pool.shape[0]), X, Y, Z, _ptr(runs), int(runs.shape[0]), arr, n)
+
+
+def cascade_commit(pool, Z, n_labels, jobs):
+    """The "was added" rule: jobs (result plane, target plane, first plane of the target's sample), one per sample: the target takes
+    the result, and what the result adds to it is cleared in the sample's other n_labels - 1 planes."""
+    X, Y, Z = _cascade_planes(pool, "pool", Z, 4)
+    arr, n = _cascade_jobs(jobs, 3, "cascade_commit")
+    _launch("mlagg_cascade_commit", _ptr(pool), int(pool.shape[0]), X, Y, Z, int(n_labels), arr, n)
+
+
+def cascade_cc_stats(planes, Z, thresh, workspace=None):
+    """planes (P, X, Y, W) -> (state for cascade_cc_remove, table (P, 2) int32 device tensor: plane non-empty, number of 26-connected
+    components with size < thresh).  The state holds two int32 per voxel and plane (parent, size); `workspace`: an earlier call's
+    state whose buffers are taken over when they are large enough (that state is then void)."""
+    X, Y, Z = _cascade_planes(planes, "planes", Z, 4)
+    P, n, dev = int(planes.shape[0]), X * Y * Z, planes.device
+    if P > 65535:
+        raise RuntimeError(f"cascade_cc_stats: {P} planes, at most 65535 are supported")
+    n_blocks = int(_lib.lib().mlagg_cascade_cc_blocks(X, Y, Z))
+    if workspace is not None and workspace[0].device == dev and workspace[0].numel() >= P * n and workspace[2].numel() >= P * n_blocks:
+        parent, size = workspace[0].view(-1)[:P * n].view(P, n), workspace[1].view(-1)[:P * n].view(P, n)
+        blockcnt = workspace[2].view(-1)[:P * n_blocks].view(P, n_blocks)
+    else:
+        parent = torch.empty((P, n), dtype=torch.int32, device=dev)
+        size = torch.empty((P, n), dtype=torch.int32, device=dev)
+        blockcnt = torch.empty((P, n_blocks), dtype=torch.int32, device=dev)
+    table = torch.empty((P, 2), dtype=torch.int32, device=dev)
+    _launch("mlagg_cascade_cc_stats", _ptr(planes), P, X, Y, Z, float(thresh), _ptr(parent), _ptr(size), _ptr(blockcnt), _ptr(table))
+    return (parent, size, blockcnt, float(thresh)), table
+
+
+def cascade_cc_remove(planes, Z, state, rank, fill=None):
+    """Clears, in plane p, the rank[p]-th component with size < thresh in root order (rank[p] < 0: nothing); fill[p] != 0 sets the
+    same voxels in plane p + fill[p] (which may lie outside `planes`, in the tensor it is a view of).  rank, fill: P ints (host)."""
+    X, Y, Z = _cascade_planes(planes, "planes", Z, 4)
+    parent, size, blockcnt, thresh = state
+    P = int(planes.shape[0])
+    rank = [int(v) for v in rank]
+    fill = [0] * P if fill is None else [int(v) for v in fill]
+    if len(rank) != P or len(fill) != P or tuple(parent.shape) != (P, X * Y * Z):
+        raise RuntimeError(f"cascade_cc_remove: {len(rank)} ranks, {len(fill)} fills and a state of {tuple(parent.shape)} for {P} planes")
+    words, have = X * Y * cascade_words(Z), planes.untyped_storage().nbytes() // 8
+    for p, f in enumerate(fill):                      # the plane to fill lies in the tensor `planes` is a view of
+        if f and not 0 <= planes.storage_offset() + (p + f) * words <= have - words:
+            raise RuntimeError(f"cascade_cc_remove: fill[{p}] = {f} points outside the planes' tensor")
+    args = torch.tensor([rank, fill], dtype=torch.int32).to(planes.device)
+    target = torch.empty(P, dtype=torch.int32, device=planes.device)
+    _launch("mlagg_cascade_cc_remove", _ptr(planes), P, X, Y, Z, thresh, _ptr(parent), _ptr(size), _ptr(blockcnt), _ptr(args[0]),
+            _ptr(args[1]), _ptr(target))
