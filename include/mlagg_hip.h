@@ -885,6 +885,24 @@ int mlagg_aug3d_resample(const float *vol, const short *lab, int B, int C, int X
                          const int *resample, float *out, float *out_lab, int Xo, int Yo, int Zo, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K31: the same transform for an anisotropic patch, "dummy 2-D" augmentation (Convert3DTo2DTransform, the 2-D SpatialTransform on
+ * (B, C * X, Y, Z) and Convert2DTo3DTransform of nnUNetTrainer.get_training_transforms, nnUNetTrainer.py:658-680, chosen by
+ * do_dummy_2d_data_aug, nnUNetTrainer.py:380): every slice x is resampled in its own (y, z) plane, X is never resampled.
+ * vol (B, C, X, Yi, Zi) fp32: per sample the cubic B-spline coefficients prefiltered along Y and Z ONLY where resample[b] != 0, the
+ * raw data where it is 0.  lab (B, 1, X, Yi, Zi) int16 or NULL.  affine: HOST array of B x 6 float64, row-major 2 x 3 per sample:
+ * input y = A[0][2] + A[0][0] y + A[0][1] z, input z = A[1][2] + A[1][0] y + A[1][1] z for output pixel (y, z) of every slice and
+ * channel.  resample: HOST array of B ints.
+ *   resampled sample: out = cubic B-spline of the slice at that coordinate (16 taps, mirror-indexed), 0 where the coordinate leaves
+ *                     [0, n - 1] on either axis; out_lab = the largest label whose bilinear indicator (4 taps) is >= 0.5, 0 where
+ *                     none is or outside.  The arithmetic is K25's with the x axis removed.
+ *   cropped sample:   out / out_lab = the centre crop starting at ((Yi - Yo) / 2, (Zi - Zo) / 2) of every slice; needs Yo <= Yi ...
+ * out (B, C, X, Yo, Zo) fp32, out_lab (B, 1, X, Yo, Zo) fp32 (required with lab).  All contiguous; Yi * Zi and Yo * Zo < 2^31.
+ * No atomics: bit-reproducible.  C = 0 with lab: labels only (vol and out may be NULL), as K25.
+ * ------------------------------------------------------------------------------------------ */
+int mlagg_aug3d_resample_planar(const float *vol, const short *lab, int B, int C, int X, int Yi, int Zi, const double *affine,
+                                const int *resample, float *out, float *out_lab, int Yo, int Zo, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K27: cell-instance F1 evaluation (reference evaluation/compute_cell_metric.py: skimage.measure.label(seg == 1), dice,
  * remove_boundary_cells, relabel_sequential, _label_overlap, _intersection_over_union and the threshold test of _true_positive).
  * All maps are contiguous int32 (H, W) unless said otherwise, H * W <= 2^31 - 1, labels >= 0.  Integer atomics only: every result

@@ -1,6 +1,6 @@
 """Training-time data augmentation of the 3-D path ON the MI355X: the reference's get_training_transforms
-(nnUNetTrainer.py:645-733) for a 3-D configuration without dummy-2-D augmentation (the BTCV plan: 160 / 96 < ANISO_THRESHOLD 3),
-behind `dataloading.DataLoader3D`.
+(nnUNetTrainer.py:645-733) for a 3-D configuration, without dummy-2-D augmentation (the BTCV plan: 160 / 96 < ANISO_THRESHOLD 3) and
+with it (thick-slice plans such as ACDC's 20 x 256 x 224), behind `dataloading.DataLoader3D`.
 
 Parameters are drawn on the host in batchgenerators' 3-D order (`draw_params_3d`); the voxels stay on the device:
   * SpatialTransform (rotation of +-30 degrees about x, y and z, p_rot_per_axis 1; isotropic scale in (0.7, 1.4); p 0.2 each):
@@ -16,11 +16,16 @@ Parameters are drawn on the host in batchgenerators' 3-D order (`draw_params_3d`
     stage's segmentation travels as a second seg channel through the spatial transform and the mirroring, then K30
     (csrc/cascade_aug.hip) packs its one-hot channels into bit planes, applies the drawn binary morphology with skimage's ball
     footprints and the "was added" rule, removes the drawn connected components and writes the planes as fp32 input channels.
+  * Dummy-2-D augmentation (`GpuAugmenter3D(dummy_2d=True)`, chosen by `configure_3d` / `GpuAugmenter3D.for_plan` when
+    max(patch) / patch[0] > 3, B:380): the 2-D draws (`draw_params_dummy_2d`, one angle in +-180 degrees), the loader patch keeps
+    patch[0], the spatial transform resamples every slice in its own plane -- prefilter along Y and Z only, then K31
+    (csrc/augment3d.hip, ops.aug3d_resample_planar: 16 cubic taps, 4 bilinear label taps, X never resampled) -- and
+    SimulateLowResolution ignores axis 0 (in-plane sizes, padding and prefilter, K31 for the up-sampling, the clip still to the
+    small VOLUME's range).  Everything after the spatial transform is 3-D again and shared with the isotropic mode.
 CPU tensors take a torch composition of the same arithmetic (the sampler as one gather of all taps; scipy.ndimage for the cascade
 transforms), for tests at small sizes.
 
-Out of scope: dummy-2-D augmentation of anisotropic patches (NotImplementedError), the region / mask transforms (B:697-699,
-B:722-726), as in the 2-D augmenter.
+Out of scope: the region / mask transforms (B:697-699, B:722-726), as in the 2-D augmenter.
 """
 import math
 
@@ -66,6 +71,40 @@ def draw_params_3d(rng, batch, channels, rotation=None, mirror_axes=(0, 1, 2)):
     return A2._draw_intensity_and_mirror(rng, p, B, C, mirror_axes)
 
 
+def configure_3d(patch_size):
+    """configure_rotation_dummyDA_mirroring_and_inital_patch_size (B:378-404), 3-D branch, both cases:
+    (rotation ranges about x, y, z; do_dummy_2d; the loader's initial patch size; mirror axes)."""
+    patch_size = tuple(int(v) for v in patch_size)
+    if len(patch_size) != 3:
+        raise RuntimeError(f"configure_3d: a 3-D patch, got {patch_size}")
+    do_dummy_2d = max(patch_size) / patch_size[0] > ANISO_THRESHOLD
+    rotation = ((-math.pi, math.pi), (0, 0), (0, 0)) if do_dummy_2d else rotation_for_3d(patch_size)
+    initial = [int(v) for v in get_patch_size(patch_size, *rotation, (0.85, 1.25))]
+    if do_dummy_2d:
+        initial[0] = patch_size[0]
+    return rotation, do_dummy_2d, tuple(initial), (0, 1, 2)
+
+
+def draw_params_dummy_2d(rng, batch, channels, rotation=(-math.pi, math.pi), mirror_axes=(0, 1, 2)):
+    """The draws of the dummy-2-D chain: SpatialTransform sees (B, C * X, Y, Z), so per sample batchgenerators' 2-D order (one
+    angle behind its uniform() <= p_rot_per_axis, then the scale: augmentation.draw_params' spatial part); after Convert2DTo3D the
+    intensity transforms draw per channel over C (not C * X) and the mirroring draws three flags.  p["angle"] is (B,)."""
+    B, C = batch, channels
+    p = {k: np.zeros(B, dtype=bool) for k in ("do_rot", "do_scale", "do_noise", "do_blur", "do_bright", "do_contrast", "do_lowres",
+                                              "do_gamma_inv", "do_gamma")}
+    p.update(angle=np.zeros(B), scale=np.ones(B), noise_std=np.zeros(B), blur_ch=np.zeros((B, C), dtype=bool),
+             blur_sigma=np.ones((B, C)), bright=np.ones((B, C)), contrast=np.ones((B, C)), lowres_ch=np.zeros((B, C), dtype=bool),
+             lowres_zoom=np.ones((B, C)), gamma_inv=np.ones((B, C)), gamma=np.ones((B, C)), mirror=np.zeros((B, 3), dtype=bool))
+    for b in range(B):                                                     # SpatialTransform: p_rot 0.2, p_scale 0.2
+        if rng.uniform() < 0.2:
+            if rng.uniform() <= 1.0:                                       # p_rot_per_axis = 1 (B:670): drawn, always taken
+                p["angle"][b] = rng.uniform(rotation[0], rotation[1])
+            p["do_rot"][b] = True
+        if rng.uniform() < 0.2:
+            p["do_scale"][b], p["scale"][b] = True, A2._two_sided(rng, 0.7, 1.4)
+    return A2._draw_intensity_and_mirror(rng, p, B, C, mirror_axes)
+
+
 def rotation_matrix(ax, ay, az):
     """rotate_coords_3d's matrix I . Rx . Ry . Rz (float64); coordinates are rotated as coords^T . M."""
     cx, sx, cy, sy, cz, sz = math.cos(ax), math.sin(ax), math.cos(ay), math.sin(ay), math.cos(az), math.sin(az)
@@ -87,6 +126,23 @@ def affines(p, in_shape, out_shape):
         L = (M * (p["scale"][b] if p["do_scale"][b] else 1.0)).T               # input_j = sum_i L[j, i] centred_i
         A[b, :, :3] = L
         A[b, :, 3] = np.asarray(in_shape, dtype=np.float64) / 2.0 - 0.5 - L @ half
+    return A, do
+
+
+def affines_planar(p, in_yz, out_yz):
+    """Per sample the (2, 3) float64 map output pixel (y, z) -> input (y, z) of the 2-D augment_spatial that every slice of a
+    dummy-2-D sample goes through: zero-centred mesh, rotated as coords^T . [[cos, -sin], [sin, cos]], scaled, moved to the input
+    centre (in / 2 - 0.5); and whether the sample is resampled at all (else: centre crop over (Y, Z))."""
+    B = len(p["do_rot"])
+    A = np.zeros((B, 2, 3))
+    do = np.asarray(p["do_rot"]) | np.asarray(p["do_scale"])
+    half = (np.asarray(out_yz, dtype=np.float64) - 1) / 2.0
+    for b in range(B):
+        cos, sin = (math.cos(p["angle"][b]), math.sin(p["angle"][b])) if p["do_rot"][b] else (1.0, 0.0)
+        M = np.array([[cos, -sin], [sin, cos]])
+        L = (M * (p["scale"][b] if p["do_scale"][b] else 1.0)).T               # input_j = sum_i L[j, i] centred_i
+        A[b, :, :2] = L
+        A[b, :, 2] = np.asarray(in_yz, dtype=np.float64) / 2.0 - 0.5 - L @ half
     return A, do
 
 
@@ -129,6 +185,33 @@ def sample_3d(img, A, out_shape, order, cval):
     out = (vals * w).sum(2)
     out = torch.where(inside.unsqueeze(1), out, torch.full_like(out, cval))
     return out.view(B, C, *out_shape)
+
+
+def sample_planar(img, A, out_yz, order, cval):
+    """sample_3d for planes: img (B, N, Y, Z) (every slice of every channel as one of the N planes; coefficients prefiltered along
+    Y and Z for order 3), A (B, 2, 3) float64 applied to the output pixel grid -> (B, N, *out_yz).  The arithmetic of K31."""
+    B, N, Y, Z = img.shape
+    dev = img.device
+    grid = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=torch.float64, device=dev) for n in out_yz], indexing="ij"))
+    At = torch.as_tensor(A, dtype=torch.float64, device=dev)
+    coords = torch.einsum("bji,ip->bjp", At[:, :, :2], grid.reshape(2, -1)) + At[:, :, 2:]       # (B, 2, P)
+    inside = torch.ones(coords.shape[::2], dtype=torch.bool, device=dev)
+    taps, weights = [], []
+    first, n = (-1, 4) if order == 3 else (0, 2)
+    for j, size in enumerate((Y, Z)):
+        c = coords[:, j]
+        inside &= (c >= 0) & (c <= size - 1)
+        f = torch.floor(c)
+        t = (c - f).float()
+        weights.append(A2._bspline3_weights(t) if order == 3 else torch.stack([1 - t, t], -2))        # (B, n, P)
+        taps.append(A2._mirror_index(f.long().unsqueeze(1) + torch.arange(n, device=dev).view(1, n, 1) + first, size))
+    iy, iz = taps
+    idx = (iy[:, :, None] * Z + iz[:, None, :]).reshape(B, 1, -1)
+    w = (weights[0][:, :, None] * weights[1][:, None, :]).reshape(B, 1, n * n, -1)
+    vals = img.reshape(B, N, -1).gather(2, idx.expand(-1, N, -1)).view(B, N, n * n, -1)
+    out = (vals * w).sum(2)
+    out = torch.where(inside.unsqueeze(1), out, torch.full_like(out, cval))
+    return out.view(B, N, *out_yz)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -183,6 +266,60 @@ def spatial_transform_3d(data, seg, patch_size, p, labels=None):
     return out_d, out_s
 
 
+def _prefiltered_planar(data, do):
+    """The planar resampler's input: coefficients prefiltered along Y and Z only of the samples in `do`, the data itself for the
+    others."""
+    idx = np.flatnonzero(do)
+    if len(idx) == len(do):
+        return A2.spline_coefficients(data).contiguous()
+    vol = data.clone()
+    if len(idx):
+        sel = torch.as_tensor(idx, device=data.device)
+        vol[sel] = A2.spline_coefficients(data[sel])
+    return vol
+
+
+def spatial_transform_dummy_2d(data, seg, patch_size, p, labels=None):
+    """Convert3DTo2DTransform, the 2-D augment_spatial with the nnU-Net arguments and Convert2DTo3DTransform (B:658-680): data
+    (B, C, X, Yi, Zi) fp32, seg (B, S, X, Yi, Zi) -> (B, C, *patch) fp32 and (B, S, *patch) fp32 labels with patch[0] == X.  Every
+    slice of every channel is resampled in its own plane with the sample's one rotation (p["angle"] (B,)) and scale; every seg
+    channel with the same map and indicator rule.  The device path is the in-plane prefilter and K31."""
+    out_shape = tuple(int(v) for v in patch_size)
+    if data.dim() != 5 or len(out_shape) != 3 or out_shape[0] != data.shape[2]:
+        raise RuntimeError(f"spatial_transform_dummy_2d: data {tuple(data.shape)} to patch {out_shape}: axis 0 is never resampled, "
+                           "the loader delivers patch[0] slices")
+    in_yz, out_yz = tuple(data.shape[3:]), out_shape[1:]
+    A, do = affines_planar(p, in_yz, out_yz)
+    if seg.shape[1] > 1:
+        out_d, first = spatial_transform_dummy_2d(data, seg[:, :1], patch_size, p, labels)
+        if data.is_cuda:                                              # K31 without a volume: the labels only
+            from . import ops
+            rest = [ops.aug3d_resample_planar(None, seg[:, c:c + 1].to(torch.int16).contiguous(), A, do, out_yz)[1]
+                    for c in range(1, seg.shape[1])]
+        else:
+            rest = [spatial_transform_dummy_2d(data[:, :1], seg[:, c:c + 1], patch_size, p)[1] for c in range(1, seg.shape[1])]
+        return out_d, torch.cat([first] + rest, 1)
+    vol = _prefiltered_planar(data.contiguous(), do)
+    if data.is_cuda:
+        from . import ops
+        return ops.aug3d_resample_planar(vol, seg.to(torch.int16).contiguous(), A, do, out_yz)
+    B, C, X = data.shape[:3]
+    out_d = sample_planar(vol.reshape(B, C * X, *in_yz), A, out_yz, 3, 0.0).view(B, C, *out_shape)
+    segf = seg.to(torch.float32)
+    lab = torch.unique(segf) if labels is None else labels.to(segf.device)
+    onehot = (segf == lab.view(1, -1, 1, 1, 1)).to(torch.float32)                           # (B, L, X, Yi, Zi)
+    r = sample_planar(onehot.reshape(B, len(lab) * X, *in_yz), A, out_yz, 1, -1.0).view(B, len(lab), *out_shape)
+    rank = ((r >= 0.5) * torch.arange(1, len(lab) + 1).view(1, -1, 1, 1, 1)).amax(1, keepdim=True)
+    out_s = torch.where(rank > 0, lab[(rank - 1).clamp_(min=0)], torch.zeros(()))
+    o = [(i - s) // 2 for i, s in zip(in_yz, out_yz)]
+    crop = (slice(None), slice(None), slice(None), slice(o[0], o[0] + out_yz[0]), slice(o[1], o[1] + out_yz[1]))
+    m = torch.as_tensor(do).view(B, 1, 1, 1, 1)
+    if (~do).any():
+        out_d = torch.where(m, out_d, data[crop])
+        out_s = torch.where(m, out_s, segf[crop])
+    return out_d, out_s
+
+
 def gaussian_blur_3d(data, do, sigma, radius):
     """scipy.ndimage.gaussian_filter(img, sigma) (same sigma on the three axes, truncate 4, "reflect") per (sample, channel)
     where `do`; `radius` = int(4 max(sigma) + 0.5) from the host-side parameters."""
@@ -199,26 +336,45 @@ def gaussian_blur_3d(data, do, sigma, radius):
     return torch.where(do.view(B, C, 1, 1, 1), x, data)
 
 
-def simulate_low_resolution_3d(data, do, zoom):
+def simulate_low_resolution_3d(data, do, zoom, ignore_axes=None):
     """SimulateLowResolutionTransform, 3-D: per selected (sample, channel) nearest-exact down-sampling to round(shape * zoom),
-    back with a cubic B-spline (12 voxels of edge padding, half-pixel grid), clipped to the small image's range."""
+    back with a cubic B-spline (12 voxels of edge padding, half-pixel grid), clipped to the small image's range.
+    ignore_axes (0,) (the dummy-2-D chain, B:687-690): the small shape keeps axis 0, so both resizes are separable per slice --
+    in-plane padding and prefilter, K31 with a diagonal map on the device -- while the clip still uses the range of the small
+    VOLUME (skimage's resize clips to the range of its whole input), not of each slice."""
+    ignore_axes = tuple(ignore_axes) if ignore_axes else ()
+    if ignore_axes not in ((), (0,)):
+        raise RuntimeError(f"simulate_low_resolution_3d: ignore_axes {ignore_axes}: None or (0,) expected")
     out = data.clone()
     shape = tuple(data.shape[2:])
     for b, c in np.argwhere(np.asarray(do)).tolist():
         small_shape = tuple(int(v) for v in np.round(np.array(shape, dtype=float) * float(zoom[b, c])))
+        if ignore_axes:
+            small_shape = (shape[0],) + small_shape[1:]
         f64 = dict(device=data.device, dtype=torch.float64)
         ix, iy, iz = (torch.floor((torch.arange(m, **f64) + 0.5) * (n / m)).long().clamp_(0, n - 1)
                       for n, m in zip(shape, small_shape))
         small = data[b, c][ix][:, iy][:, :, iz]
-        coef = spline_coefficients_3d(F.pad(small[None, None], (12,) * 6, mode="replicate")).contiguous()
-        A = np.zeros((1, 3, 4))
-        for j, (n, m) in enumerate(zip(shape, small_shape)):
-            A[0, j, j], A[0, j, 3] = m / n, 0.5 * m / n - 0.5 + 12
-        if data.is_cuda:
-            from . import ops
-            up = ops.aug3d_resample(coef, None, A, [True], shape)[0][0, 0]
+        if ignore_axes:
+            coef = A2.spline_coefficients(F.pad(small[None], (12,) * 4, mode="replicate")).contiguous()      # (1, X, h + 24, w + 24)
+            A = np.zeros((1, 2, 3))
+            for j, (n, m) in enumerate(zip(shape[1:], small_shape[1:])):
+                A[0, j, j], A[0, j, 2] = m / n, 0.5 * m / n - 0.5 + 12
+            if data.is_cuda:
+                from . import ops
+                up = ops.aug3d_resample_planar(coef[None], None, A, [True], shape[1:])[0][0, 0]
+            else:
+                up = sample_planar(coef, A, shape[1:], 3, 0.0)[0]
         else:
-            up = sample_3d(coef, A, shape, 3, 0.0)[0, 0]
+            coef = spline_coefficients_3d(F.pad(small[None, None], (12,) * 6, mode="replicate")).contiguous()
+            A = np.zeros((1, 3, 4))
+            for j, (n, m) in enumerate(zip(shape, small_shape)):
+                A[0, j, j], A[0, j, 3] = m / n, 0.5 * m / n - 0.5 + 12
+            if data.is_cuda:
+                from . import ops
+                up = ops.aug3d_resample(coef, None, A, [True], shape)[0][0, 0]
+            else:
+                up = sample_3d(coef, A, shape, 3, 0.0)[0, 0]
         out[b, c] = torch.minimum(torch.maximum(up, small.min()), small.max())
     return out
 
@@ -462,16 +618,22 @@ def move_seg_as_one_hot(data, seg, labels):
 
 class GpuAugmenter3D:
     """(loader batch on the device) -> augmented (data, seg): the reference's 3-D training transform chain behind
-    `dataloading.DataLoader3D`.  `patch_size`: the network's; the loader delivers `initial_patch_size()`."""
+    `dataloading.DataLoader3D`.  `patch_size`: the network's; the loader delivers `initial_patch_size()`.
+    `dummy_2d`: the chain of an anisotropic plan (do_dummy_2d_data_aug): 2-D draws, every slice resampled in its own plane (K31),
+    SimulateLowResolution with ignore_axes (0,).  `for_plan` picks the mode as the reference does."""
 
     takes_int16_seg = True                      # dataloading.to_device hands over the loader's int16 labels as they are
 
-    def __init__(self, patch_size, device, rotation=None, mirror_axes=(0, 1, 2), seed=None, labels=None, cascade_labels=None):
+    def __init__(self, patch_size, device, rotation=None, mirror_axes=(0, 1, 2), seed=None, labels=None, cascade_labels=None,
+                 dummy_2d=False):
         self.patch_size = tuple(int(v) for v in patch_size)
         if len(self.patch_size) != 3:
             raise RuntimeError(f"GpuAugmenter3D: a 3-D patch, got {self.patch_size}")
         self.device = torch.device(device)
-        self.rotation = rotation_for_3d(self.patch_size) if rotation is None else rotation
+        self.dummy_2d = bool(dummy_2d)
+        if rotation is None:
+            rotation = ((-math.pi, math.pi), (0, 0), (0, 0)) if self.dummy_2d else rotation_for_3d(self.patch_size)
+        self.rotation = rotation
         self.mirror_axes = tuple(mirror_axes)
         # every value the loader's segmentation can hold (label_manager.all_labels and the -1 padding), ascending (host path)
         self.labels = None if labels is None else torch.tensor(sorted(set(labels) | {-1}), dtype=torch.float32)
@@ -480,12 +642,21 @@ class GpuAugmenter3D:
         self.cascade_labels = None if cascade_labels is None else tuple(int(v) for v in cascade_labels)
         self.cascade_order = None if cascade_labels is None else list(range(len(self.cascade_labels)))
 
+    @classmethod
+    def for_plan(cls, patch_size, device, **kw):
+        """The augmenter of a 3-D plan: rotation ranges, mirror axes and the dummy-2-D switch from `configure_3d`."""
+        rotation, dummy_2d, _, mirror_axes = configure_3d(patch_size)
+        return cls(patch_size, device, rotation=rotation, mirror_axes=mirror_axes, dummy_2d=dummy_2d, **kw)
+
     def initial_patch_size(self):
-        """get_patch_size with the rotation ranges and the (0.85, 1.25) scale range of B:389-391."""
-        return tuple(int(v) for v in get_patch_size(self.patch_size, *self.rotation, (0.85, 1.25)))
+        """get_patch_size with the rotation ranges and the (0.85, 1.25) scale range of B:389-391; dummy-2-D keeps patch[0]
+        (B:403-404)."""
+        initial = tuple(int(v) for v in get_patch_size(self.patch_size, *self.rotation, (0.85, 1.25)))
+        return (self.patch_size[0],) + initial[1:] if self.dummy_2d else initial
 
     def apply(self, data, seg, p, noise=None, cascade=None, rng=None):
-        """The transform chain with given parameters (`draw_params_3d` layout); data (B, C, Xi, Yi, Zi) fp32, seg (B, 1, Xi, Yi, Zi).
+        """The transform chain with given parameters (`draw_params_3d` layout; `draw_params_dummy_2d`'s with dummy_2d, where
+        Xi == patch[0]); data (B, C, Xi, Yi, Zi) fp32, seg (B, 1, Xi, Yi, Zi).
         With `cascade_labels`: seg (B, 2, Xi, Yi, Zi), `cascade` the draw_cascade_params lists, `rng` the stream of the component
         removal's draws (the augmenter's own by default); returns data (B, C + L, *patch) and the one-channel target."""
         if (self.cascade_labels is not None) != (seg.shape[1] == 2) or seg.shape[1] > 2:
@@ -493,7 +664,8 @@ class GpuAugmenter3D:
                                "stage's segmentation is the second seg channel of a cascade batch, and of no other")
         dev = data.device
         T = lambda a, dt=torch.float32: torch.as_tensor(np.asarray(a), device=dev).to(dt)      # noqa: E731
-        data, seg = spatial_transform_3d(data, seg, self.patch_size, p, self.labels)
+        spatial = spatial_transform_dummy_2d if self.dummy_2d else spatial_transform_3d
+        data, seg = spatial(data, seg, self.patch_size, p, self.labels)
         if noise is None:
             noise = torch.randn_like(data)
         data = data + noise * T(p["noise_std"] * p["do_noise"]).view(-1, 1, 1, 1, 1)
@@ -503,7 +675,8 @@ class GpuAugmenter3D:
         data = torch.where(T(p["do_bright"], torch.bool).view(-1, 1, 1, 1, 1),
                            data * T(p["bright"]).view(*p["bright"].shape, 1, 1, 1), data)
         data = contrast_transform(data, T(p["do_contrast"], torch.bool), T(p["contrast"]))
-        data = simulate_low_resolution_3d(data, p["lowres_ch"] & p["do_lowres"][:, None], p["lowres_zoom"])
+        data = simulate_low_resolution_3d(data, p["lowres_ch"] & p["do_lowres"][:, None], p["lowres_zoom"],
+                                          (0,) if self.dummy_2d else None)
         data = gamma_transform(data, T(p["do_gamma_inv"], torch.bool), T(p["gamma_inv"]), invert=True)
         data = gamma_transform(data, T(p["do_gamma"], torch.bool), T(p["gamma"]), invert=False)
         data, seg = mirror_transform(data, seg, T(p["mirror"], torch.bool))
@@ -517,12 +690,16 @@ class GpuAugmenter3D:
 
     def clone(self, seed):
         """The same chain with its own parameter stream (one per loader worker) and its own channel order."""
-        twin = GpuAugmenter3D(self.patch_size, self.device, self.rotation, self.mirror_axes, seed, cascade_labels=self.cascade_labels)
+        twin = GpuAugmenter3D(self.patch_size, self.device, self.rotation, self.mirror_axes, seed, cascade_labels=self.cascade_labels,
+                              dummy_2d=self.dummy_2d)
         twin.labels = self.labels
         return twin
 
     def __call__(self, data, seg):
-        p = draw_params_3d(self.rng, data.shape[0], data.shape[1], self.rotation, self.mirror_axes)
+        if self.dummy_2d:
+            p = draw_params_dummy_2d(self.rng, data.shape[0], data.shape[1], self.rotation[0], self.mirror_axes)
+        else:
+            p = draw_params_3d(self.rng, data.shape[0], data.shape[1], self.rotation, self.mirror_axes)
         if self.cascade_labels is None:
             return self.apply(data, seg, p)
         cascade = draw_cascade_params(self.rng, data.shape[0], len(self.cascade_labels), self.cascade_order)

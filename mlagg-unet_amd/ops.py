@@ -3238,6 +3238,39 @@ def aug3d_resample(vol, lab, affine, resample, out_shape):
 
 
 # ------------------------------------------------------------------------------------------------
+# K31: planar ("dummy 2-D") spatial augmentation of anisotropic 3-D patches (augmentation3d.GpuAugmenter3D(dummy_2d=True))
+# ------------------------------------------------------------------------------------------------
+def aug3d_resample_planar(vol, lab, affine, resample, out_yz):
+    """vol (B, C, X, Yi, Zi) fp32 (spline coefficients along Y and Z of the resampled samples, raw data of the cropped ones), lab
+    (B, 1, X, Yi, Zi) int16 or None, affine (B, 2, 3) float64 host array (output pixel (y, z) -> input (y, z), the same for every
+    slice and channel of the sample), resample (B,) host bools -> (out (B, C, X, *out_yz) fp32, out_lab (B, 1, X, *out_yz) fp32 or
+    None).  vol None with lab: the labels only, out is None.  See include/mlagg_hip.h, K31."""
+    if vol is None:
+        _expect(lab, "lab", torch.int16, dim=5)
+        B, C, (X, Yi, Zi) = int(lab.shape[0]), 0, (int(v) for v in lab.shape[2:])
+        vol = lab                                         # shape and device of the checks below
+    else:
+        _expect(vol, "vol", dim=5)
+        B, C, X, Yi, Zi = (int(v) for v in vol.shape)
+    if len(out_yz) != 2 or min(int(v) for v in out_yz) < 1:
+        raise RuntimeError(f"aug3d_resample_planar: output plane {tuple(out_yz)}")
+    Yo, Zo = (int(v) for v in out_yz)
+    if lab is not None:
+        _expect(lab, "lab", torch.int16, shape=(B, 1, X, Yi, Zi), like=vol)
+    A = np.ascontiguousarray(np.asarray(affine, dtype=np.float64).reshape(B, 6))
+    rs = np.asarray(resample, dtype=bool).reshape(-1)
+    if rs.shape[0] != B:
+        raise RuntimeError(f"aug3d_resample_planar: {rs.shape[0]} resample flags for {B} samples")
+    if (~rs).any() and (Yo > Yi or Zo > Zi):
+        raise RuntimeError(f"aug3d_resample_planar: a cropped sample needs input planes ({Yi}, {Zi}) at least the output ({Yo}, {Zo})")
+    out = torch.empty((B, C, X, Yo, Zo), device=vol.device, dtype=torch.float32) if C else None
+    out_lab = torch.empty((B, 1, X, Yo, Zo), device=vol.device, dtype=torch.float32) if lab is not None else None
+    _launch("mlagg_aug3d_resample_planar", _ptr(vol) if C else None, _ptr(lab), B, C, X, Yi, Zi, A.ctypes.data, _int_array(rs.astype(int)),
+            _ptr(out), _ptr(out_lab), Yo, Zo)
+    return out, out_lab
+
+
+# ------------------------------------------------------------------------------------------------
 # K27: cell-instance F1 evaluation (csrc/cells.hip).  cells.py composes these per image and per tile and does the assignment on the
 # host.  Inference only.
 # ------------------------------------------------------------------------------------------------
