@@ -19,6 +19,8 @@ struct Rec {
 std::mutex g_mu;
 std::vector<Rec> g_recs;         // event pairs, reused across collect() calls
 size_t g_used = 0;
+// the labels of prof.h's timed scopes, in KernelId order: a label names the phase it times, which need not be one kernel's name
+// (cc_compress / cc_size / cl_compress time unionfind.h's compress_kernel and size_kernel in their callers)
 const char *const kNames[K_COUNT] = {
     "selscan_fwd_kernel<false>", "selscan_chunk_prefix", "selscan_fwd_kernel<true>", "selscan_bwd_local_kernel",
     "selscan_bwd_group_kernel", "selscan_reduce_partials", "local_attn_fwd_kernel", "local_attn_bwd_a_kernel",

@@ -18,22 +18,22 @@
 //                           (i - c);
 //   cascade_commit_kernel   the reference's "was added" rule: plane c of a sample takes the result, res & ~before is cleared in the
 //                           sample's other planes;
-//   cascade_cc_*            26-connected components of every plane with the union-find of unionfind.h in K23's phases (8 x 8 x 32
-//                           tile in LDS, merge across tile faces, compress, sizes), then per plane the number of components with
-//                           size < thresh and, for a chosen rank k, the k-th such component in root order (a root is its component's
-//                           minimum linear index: scipy's / skimage's label order), which is cleared, and optionally set in another
-//                           plane.
+//   cascade_cc_*            26-connected components of every plane with the labelling of cc_label.h over a voxel source that reads
+//                           the bits (tile-local union-find, merge across tile faces, compress, sizes), then per plane the number
+//                           of components with size < thresh and, for a chosen rank k, the k-th such component in root order (a
+//                           root is its component's minimum linear index: scipy's / skimage's label order), which is cleared, and
+//                           optionally set in another plane.
 // Integer atomics only; every result is independent of the schedule.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
+#include "cc_label.h"
 #include "mlagg_hip.h"
-#include "unionfind.h"
 
 namespace {
 
-using namespace mlagg_uf;
+using namespace mlagg_cc;
 typedef unsigned long long u64;
 
 struct Labels {
@@ -178,165 +178,46 @@ __global__ void __launch_bounds__(256) cascade_commit_kernel(u64 *__restrict__ p
 // ---------------------------------------------------------------------------------------------------------------------------
 // connected components of the planes (grid.y = plane)
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr int TX = 8, TY = 8, TZ = 32;                 // K23's tile; z is the contiguous axis
-constexpr int TV = TX * TY * TZ;
-constexpr int CC_BLOCK = 512;                          // 4 consecutive z voxels per lane
 constexpr int SEL_BLOCK = 256;
 
-struct Geo {
-    int X, Y, Z, W;
-    int ntx, nty, ntz;
-    long long N, plane_words;
+struct Planes {
+    Geo g;
+    int W;                                             // words per row
+    long long plane_words;
 };
 
-__device__ __forceinline__ void backward(int i, int &dx, int &dy, int &dz)
-{
-    if (i < 9) {
-        dx = -1;
-        dy = i / 3 - 1;
-        dz = i % 3 - 1;
-    } else if (i < 12) {
-        dx = 0;
-        dy = -1;
-        dz = i - 10;
-    } else {
-        dx = 0;
-        dy = 0;
-        dz = -1;
+// K30's voxel source: the class of a voxel is its bit
+struct BitSource {
+    const u64 *plane;
+    int Y, W;
+
+    __device__ __forceinline__ u64 word(int x, int y, int z) const
+    {
+        return plane[((long long)x * Y + y) * W + (z >> 6)] >> (z & 63);
     }
-}
 
-__device__ __forceinline__ void lane_coords(int t, int &lx, int &ly, int &lz)
-{
-    lz = (t & 7) * 4;
-    ly = (t >> 3) & 7;
-    lx = t >> 6;
-}
+    // z is a multiple of 4: the four voxels lie in one word, and the padding bits beyond Z are 0
+    __device__ __forceinline__ uint32_t classes4(int x, int y, int z) const
+    {
+        const uint32_t b = (uint32_t)word(x, y, z);
+        return (b & 1u) | (b & 2u) << 7 | (b & 4u) << 14 | (b & 8u) << 21;
+    }
 
-__device__ __forceinline__ bool voxel(const u64 *plane, const Geo &g, int x, int y, int z)
-{
-    return (plane[((long long)x * g.Y + y) * g.W + (z >> 6)] >> (z & 63)) & 1ull;
-}
+    __device__ __forceinline__ uint32_t class1(int x, int y, int z) const
+    {
+        return (uint32_t)word(x, y, z) & 1u;
+    }
+};
 
-__global__ void __launch_bounds__(CC_BLOCK) cascade_cc_local_kernel(const u64 *__restrict__ planes, Geo g, int *__restrict__ parent,
+__global__ void __launch_bounds__(CC_BLOCK) cascade_cc_local_kernel(const u64 *__restrict__ planes, Planes p, int *__restrict__ parent,
                                                                      int *__restrict__ size)
 {
-    __shared__ int par[TV];
-    __shared__ int cnt[TV];
-    __shared__ uint8_t in[TV];
-    const u64 *plane = planes + blockIdx.y * g.plane_words;
-    parent += blockIdx.y * g.N;
-    size += blockIdx.y * g.N;
-    const int t = threadIdx.x;
-    const int tz = blockIdx.x % g.ntz, r = blockIdx.x / g.ntz;
-    const int x0 = (r / g.nty) * TX, y0 = (r % g.nty) * TY, z0 = tz * TZ;
-    int lx, ly, lz;
-    lane_coords(t, lx, ly, lz);
-    const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-    const bool row = x < g.X && y < g.Y && z < g.Z;
-    // z is a multiple of 4: the four voxels lie in one word, and the padding bits beyond Z are 0
-    const unsigned bits = row ? (unsigned)((plane[((long long)x * g.Y + y) * g.W + (z >> 6)] >> (z & 63)) & 15ull) : 0u;
-    const int l0 = (lx * TY + ly) * TZ + lz;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        in[l0 + j] = (bits >> j) & 1u;
-        par[l0 + j] = l0 + j;
-        cnt[l0 + j] = 0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (!((bits >> j) & 1u)) continue;
-        for (int i = 0; i < 13; ++i) {
-            int dx, dy, dz;
-            backward(i, dx, dy, dz);
-            const int nx = lx + dx, ny = ly + dy, nz = lz + j + dz;
-            if (nx < 0 || ny < 0 || ny >= TY || nz < 0 || nz >= TZ) continue;
-            const int n = (nx * TY + ny) * TZ + nz;
-            if (in[n]) lds_unite(par, l0 + j, n);
-        }
-    }
-    __syncthreads();
-    int root[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        root[j] = -1;
-        if ((bits >> j) & 1u) {
-            root[j] = lds_find(par, l0 + j);
-            atomicAdd(&cnt[root[j]], 1);
-        }
-    }
-    __syncthreads();
-    if (!row) return;
-    const long long o = ((long long)x * g.Y + y) * g.Z + z;
-    for (int j = 0; j < 4 && z + j < g.Z; ++j) {
-        int p = -1, s = 0;
-        if ((bits >> j) & 1u) {
-            const int rt = root[j];
-            const int rx = rt / (TY * TZ), ry = (rt / TZ) % TY, rz = rt % TZ;
-            p = (int)(((long long)(x0 + rx) * g.Y + (y0 + ry)) * g.Z + (z0 + rz));
-            if (rt == l0 + j) s = cnt[rt];
-        }
-        parent[o + j] = p;
-        size[o + j] = s;
-    }
+    label_tile(BitSource{planes + blockIdx.y * p.plane_words, p.g.Y, p.W}, p.g, parent, size);
 }
 
-__global__ void __launch_bounds__(CC_BLOCK) cascade_cc_merge_kernel(const u64 *__restrict__ planes, Geo g, int *__restrict__ parent)
+__global__ void __launch_bounds__(CC_BLOCK) cascade_cc_merge_kernel(const u64 *__restrict__ planes, Planes p, int *__restrict__ parent)
 {
-    const u64 *plane = planes + blockIdx.y * g.plane_words;
-    parent += blockIdx.y * g.N;
-    const int t = threadIdx.x;
-    const int tz = blockIdx.x % g.ntz, r = blockIdx.x / g.ntz;
-    const int x0 = (r / g.nty) * TX, y0 = (r % g.nty) * TY, z0 = tz * TZ;
-    int lx, ly, lz;
-    lane_coords(t, lx, ly, lz);
-    const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-    // only lanes on a tile face have backward neighbours in another tile
-    const bool face = lx == 0 || ly == 0 || ly == TY - 1 || lz == 0 || lz + 4 == TZ;
-    if (!face || x >= g.X || y >= g.Y || z >= g.Z) return;
-    for (int j = 0; j < 4 && z + j < g.Z; ++j) {
-        const int lzj = lz + j;
-        if (!(lx == 0 || ly == 0 || ly == TY - 1 || lzj == 0 || lzj == TZ - 1)) continue;
-        if (!voxel(plane, g, x, y, z + j)) continue;
-        const int me = (int)(((long long)x * g.Y + y) * g.Z + z + j);
-        for (int i = 0; i < 13; ++i) {
-            int dx, dy, dz;
-            backward(i, dx, dy, dz);
-            const int nlx = lx + dx, nly = ly + dy, nlz = lzj + dz;
-            if (nlx >= 0 && nly >= 0 && nly < TY && nlz >= 0 && nlz < TZ) continue;      // same tile: done in the local pass
-            const int nx = x + dx, ny = y + dy, nz = z + j + dz;
-            if (nx < 0 || ny < 0 || ny >= g.Y || nz < 0 || nz >= g.Z) continue;
-            if (voxel(plane, g, nx, ny, nz)) gunite(parent, me, (int)(((long long)nx * g.Y + ny) * g.Z + nz));
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) cascade_cc_compress_kernel(int *__restrict__ parent, long long N)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    parent += blockIdx.y * N;
-    const int p = parent[i];
-    if (p < 0 || p == i) return;
-    int r = p, q = parent[r];
-    while (q != r) {
-        r = q;
-        q = parent[r];
-    }
-    if (r != p) parent[i] = r;
-}
-
-__global__ void __launch_bounds__(256) cascade_cc_size_kernel(const int *__restrict__ parent, int *__restrict__ size, long long N)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    parent += blockIdx.y * N;
-    size += blockIdx.y * N;
-    const int s = size[i];
-    if (s == 0) return;
-    const int r = parent[i];
-    if (r != i) atomicAdd(&size[r], s);               // a component root keeps its own tile count in place
+    merge_tiles(BitSource{planes + blockIdx.y * p.plane_words, p.g.Y, p.W}, p.g, parent);
 }
 
 // per 256 voxels the number of valid roots (size < thresh); table[plane] = (non-empty, n_valid)
@@ -398,36 +279,28 @@ __global__ void __launch_bounds__(SEL_BLOCK) cascade_cc_select_kernel(const int 
 }
 
 // one wave per word: clears the voxels of the target component, and sets them in plane pl + fill[pl] when fill[pl] != 0
-__global__ void __launch_bounds__(256) cascade_cc_remove_kernel(u64 *__restrict__ planes, Geo g, const int *__restrict__ parent,
+__global__ void __launch_bounds__(256) cascade_cc_remove_kernel(u64 *__restrict__ planes, Planes p, const int *__restrict__ parent,
                                                                 const int *__restrict__ target, const int *__restrict__ fill)
 {
     const int pl = blockIdx.y, lane = threadIdx.x & 63;
     const int tg = target[pl];
     if (tg < 0) return;
     const long long word = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (word >= g.plane_words) return;
-    const int w = (int)(word % g.W);
-    const long long row = word / g.W;
+    if (word >= p.plane_words) return;
+    const int w = (int)(word % p.W);
+    const long long row = word / p.W;
     const int z = w * 64 + lane;
-    const u64 m = __ballot(z < g.Z && parent[pl * g.N + row * g.Z + z] == tg);
+    const u64 m = __ballot(z < p.g.Z && parent[pl * p.g.N + row * p.g.Z + z] == tg);
     if (lane || !m) return;
-    atomicAnd(&planes[pl * g.plane_words + word], ~m);
-    if (fill[pl]) atomicOr(&planes[(pl + fill[pl]) * g.plane_words + word], m);
+    atomicAnd(&planes[pl * p.plane_words + word], ~m);
+    if (fill[pl]) atomicOr(&planes[(pl + fill[pl]) * p.plane_words + word], m);
 }
 
-bool geometry(int P, int X, int Y, int Z, Geo &g)
+bool planes_geometry(int P, int X, int Y, int Z, Planes &p)
 {
-    if (P < 1 || X < 1 || Y < 1 || Z < 1) return false;
-    g.X = X;
-    g.Y = Y;
-    g.Z = Z;
-    g.W = (Z + 63) / 64;
-    g.N = (long long)X * Y * Z;
-    if (g.N > 2147483647LL || P > 65535) return false;
-    g.plane_words = (long long)X * Y * g.W;
-    g.ntx = (X + TX - 1) / TX;
-    g.nty = (Y + TY - 1) / TY;
-    g.ntz = (Z + TZ - 1) / TZ;
+    if (!geometry(P, X, Y, Z, p.g)) return false;
+    p.W = (Z + 63) / 64;
+    p.plane_words = (long long)X * Y * p.W;
     return true;
 }
 
@@ -470,8 +343,8 @@ extern "C" int mlagg_cascade_morph(unsigned long long *pool, int n_planes, int X
                                    const int *jobs, int n_jobs, void *stream)
 {
     if (!pool || !runs || !jobs) return MLAGG_E_NULLPTR;
-    Geo g;
-    if (!geometry(1, X, Y, Z, g) || n_planes < 2 || n_jobs < 1 || n_runs_total < 1) return MLAGG_E_UNSUPPORTED;
+    Planes p;
+    if (!planes_geometry(1, X, Y, Z, p) || n_planes < 2 || n_jobs < 1 || n_runs_total < 1) return MLAGG_E_UNSUPPORTED;
     for (int j = 0; j < n_jobs; ++j) {
         const int *q = jobs + 5 * j;                                 // (src, dst, first run, runs, complement)
         if (q[0] < 0 || q[0] >= n_planes || q[1] < 0 || q[1] >= n_planes || q[0] == q[1] || q[2] < 0 || q[3] < 1 ||
@@ -481,7 +354,7 @@ extern "C" int mlagg_cascade_morph(unsigned long long *pool, int n_planes, int X
             if (jobs[5 * i + 1] == q[1] || jobs[5 * i + 1] == q[0] || jobs[5 * i] == q[1]) return MLAGG_E_UNSUPPORTED;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int ntx = (X + MT - 1) / MT, nty = (Y + MT - 1) / MT, ntw = (g.W + MW - 1) / MW;
+    const int ntx = (X + MT - 1) / MT, nty = (Y + MT - 1) / MT, ntw = (p.W + MW - 1) / MW;
     if ((long long)ntx * nty * ntw > 2147483647LL) return MLAGG_E_UNSUPPORTED;
     for (int j0 = 0; j0 < n_jobs; j0 += MJ) {
         const int nj = n_jobs - j0 < MJ ? n_jobs - j0 : MJ;
@@ -495,7 +368,7 @@ extern "C" int mlagg_cascade_morph(unsigned long long *pool, int n_planes, int X
             mj.complement[j] = q[4] != 0;
         }
         hipLaunchKernelGGL(cascade_morph_kernel, dim3((unsigned)(ntx * nty * ntw), (unsigned)nj), dim3(MT * MT * MW), 0, st, pool,
-                           g.plane_words, X, Y, Z, g.W, ntx, nty, ntw, reinterpret_cast<const int4 *>(runs), mj);
+                           p.plane_words, X, Y, Z, p.W, ntx, nty, ntw, reinterpret_cast<const int4 *>(runs), mj);
         if (int rc = (int)hipGetLastError()) return rc;
     }
     return 0;
@@ -505,8 +378,8 @@ extern "C" int mlagg_cascade_commit(unsigned long long *pool, int n_planes, int 
                                     void *stream)
 {
     if (!pool || !jobs) return MLAGG_E_NULLPTR;
-    Geo g;
-    if (!geometry(1, X, Y, Z, g) || L < 1 || n_jobs < 1) return MLAGG_E_UNSUPPORTED;
+    Planes p;
+    if (!planes_geometry(1, X, Y, Z, p) || L < 1 || n_jobs < 1) return MLAGG_E_UNSUPPORTED;
     for (int j = 0; j < n_jobs; ++j) {
         const int *q = jobs + 3 * j;                                 // (result plane, target plane, the sample's first plane)
         if (q[0] < 0 || q[0] >= n_planes || q[2] < 0 || q[2] + L > n_planes || q[1] < q[2] || q[1] >= q[2] + L ||
@@ -516,7 +389,7 @@ extern "C" int mlagg_cascade_commit(unsigned long long *pool, int n_planes, int 
             if (jobs[3 * i + 2] < q[2] + L && q[2] < jobs[3 * i + 2] + L) return MLAGG_E_UNSUPPORTED;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned blocks = (unsigned)((g.plane_words + 255) / 256);
+    const unsigned blocks = (unsigned)((p.plane_words + 255) / 256);
     for (int j0 = 0; j0 < n_jobs; j0 += MJ) {
         const int nj = n_jobs - j0 < MJ ? n_jobs - j0 : MJ;
         CommitJobs cj = {};
@@ -525,7 +398,7 @@ extern "C" int mlagg_cascade_commit(unsigned long long *pool, int n_planes, int 
             cj.target[j] = jobs[3 * (j0 + j) + 1];
             cj.first[j] = jobs[3 * (j0 + j) + 2];
         }
-        hipLaunchKernelGGL(cascade_commit_kernel, dim3(blocks, (unsigned)nj), dim3(256), 0, st, pool, g.plane_words, L, cj);
+        hipLaunchKernelGGL(cascade_commit_kernel, dim3(blocks, (unsigned)nj), dim3(256), 0, st, pool, p.plane_words, L, cj);
         if (int rc = (int)hipGetLastError()) return rc;
     }
     return 0;
@@ -540,16 +413,17 @@ extern "C" int mlagg_cascade_cc_stats(const unsigned long long *planes, int P, i
                                       int *size, int *blockcnt, int *table, void *stream)
 {
     if (!planes || !parent || !size || !blockcnt || !table) return MLAGG_E_NULLPTR;
-    Geo g;
-    if (!geometry(P, X, Y, Z, g)) return MLAGG_E_UNSUPPORTED;
+    Planes p;
+    if (!planes_geometry(P, X, Y, Z, p)) return MLAGG_E_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (hipError_t e = hipMemsetAsync(table, 0, 2 * (size_t)P * sizeof(int), st)) return (int)e;
-    const dim3 tiles((unsigned)(g.ntx * g.nty * g.ntz), (unsigned)P), vox((unsigned)((g.N + 255) / 256), (unsigned)P);
-    hipLaunchKernelGGL(cascade_cc_local_kernel, tiles, dim3(CC_BLOCK), 0, st, planes, g, parent, size);
-    hipLaunchKernelGGL(cascade_cc_merge_kernel, tiles, dim3(CC_BLOCK), 0, st, planes, g, parent);
-    hipLaunchKernelGGL(cascade_cc_compress_kernel, vox, dim3(256), 0, st, parent, g.N);
-    hipLaunchKernelGGL(cascade_cc_size_kernel, vox, dim3(256), 0, st, parent, size, g.N);
-    hipLaunchKernelGGL(cascade_cc_count_kernel, vox, dim3(256), 0, st, parent, size, g.N, thresh, blockcnt, table);
+    const long long N = p.g.N;
+    const dim3 tiles(tile_count(p.g), (unsigned)P), vox((unsigned)((N + 255) / 256), (unsigned)P);
+    hipLaunchKernelGGL(cascade_cc_local_kernel, tiles, dim3(CC_BLOCK), 0, st, planes, p, parent, size);
+    hipLaunchKernelGGL(cascade_cc_merge_kernel, tiles, dim3(CC_BLOCK), 0, st, planes, p, parent);
+    hipLaunchKernelGGL(mlagg_uf::compress_kernel<>, vox, dim3(256), 0, st, parent, N);
+    hipLaunchKernelGGL(mlagg_uf::size_kernel<>, vox, dim3(256), 0, st, parent, size, N);
+    hipLaunchKernelGGL(cascade_cc_count_kernel, vox, dim3(256), 0, st, parent, size, N, thresh, blockcnt, table);
     return (int)hipGetLastError();
 }
 
@@ -558,13 +432,13 @@ extern "C" int mlagg_cascade_cc_remove(unsigned long long *planes, int P, int X,
                                        void *stream)
 {
     if (!planes || !parent || !size || !blockcnt || !rank || !fill || !target) return MLAGG_E_NULLPTR;
-    Geo g;
-    if (!geometry(P, X, Y, Z, g)) return MLAGG_E_UNSUPPORTED;
+    Planes p;
+    if (!planes_geometry(P, X, Y, Z, p)) return MLAGG_E_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (hipError_t e = hipMemsetAsync(target, 0xff, (size_t)P * sizeof(int), st)) return (int)e;
-    hipLaunchKernelGGL(cascade_cc_select_kernel, dim3((unsigned)P), dim3(SEL_BLOCK), 0, st, parent, size, g.N, thresh, blockcnt,
-                       (int)((g.N + 255) / 256), rank, target);
-    hipLaunchKernelGGL(cascade_cc_remove_kernel, dim3((unsigned)((g.plane_words + 3) / 4), (unsigned)P), dim3(256), 0, st, planes, g,
+    hipLaunchKernelGGL(cascade_cc_select_kernel, dim3((unsigned)P), dim3(SEL_BLOCK), 0, st, parent, size, p.g.N, thresh, blockcnt,
+                       (int)((p.g.N + 255) / 256), rank, target);
+    hipLaunchKernelGGL(cascade_cc_remove_kernel, dim3((unsigned)((p.plane_words + 3) / 4), (unsigned)P), dim3(256), 0, st, planes, p,
                        parent, target, fill);
     return (int)hipGetLastError();
 }

@@ -12,8 +12,9 @@
 //                         backward neighbours W, NW, N, NE; writes parent[v] = global index of v's tile root, -1 off the mask; with a
 //                         gt map also the three dice counts |gt > 0|, |seg == fg|, |both| (LDS partials, one global add per block);
 //     cl_merge_kernel     pixels on a tile edge unite their tree with the neighbour tiles' trees in the global parent array;
-//     cl_compress_kernel  parent[v] = find(v).  Links go towards the smaller index (unionfind.h, shared with K23), so every root is
-//                         its component's minimum linear index = its first pixel in raster order, whatever the schedule.
+//     mlagg_uf::compress_kernel   parent[v] = find(v), the kernel the 3-D labellings use.  Links go towards the smaller index
+//                         (unionfind.h), so every root is its component's minimum linear index = its first pixel in raster order,
+//                         whatever the schedule.
 //   mlagg_cells_relabel   order-preserving compaction of a key map (a label map, or parent + 1) to 1..n over a rectangular view:
 //     cl_flag_kernel      present[key] = 1, and removed[key] = 1 for keys seen in the view's 2-pixel ring (plain byte stores of 1);
 //     cl_scan_count / cl_scan_offsets / cl_scan_apply   exclusive scan of present & ~removed over the key domain -> newid[key];
@@ -155,20 +156,6 @@ __global__ void __launch_bounds__(CL_BLOCK) cl_merge_kernel(Img m, int *__restri
             if ((ly == 0 || cx == TW - 1) && gx + 1 < m.W && is_fg(m, up + 1)) gunite(parent, me, (int)(up + 1));   // NE
         }
     }
-}
-
-__global__ void __launch_bounds__(256) cl_compress_kernel(int *__restrict__ parent, int N)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const int p = parent[i];
-    if (p < 0 || p == i) return;
-    int r = p, q = parent[r];
-    while (q != r) {
-        r = q;
-        q = parent[r];
-    }
-    if (r != p) parent[i] = r;
 }
 
 // A rectangular view of a key map: key = keys[r * stride + c] + bias for r < h, c < w; the view stands for an Hr x Wr image (the
@@ -410,7 +397,7 @@ extern "C" int mlagg_cells_label(const void *seg, int elem_bytes, int foreground
     }
     {
         MLAGG_TIMED(K_CL_COMPRESS, st);
-        hipLaunchKernelGGL(cl_compress_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, parent, (int)N);
+        hipLaunchKernelGGL(mlagg_uf::compress_kernel<>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, parent, N);
     }
     return (int)hipGetLastError();
 }

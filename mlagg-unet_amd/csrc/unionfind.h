@@ -1,5 +1,6 @@
-// Union-find device helpers shared by K23 (components.hip) and K27 (cells.hip): Playne-Hawick linking, atomicMin always links the
-// larger root to the smaller one, so every set's root is its minimum index whatever the schedule.
+// Union-find on the device, shared by the 3-D labelling of cc_label.h (K23 components.hip, K30 cascade_aug.hip) and the 2-D one of
+// K27 (cells.hip): Playne-Hawick linking, atomicMin always links the larger root to the smaller one, so every set's root is its
+// minimum index whatever the schedule.  The find / unite helpers, and the two kernels that finish a labelling once every link is made.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,6 +59,40 @@ __device__ inline void gunite(int *par, int a, int b)
         if (old == b) return;
         b = old;
     }
+}
+
+// The kernels below work on grid.y planes of N elements each, 256 per workgroup along grid.x.
+
+// parent[v] = find(v); -1 (outside the mask) stays
+template <int UNUSED = 0>              // a template only so that the header can hold the definition
+__global__ void __launch_bounds__(256) compress_kernel(int *__restrict__ parent, long long N)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    parent += blockIdx.y * N;
+    const int p = parent[i];
+    if (p < 0 || p == i) return;
+    int r = p, q = parent[r];
+    while (q != r) {
+        r = q;
+        q = parent[r];
+    }
+    if (r != p) parent[i] = r;
+}
+
+// size[] holds partial counts at the roots of the trees that were united (0 elsewhere); after compress_kernel each adds its count
+// into its set's root: one global integer atomic per partial count, not one per element
+template <int UNUSED = 0>
+__global__ void __launch_bounds__(256) size_kernel(const int *__restrict__ parent, int *__restrict__ size, long long N)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    parent += blockIdx.y * N;
+    size += blockIdx.y * N;
+    const int s = size[i];
+    if (s == 0) return;
+    const int r = parent[i];
+    if (r != i) atomicAdd(&size[r], s);               // a set's root keeps its own count in place
 }
 
 }  // namespace mlagg_uf

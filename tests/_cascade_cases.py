@@ -141,6 +141,19 @@ def component_planes():
     return np.stack([a, b])
 
 
+def small_component_planes():
+    """{name: (1, X, Y, Z) planes} at the edges of the labelling's 8 x 8 x 32 tile and of the 64-bit word, next to the ragged
+    COMPONENT_SHAPE"""
+    chain = np.zeros((16, 8, 128), dtype=bool)       # every extent a multiple of the tile and of the word
+    chain[7, 7, 20:32] = True                        # ... (7, 7, 31) -> (8, 6, 32): across the tile corner, diagonally
+    chain[8, 6, 32:64] = True                        # ... (8, 6, 63) -> (9, 7, 64): across the word border, diagonally
+    chain[9, 7, 64:100] = True
+    chain[0, 0, 0] = chain[15, 7, 127] = True        # two single voxels
+    return {"1x1x1": np.ones((1, 1, 1, 1), dtype=bool),
+            "8x8x32": np.ones((1, 8, 8, 32), dtype=bool),         # exactly one tile, no face and no tail
+            "16x8x128": chain[None]}
+
+
 def seg_from_planes(planes, labels):
     """int16 label map whose listed labels are the (disjoint) planes; elsewhere 0"""
     seg = np.zeros(planes.shape[1:], dtype=np.int16)

@@ -130,19 +130,38 @@ def test_batched_samples_equal_single_samples():
     assert K.erosion(want[1, 2], far).all()                     # what a planning-time emptiness check would have produced
 
 
-def test_component_removal_matches_the_oracle():
-    planes = K.component_planes()
-    X, Y, Z = K.COMPONENT_SHAPE
-    thresh = float(np.prod(K.COMPONENT_SHAPE, dtype=np.uint64) * 0.15)
-    pool = _pack(planes)
-    state, table = ops.cascade_cc_stats(pool, Z, thresh)
+def _check_labelling(planes):
+    """cascade_cc_stats of (P, X, Y, Z) non-empty planes against scipy's labelling: the table, parent = each component's first voxel
+    in raster order, size at every root = the component's voxel count.  Returns (state, [(label map, valid ids)])."""
+    Z = planes.shape[3]
+    thresh = float(np.prod(planes.shape[1:], dtype=np.uint64) * 0.15)
+    state, table = ops.cascade_cc_stats(_pack(planes), Z, thresh)
     valid = [K.valid_components(p) for p in planes]
     assert table.cpu().tolist() == [[1, len(v)] for _, v in valid]
-    # the parent map: every voxel's root is its component's first voxel in raster order
     parent = state[0].cpu().numpy().reshape(planes.shape)
-    for p, (lab, _) in zip(range(2), valid):
+    size = state[1].cpu().numpy().reshape(planes.shape)
+    for p, (lab, _) in enumerate(valid):
         first = np.array([-1] + [np.flatnonzero(lab.ravel() == i)[0] for i in range(1, lab.max() + 1)])
         assert np.array_equal(parent[p], first[lab])
+        assert np.array_equal(size[p].ravel()[first[1:]], np.bincount(lab.ravel())[1:])
+    return state, valid
+
+
+@pytest.mark.parametrize("case", list(K.small_component_planes()))
+def test_labelling_at_tile_and_word_edges(case):
+    planes = K.small_component_planes()[case]
+    state, valid = _check_labelling(planes)
+    if case == "8x8x32":                                        # one component of 2048 rooted at 0
+        assert int(state[0].max()) == 0 and int(state[1][0, 0]) == 2048
+    if case == "16x8x128":                                      # the chain is one component, beside the two single voxels
+        assert valid[0][0].max() == 3
+
+
+def test_component_removal_matches_the_oracle():
+    planes = K.component_planes()
+    Z = K.COMPONENT_SHAPE[2]
+    state, valid = _check_labelling(planes)
+    thresh = state[3]                                           # the threshold _check_labelling labelled with
     for k in range(len(valid[0][1])):
         for fill in (0, 1):
             pool = _pack(planes)

@@ -123,6 +123,23 @@ def test_serpentine_component_crossing_every_tile(shape):
 
 
 @gpu
+def test_k23_and_k30_run_one_labelling():
+    """both callers of csrc/cc_label.h on the same (10, 17, 70) masks: the largest component's size"""
+    from scipy import ndimage as ndi
+    from tests import _cascade_cases as K
+    for mask in K.component_planes():
+        v = mask.astype(np.uint8)
+        got, stats, host = _device_and_host(v, {1: 1})
+        assert np.array_equal(got, host)
+        planes = ops.cascade_pack(torch.from_numpy(v.astype(np.int16)).to(DEV)[None], [1])[0]
+        (parent, size, _, _), _ = ops.cascade_cc_stats(planes, v.shape[2], 0.0)
+        parent, size = parent[0].cpu().numpy(), size[0].cpu().numpy()
+        lab, _ = ndi.label(mask, structure=np.ones((3, 3, 3)))
+        largest = np.bincount(lab.ravel())[1:].max()
+        assert stats[1, 1] == largest and size[parent == np.arange(parent.size)].max() == largest
+
+
+@gpu
 @pytest.mark.parametrize("shape", [(33, 40, 68), (30, 17, 45)])
 def test_lattice_connected_only_through_corners(shape):
     i, j, k = np.indices(shape)
