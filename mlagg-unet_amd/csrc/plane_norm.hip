@@ -101,17 +101,19 @@ plane_norm_fwd_kernel(PNF a)
     }
     for (long i = 4 * n4 + threadIdx.x; i < HW; i += 256) { const float d = ld1(xp, i, a.xdt) - mean; q += d * d; }
     const float rstd = rsqrtf(block_sum(q, red) / (float)HW + a.eps);
-    const float ga = (a.gamma ? a.gamma[c] : 1.f) * rstd, be = (a.beta ? a.beta[c] : 0.f) - mean * ga;
+    // y = (x - mean) * ga + be in every forward kernel, never x * ga + (be - mean * ga): folding the mean into the offset rounds at
+    // |mean| * rstd * gamma (a one-pixel plane has rstd = eps^-1/2 = 316: 3e-5 of the output, where the exact result is beta)
+    const float ga = (a.gamma ? a.gamma[c] : 1.f) * rstd, be = a.beta ? a.beta[c] : 0.f;
     const int act = a.act;
     const float slope = a.slope;
     for (long i = threadIdx.x; i < n4; i += 256) {
         const float4 v = ld4(xp, i, a.xdt);
         const float4 r = rp ? ld4(rp, i, a.rdt) : make_float4(0.f, 0.f, 0.f, 0.f);
-        st4(yp, i, a.ydt, make_float4(act_fwd(v.x * ga + be + r.x, act, slope), act_fwd(v.y * ga + be + r.y, act, slope),
-                                      act_fwd(v.z * ga + be + r.z, act, slope), act_fwd(v.w * ga + be + r.w, act, slope)));
+        st4(yp, i, a.ydt, make_float4(act_fwd((v.x - mean) * ga + be + r.x, act, slope), act_fwd((v.y - mean) * ga + be + r.y, act, slope),
+                                      act_fwd((v.z - mean) * ga + be + r.z, act, slope), act_fwd((v.w - mean) * ga + be + r.w, act, slope)));
     }
     for (long i = 4 * n4 + threadIdx.x; i < HW; i += 256)
-        st1(yp, i, a.ydt, act_fwd(ld1(xp, i, a.xdt) * ga + be + (rp ? ld1(rp, i, a.rdt) : 0.f), act, slope));
+        st1(yp, i, a.ydt, act_fwd((ld1(xp, i, a.xdt) - mean) * ga + be + (rp ? ld1(rp, i, a.rdt) : 0.f), act, slope));
     if (threadIdx.x == 0) { a.stats[2 * plane] = mean; a.stats[2 * plane + 1] = rstd; }
 }
 
@@ -226,7 +228,7 @@ __device__ __forceinline__ float block_sum_nt(float v, float *red)
 constexpr int NV = 16;
 
 template <int NT>
-__global__ void __launch_bounds__(NT)
+__global__ void __launch_bounds__(NT, NT == 256 ? 5 : 4)          // (threads, waves per SIMD): 96 VGPRs keep 5 workgroups of 256 on a CU
 plane_norm_fwd_reg_kernel(PNF a)
 {
     __shared__ float red[NT / 64];
@@ -249,12 +251,12 @@ plane_norm_fwd_reg_kernel(PNF a)
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         if (threadIdx.x + i * NT < n4) {
-            const float d0 = v[i].x - mean, d1 = v[i].y - mean, d2 = v[i].z - mean, d3 = v[i].w - mean;
-            q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+            v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;          // the registers keep x - mean from here on
+            q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
         }
     }
     const float rstd = rsqrtf(block_sum_nt<NT>(q, red) / (float)HW + a.eps);
-    const float ga = (a.gamma ? a.gamma[c] : 1.f) * rstd, be = (a.beta ? a.beta[c] : 0.f) - mean * ga;
+    const float ga = (a.gamma ? a.gamma[c] : 1.f) * rstd, be = a.beta ? a.beta[c] : 0.f;
     const int act = a.act;
     const float slope = a.slope;
 #pragma unroll
@@ -334,7 +336,7 @@ plane_split_apply_kernel(PNF a, const float *__restrict__ partial, int S)
     const float slope = a.slope;
     float mean, rstd;
     pooled_stats(partial, plane, S, HW, a.eps, red, mean, rstd);
-    const float ga = (a.gamma ? a.gamma[c] : 1.f) * rstd, be = (a.beta ? a.beta[c] : 0.f) - mean * ga;
+    const float ga = (a.gamma ? a.gamma[c] : 1.f) * rstd, be = a.beta ? a.beta[c] : 0.f;
     const void *xp = plane_ptr(a.x, plane, HW, a.xdt);
     void *yp = plane_ptr(a.y, plane, HW, a.ydt);
     const bool has_res = a.res != nullptr;
@@ -354,8 +356,8 @@ plane_split_apply_kernel(PNF a, const float *__restrict__ partial, int S)
         const long idx = threadIdx.x + i * 256;
         if (idx < cnt) {
             const float r0 = has_res ? r[i].x : 0.f, r1 = has_res ? r[i].y : 0.f, r2 = has_res ? r[i].z : 0.f, r3 = has_res ? r[i].w : 0.f;
-            st4(yp, lo + idx, a.ydt, make_float4(act_fwd(v[i].x * ga + be + r0, act, slope), act_fwd(v[i].y * ga + be + r1, act, slope),
-                                                 act_fwd(v[i].z * ga + be + r2, act, slope), act_fwd(v[i].w * ga + be + r3, act, slope)));
+            st4(yp, lo + idx, a.ydt, make_float4(act_fwd((v[i].x - mean) * ga + be + r0, act, slope), act_fwd((v[i].y - mean) * ga + be + r1, act, slope),
+                                                 act_fwd((v[i].z - mean) * ga + be + r2, act, slope), act_fwd((v[i].w - mean) * ga + be + r3, act, slope)));
         }
     }
     if (seg == 0 && threadIdx.x == 0) { stats[2 * plane] = mean; stats[2 * plane + 1] = rstd; }
