@@ -682,8 +682,23 @@ int mlagg_adamw_clip_step_dev(const void *tensor_table, const void *work_list, i
  *             the overlapping tiles accumulate in the reference's order, whatever the chunking.
  *   finalize: logits (K, X0, Y0, Z0) = acc / w on the region starting at (lx, ly, lz), contiguous (:203, :206); labels
  *             (X0, Y0, Z0) int64 = argmax over K with torch.argmax's first-maximum rule, or NULL.
+ *
+ * K32: the gather of a cascaded stage (3d_cascade_fullres).  The reference stacks the one-hot encoding of the previous stage's
+ * segmentation below the image channels, `np.vstack((data, seg_onehot))` with `result[i] = seg == l`
+ * (inference/predict_from_raw_data.py:47-67, utilities/label_handling/label_handling.py:266-270, and nnUNetTrainer.py:1099-1101 in
+ * validation; the segmentation comes from inference/export_prediction.py:74-106), and cuts tiles from that volume of 4 L X Y Z bytes.
+ *   gather_onehot: vol (C, X, Y, Z) fp32 and seg (X, Y, Z) contiguous labels of seg_kind (MLAGG_SEG_INT8 / _UINT8 / _INT16, read as
+ *             they are: any byte alignment, no conversion pass) -> out (V * n, C + L, tx, ty, tz).  Channels 0 .. C-1 are those of
+ *             gather, bit for bit; channel C + i is 1.0f where the label at the same (flipped) source voxel equals labels[i], else
+ *             0.0f.  labels: HOST array of L values in 1 .. 255, 1 <= L <= MLAGG_CASCADE_MAX_LABELS (64).  origins, flips, V as in
+ *             gather.  Every label is read once for its L outputs; the one-hot volume never exists.
  * No atomics: bit-reproducible.
  * ------------------------------------------------------------------------------------------ */
+#define MLAGG_SEG_INT8  0
+#define MLAGG_SEG_UINT8 1
+#define MLAGG_SEG_INT16 2
+int mlagg_sw_gather_onehot(const float *vol, int C, const void *seg, int seg_kind, const int *labels, int L, int X, int Y, int Z,
+                           const int *origins, int n, const int *flips, int V, float *out, int tx, int ty, int tz, void *stream);
 int mlagg_sw_gather(const float *vol, int C, int X, int Y, int Z, const int *origins, int n, const int *flips, int V, float *out,
                     int tx, int ty, int tz, void *stream);
 int mlagg_sw_fold(const float *out, int tile, int n, const int *flips, int V, int K, const float *gauss, int tx, int ty, int tz,

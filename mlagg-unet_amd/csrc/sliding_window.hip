@@ -1,4 +1,6 @@
 // K20 -- 3-D sliding-window inference: tile gather with mirror variants, Gaussian fold, finalize (+ argmax).
+// K32 -- the same gather for a cascaded stage: the one-hot channels of the previous stage's label map are written next to the
+//        image channels of every tile, from the label map itself (no one-hot volume).
 //
 // What it replaces: the per-tile tensor traffic of the reference's predict_sliding_window_return_logits for 3-D tiles
 // (nnunetv2/inference/sliding_window_prediction.py:60-210):
@@ -8,6 +10,10 @@
 //            predicted_logits / n_predictions (:200-201), one launch per tile so the overlapping tiles accumulate in tile order;
 //   finalize `predicted_logits /= n_predictions` (:203) and the crop of the padding (:206), into a contiguous tensor, optionally
 //            with the argmax labels of the segmentation.
+//   gather_onehot  the gather on `np.vstack((data, seg_onehot))` of the cascade's second stage (predict_from_raw_data.py:57-60,
+//            convert_labelmap_to_one_hot label_handling.py:266-270, nnUNetTrainer.py:1099-1101) without that stack: a tile's image
+//            rows are copied as in gather, and one block per (variant, tile, x, y) row of the LABEL MAP reads its Z run once and
+//            writes the L rows `label == labels[i]` of the one-hot channels.
 //
 // Layouts (fp32, Z the contiguous axis everywhere):
 //   volume (C, X, Y, Z) padded input; chunk input / output (V * n, C|K, tx, ty, tz), variant-major then tile;
@@ -57,6 +63,48 @@ __global__ void __launch_bounds__(SW_WAVE) sw_gather_kernel(const float *__restr
         for (int z = threadIdx.x; z < tz; z += SW_WAVE) dst[z] = src[tz - 1 - z];
     } else {
         for (int z = threadIdx.x; z < tz; z += SW_WAVE) dst[z] = src[z];
+    }
+}
+
+struct OneHotArgs {
+    unsigned char labels[MLAGG_CASCADE_MAX_LABELS];
+};
+
+// one block per row (b, c, x, y) with c in 0 .. C: c < C is sw_gather_kernel's copy of image channel c into a (C + L)-channel tile;
+// c == C owns the same row of the label map (S: int8, uint8 or int16, any byte alignment: one element per lane) and writes the
+// rows of output channels C .. C + L - 1, so every label is read once for its L outputs.  Coalesced 256-byte stores per channel row.
+template <typename S>
+__global__ void __launch_bounds__(SW_WAVE) sw_gather_onehot_kernel(const float *__restrict__ vol, const S *__restrict__ seg,
+                                                                   float *__restrict__ out, GatherArgs a, OneHotArgs h, int C, int L,
+                                                                   int X, int Y, int Z, int tx, int ty, int tz, int n, int i0,
+                                                                   int nsub)
+{
+    int r = blockIdx.x;
+    const int y = r % ty;
+    r /= ty;
+    const int x = r % tx;
+    r /= tx;
+    const int c = r % (C + 1);
+    const int b = r / (C + 1);
+    const int v = b / nsub, i = b % nsub;
+    const int m = a.flips[v];
+    const int sx = a.ox[i] + ((m & 1) ? tx - 1 - x : x);
+    const int sy = a.oy[i] + ((m & 2) ? ty - 1 - y : y);
+    const size_t T = (size_t)tx * ty * tz;
+    float *dst = out + (((size_t)v * n + i0 + i) * (C + L) + c) * T + ((size_t)x * ty + y) * tz;
+    if (c < C) {
+        const float *src = vol + (((size_t)c * X + sx) * Y + sy) * (size_t)Z + a.oz[i];
+        if (m & 4) {
+            for (int z = threadIdx.x; z < tz; z += SW_WAVE) dst[z] = src[tz - 1 - z];
+        } else {
+            for (int z = threadIdx.x; z < tz; z += SW_WAVE) dst[z] = src[z];
+        }
+        return;
+    }
+    const S *src = seg + ((size_t)sx * Y + sy) * (size_t)Z + a.oz[i];
+    for (int z = threadIdx.x; z < tz; z += SW_WAVE) {
+        const int label = (int)src[(m & 4) ? tz - 1 - z : z];
+        for (int k = 0; k < L; ++k) dst[(size_t)k * T + z] = label == (int)h.labels[k] ? 1.0f : 0.0f;
     }
 }
 
@@ -163,6 +211,52 @@ extern "C" int mlagg_sw_gather(const float *vol, int C, int X, int Y, int Z, con
         }
         const unsigned rows = (unsigned)((long long)V * nsub * C * tx * ty);
         hipLaunchKernelGGL(sw_gather_kernel, dim3(rows), dim3(SW_WAVE), 0, st, vol, out, a, C, X, Y, Z, tx, ty, tz, n, i0, nsub);
+        if (int rc = (int)hipGetLastError()) return rc;
+    }
+    return 0;
+}
+
+extern "C" int mlagg_sw_gather_onehot(const float *vol, int C, const void *seg, int seg_kind, const int *labels, int L, int X, int Y,
+                                      int Z, const int *origins, int n, const int *flips, int V, float *out, int tx, int ty, int tz,
+                                      void *stream)
+{
+    if (!vol || !out || !origins || !seg || !labels) return MLAGG_E_NULLPTR;
+    if (int rc = check_flips(flips, V)) return rc;
+    if (C < 1 || X < 1 || Y < 1 || Z < 1 || n < 1 || tx < 1 || ty < 1 || tz < 1) return MLAGG_E_UNSUPPORTED;
+    if (seg_kind != MLAGG_SEG_INT8 && seg_kind != MLAGG_SEG_UINT8 && seg_kind != MLAGG_SEG_INT16) return MLAGG_E_UNSUPPORTED;
+    if (L < 1 || L > MLAGG_CASCADE_MAX_LABELS) return MLAGG_E_UNSUPPORTED;
+    OneHotArgs h;
+    for (int k = 0; k < MLAGG_CASCADE_MAX_LABELS; ++k) {
+        if (k < L && (labels[k] < 1 || labels[k] > 255)) return MLAGG_E_UNSUPPORTED;
+        h.labels[k] = k < L ? (unsigned char)labels[k] : 0;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int *o = origins + 3 * i;
+        if (o[0] < 0 || o[1] < 0 || o[2] < 0 || o[0] + tx > X || o[1] + ty > Y || o[2] + tz > Z) return MLAGG_E_UNSUPPORTED;
+    }
+    if ((long long)V * SW_MAX_TILES * (C + 1) * tx * ty > 2147483647LL) return MLAGG_E_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MLAGG_TIMED(K_SW_GATHER_ONEHOT, st);
+    GatherArgs a;
+    for (int v = 0; v < SW_MAX_V; ++v) a.flips[v] = v < V ? flips[v] : 0;
+    for (int i0 = 0; i0 < n; i0 += SW_MAX_TILES) {
+        const int nsub = n - i0 < SW_MAX_TILES ? n - i0 : SW_MAX_TILES;
+        for (int i = 0; i < nsub; ++i) {
+            a.ox[i] = origins[3 * (i0 + i)];
+            a.oy[i] = origins[3 * (i0 + i) + 1];
+            a.oz[i] = origins[3 * (i0 + i) + 2];
+        }
+        for (int i = nsub; i < SW_MAX_TILES; ++i) a.ox[i] = a.oy[i] = a.oz[i] = 0;
+        const dim3 grid((unsigned)((long long)V * nsub * (C + 1) * tx * ty)), block(SW_WAVE);
+        if (seg_kind == MLAGG_SEG_INT8)
+            hipLaunchKernelGGL(sw_gather_onehot_kernel<signed char>, grid, block, 0, st, vol, static_cast<const signed char *>(seg),
+                               out, a, h, C, L, X, Y, Z, tx, ty, tz, n, i0, nsub);
+        else if (seg_kind == MLAGG_SEG_UINT8)
+            hipLaunchKernelGGL(sw_gather_onehot_kernel<unsigned char>, grid, block, 0, st, vol,
+                               static_cast<const unsigned char *>(seg), out, a, h, C, L, X, Y, Z, tx, ty, tz, n, i0, nsub);
+        else
+            hipLaunchKernelGGL(sw_gather_onehot_kernel<short>, grid, block, 0, st, vol, static_cast<const short *>(seg), out, a, h,
+                               C, L, X, Y, Z, tx, ty, tz, n, i0, nsub);
         if (int rc = (int)hipGetLastError()) return rc;
     }
     return 0;

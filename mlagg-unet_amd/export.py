@@ -19,6 +19,13 @@ same fp32 resampled logits bit for bit.
 Region-based label managers (sigmoid heads, dataset.json with tuple-valued labels and a regions_class_order) take step 2 in the form of
 label_handling.py:46-47, 166-173: the fp32 sigmoid of every head, and a label that starts at 0 and takes regions_class_order[i] wherever
 sigmoid_i > 0.5, for i in order -- the last match wins.  K21 has a region mode for it (mlagg_export_segmentation_regions).
+
+The cascade's hand-off out of a low-resolution stage (export_prediction.py:74-106, called per validation case by
+nnUNetTrainer.perform_actual_validation :1146-1181) is the same computation with another target: the logits are resampled to the shape
+the NEXT stage's preprocessing gives the case and turned into labels there, without paste or transpose.  resample_logits_to_next_stage
+does it (K21 with an empty border on the device), resample_and_save is the reference's drop-in that writes the .npz
+dataloading.Dataset(folder_with_segs_from_previous_stage=...) reads, and next_stage_target_shape computes that shape from the case's
+properties, for a caller that has no preprocessed next-stage file at hand.
 """
 import json
 import os
@@ -259,6 +266,47 @@ def convert_predicted_logits_to_segmentation_with_correct_shape(logits, properti
     return _finish(resampled, crop, full, lo, perm, return_probabilities, regions_class_order)
 
 
+def resample_logits_to_next_stage(logits, target_shape, configuration_spacing, properties, regions_class_order=None, order=1,
+                                  order_z=0, force_separate_z=None):
+    """The computation of the reference's resample_and_save (export_prediction.py:74-106): logits (K, x, y, z) of this (low-resolution)
+    configuration -> the uint8 segmentation (*target_shape) in the next stage's preprocessed geometry, on the logits' device.  As in
+    the reference, the current AND the new spacing handed to the resampler are this configuration's spacing (with properties['spacing'][0]
+    in front of a 2-value spacing), so the separate-z decision depends on it alone.  A device tensor takes K21 (the fused kernel with
+    box (0, 0, 0), shape target_shape and the identity transpose; above 32 classes the resampling kernel and torch's softmax / argmax),
+    a CPU tensor or numpy array the host path."""
+    logits = _as_logits(logits)
+    target = tuple(int(s) for s in target_shape)
+    if len(target) != 3 or min(target) < 1:
+        raise RuntimeError(f"target_shape {tuple(target_shape)}: three positive sizes expected")
+    if logits.shape[0] > 256:
+        raise RuntimeError(f"{logits.shape[0]} classes do not fit the uint8 segmentation")
+    spacing = current_spacing_for(configuration_spacing, properties)
+    kinds = resampling_plan(logits.shape[1:], target, spacing, spacing, order, order_z, force_separate_z)
+    taps = build_taps(logits.shape[1:], target, kinds)
+    origin, identity = (0, 0, 0), (0, 1, 2)
+    if logits.is_cuda:
+        from . import ops
+        if logits.shape[0] <= ops.EXPORT_MAX_CLASSES:
+            return ops.export_segmentation(logits, taps, target, origin, target, identity, False, regions_class_order)[0]
+        resampled = logits if kinds is None else ops.resample_linear(logits, taps, target)
+    else:
+        resampled = logits if kinds is None else _resample_host(logits, taps, target)
+    return _finish(resampled, target, target, origin, identity, False, regions_class_order)[0]
+
+
+def next_stage_target_shape(properties, plans, next_configuration):
+    """The spatial shape preprocessing.preprocess_case of `next_configuration` gives the case whose (preprocessed) properties these
+    are: compute_new_shape of shape_after_cropping_and_before_resampling under the transposed original spacing and the next
+    configuration's spacing (default_preprocessor.py:75-81) -- resample_and_save's target_shape, which the reference reads from the
+    next stage's preprocessed file (nnUNetTrainer.py:1166-1172)."""
+    from . import preprocessing
+    tf = [int(t) for t in plans.get("transpose_forward", [0, 1, 2])]
+    original_spacing = [float(properties["spacing"][i]) for i in tf]
+    cfg = preprocessing.get_configuration(plans, next_configuration)
+    shape = tuple(int(s) for s in properties["shape_after_cropping_and_before_resampling"])
+    return tuple(int(s) for s in preprocessing._target_shape(cfg, shape, original_spacing)[1])
+
+
 def region_order_of(label_manager):
     """regions_class_order of a region-based label manager, None for a label-based one."""
     if not getattr(label_manager, "has_regions", False):
@@ -305,3 +353,28 @@ def export_prediction_from_softmax(predicted_array_or_file, properties_dict, con
         del probs
     rw = plans_manager.image_reader_writer_class()
     rw.write_seg(seg.cpu().numpy(), output_file_truncated + dataset_json_dict_or_file["file_ending"], properties_dict)
+
+
+def resample_and_save(predicted, target_shape, output_file, plans_manager, configuration_manager, properties_dict,
+                      dataset_json_dict_or_file, next_configuration):
+    """Drop-in for the reference's resample_and_save (export_prediction.py:74-106), same arguments: the logits of a low-resolution
+    stage (a device tensor, a CPU tensor, a numpy array or a .npy file, removed after loading) -> np.savez_compressed(output_file,
+    seg=uint8 (*target_shape)), the file dataloading.Dataset(folder_with_segs_from_previous_stage=...) reads.  Duck-typed as
+    export_prediction_from_softmax is; next_configuration is unused, as in the reference."""
+    if isinstance(predicted, str):
+        path = predicted
+        if not path.endswith(".npy") or not os.path.isfile(path):
+            raise RuntimeError(f"resample_and_save: {path} is no .npy file")
+        predicted = np.load(path)
+        os.remove(path)
+    if isinstance(dataset_json_dict_or_file, str):
+        with open(dataset_json_dict_or_file) as f:
+            dataset_json_dict_or_file = json.load(f)
+    regions_class_order = region_order_of(plans_manager.get_label_manager(dataset_json_dict_or_file))
+    kwargs = dict(getattr(configuration_manager, "configuration", {}).get("resampling_fn_probabilities_kwargs", {}) or {})
+    if kwargs.pop("is_seg", False):
+        raise NotImplementedError("the probability resampler must not be a segmentation resampler")
+    kwargs = {k: kwargs[k] for k in ("order", "order_z", "force_separate_z") if k in kwargs}
+    seg = resample_logits_to_next_stage(predicted, target_shape, configuration_manager.spacing, properties_dict,
+                                        regions_class_order=regions_class_order, **kwargs)
+    np.savez_compressed(output_file, seg=seg.cpu().numpy())

@@ -14,6 +14,11 @@ Same tiling, Gaussian importance map and mirror test-time augmentation as the re
 gather builds a chunk's network input with every mirror variant, one fold per tile sums the variants, scales by the Gaussian and
 accumulates in the reference's order, and one finalize divides, crops and (optionally) takes the argmax -- no flipped copy of an
 output, no transient, a contiguous result.  On a CPU device the same order runs as a torch composition (_sliding_window_3d_torch).
+
+A cascaded stage (3d_cascade_fullres) also sees the previous stage's segmentation, one-hot encoded below the image channels
+(predict_from_raw_data.py:47-67: `np.vstack((data, seg_onehot))`; nnUNetTrainer.py:1099-1101 in validation).  Both public functions
+take it as previous_stage_seg / cascade_labels: on the device the K32 gather writes a chunk's one-hot channels from the label map
+itself, so the 4 L x y z bytes of the one-hot volume are never allocated; on the host the stack is built and takes the torch path.
 """
 import numpy as np
 import torch
@@ -110,13 +115,56 @@ def _sliding_window_3d_torch(network, data, gaussian, places, flips, tile_size, 
     return logits, weight
 
 
+def one_hot(seg, labels, dtype=torch.float32):
+    """convert_labelmap_to_one_hot's numpy branch (label_handling.py:266-270): seg (x, y, z) -> (L, x, y, z), row i = seg == labels[i]."""
+    return torch.stack([seg == int(l) for l in labels]).to(dtype)
+
+
+_SEG_DTYPES = (torch.int8, torch.uint8, torch.int16)
+
+
+def _cascade_inputs(input_image, tile_size, previous_stage_seg, cascade_labels):
+    """The checks of the two cascade arguments -> (seg (x, y, z) int8 / uint8 / int16 tensor on its device, [labels]) or (None, None)."""
+    if previous_stage_seg is None and cascade_labels is None:
+        return None, None
+    if previous_stage_seg is None or cascade_labels is None:
+        raise RuntimeError("previous_stage_seg and cascade_labels go together: the segmentation of the previous stage and the "
+                           "foreground labels it is one-hot encoded with")
+    if len(tile_size) != 3:
+        raise RuntimeError("a previous-stage segmentation needs a 3-D tile_size: the cascade is 3-D only")
+    labels = [int(v) for v in cascade_labels]
+    if not labels or any(v < 1 or v > 255 for v in labels):
+        raise RuntimeError(f"cascade_labels {labels}: at least one foreground label, each in 1 .. 255")
+    seg = torch.as_tensor(previous_stage_seg)
+    if seg.dim() == 4 and seg.shape[0] == 1:
+        seg = seg[0]
+    if input_image.dim() != 4 or tuple(seg.shape) != tuple(input_image.shape[1:]):
+        raise RuntimeError(f"previous_stage_seg of shape {tuple(torch.as_tensor(previous_stage_seg).shape)} does not match the image "
+                           f"{tuple(input_image.shape)}: (x, y, z) or (1, x, y, z) expected")
+    if seg.dtype not in _SEG_DTYPES:
+        if seg.is_floating_point() and not bool((seg == seg.round()).all()):
+            raise RuntimeError("previous_stage_seg must hold integer values")
+        lo, hi = (int(v) for v in torch.aminmax(seg))
+        if lo < -32768 or hi > 32767:
+            raise RuntimeError(f"previous_stage_seg holds labels {lo} .. {hi}: -32768 .. 32767 expected")
+        seg = seg.to(torch.int16)
+    return seg, labels
+
+
 def _predict_3d(network, input_image, num_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch, device,
-                want_labels):
-    """(c, x, y, z) volume, 3-D tile -> (logits (K, x, y, z), labels (x, y, z) int64 or None), contiguous fp32 on `device`."""
+                want_labels, seg=None, labels=None):
+    """(c, x, y, z) volume, 3-D tile -> (logits (K, x, y, z), labels (x, y, z) int64 or None), contiguous fp32 on `device`.  seg
+    (x, y, z) / labels: the previous stage's segmentation of a cascaded stage, one-hot encoded below the image channels."""
     tile_size = tuple(int(t) for t in tile_size)
     flips = mirror_variants(mirror_axes)
-    data, revert = _pad_to_tile(torch.as_tensor(input_image, dtype=torch.float32), tile_size)
+    image = torch.as_tensor(input_image, dtype=torch.float32)
+    if seg is not None and device.type != "cuda":
+        image = torch.cat((image.to(device), one_hot(seg.to(device), labels)))          # the reference's stack
+    data, revert = _pad_to_tile(image, tile_size)
     data = data.to(device).contiguous()
+    if seg is not None and device.type == "cuda":
+        # zero wherever the image is zero-padded: foreground labels are >= 1, so the padded one-hot channels are 0 as in the reference
+        seg = _pad_to_tile(seg, tile_size)[0].to(device).contiguous()
     gaussian = compute_gaussian(tile_size).to(device) if use_gaussian else torch.ones(tile_size, device=device)
     steps = compute_steps_for_sliding_window(tuple(data.shape[1:]), tile_size, tile_step_size)
     places = [(sx, sy, sz) for sx in steps[0] for sy in steps[1] for sz in steps[2]]
@@ -131,7 +179,10 @@ def _predict_3d(network, input_image, num_heads, tile_size, mirror_axes, tile_st
     weight = torch.zeros((X, Y, Z), dtype=torch.float32, device=device)
     for i in range(0, len(places), tile_batch):
         chunk = places[i:i + tile_batch]
-        out = network(ops.sliding_window_gather(data, chunk, flips, tile_size))
+        if seg is None:
+            out = network(ops.sliding_window_gather(data, chunk, flips, tile_size))
+        else:
+            out = network(ops.sliding_window_gather_onehot(data, seg, labels, chunk, flips, tile_size))
         if isinstance(out, (list, tuple)):
             raise RuntimeError("the inference network must be built with enable_deep_supervision=False")
         if tuple(out.shape) != (len(flips) * len(chunk), num_heads) + tile_size:
@@ -143,28 +194,35 @@ def _predict_3d(network, input_image, num_heads, tile_size, mirror_axes, tile_st
 
 
 def _run_3d(network, input_image, num_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch, device,
-            want_labels):
+            want_labels, previous_stage_seg=None, cascade_labels=None):
     """Argument handling of the two public functions for a 3-D tile_size."""
+    input_image = torch.as_tensor(input_image)
     if input_image.dim() != 4:
         raise RuntimeError("input_image must be (c, x, y, z) for a 3-D tile_size")
+    seg, labels = _cascade_inputs(input_image, tile_size, previous_stage_seg, cascade_labels)
     tile_batch = 1 if tile_batch is None else int(tile_batch)
     if tile_batch < 1:
         raise RuntimeError("tile_batch must be at least 1")
     device = torch.device(device) if device is not None else next(network.parameters()).device
     network.eval()
     return _predict_3d(network, input_image, num_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch, device,
-                       want_labels)
+                       want_labels, seg, labels)
 
 
 @torch.no_grad()
 def predict_sliding_window_return_logits(network, input_image, num_segmentation_heads, tile_size, mirror_axes=None,
-                                         tile_step_size=0.5, use_gaussian=True, tile_batch=None, device=None):
+                                         tile_step_size=0.5, use_gaussian=True, tile_batch=None, device=None,
+                                         previous_stage_seg=None, cascade_labels=None):
     """input_image (c, D, X, Y) with a 2-D tile_size, or (c, x, y, z) with a 3-D tile_size -> fp32 logits
     (num_segmentation_heads, ...) on `device`.  `network(x)` must return a tensor (deep supervision disabled).  tile_batch: tiles per
-    network call (the batch is tile_batch * 2^|mirror_axes|); default 8 for 2-D tiles, 1 for 3-D tiles."""
+    network call (the batch is tile_batch * 2^|mirror_axes|); default 8 for 2-D tiles, 1 for 3-D tiles.
+    previous_stage_seg (integer-valued (x, y, z) or (1, x, y, z) tensor or array) with cascade_labels (foreground labels in
+    1 .. 255): a cascaded stage, 3-D tiles only -- the result equals the call on vstack((input_image, one_hot(seg, cascade_labels)));
+    on a CUDA device the K32 gather builds the one-hot channels of every chunk and that volume is never allocated."""
     if len(tile_size) == 3:
         return _run_3d(network, input_image, num_segmentation_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch,
-                       device, False)[0]
+                       device, False, previous_stage_seg, cascade_labels)[0]
+    _cascade_inputs(torch.as_tensor(input_image), tile_size, previous_stage_seg, cascade_labels)
     if tile_batch is None:
         tile_batch = 8
     if input_image.dim() != 4 or len(tile_size) != 2:
@@ -210,11 +268,13 @@ def predict_sliding_window_return_logits(network, input_image, num_segmentation_
 
 @torch.no_grad()
 def predict_sliding_window_return_segmentation(network, input_image, num_segmentation_heads, tile_size, mirror_axes=None,
-                                               tile_step_size=0.5, use_gaussian=True, tile_batch=None, device=None):
+                                               tile_step_size=0.5, use_gaussian=True, tile_batch=None, device=None,
+                                               previous_stage_seg=None, cascade_labels=None):
     """The int64 label map argmax_k(logits) of predict_sliding_window_return_logits (torch.argmax's first-maximum rule).  3-D tiles
     on the device take it from the finalize kernel, which writes it next to the logits without a second pass over them."""
     if len(tile_size) == 3:
         return _run_3d(network, input_image, num_segmentation_heads, tile_size, mirror_axes, tile_step_size, use_gaussian, tile_batch,
-                       device, True)[1]
+                       device, True, previous_stage_seg, cascade_labels)[1]
     return predict_sliding_window_return_logits(network, input_image, num_segmentation_heads, tile_size, mirror_axes,
-                                                tile_step_size, use_gaussian, tile_batch, device).argmax(0)
+                                                tile_step_size, use_gaussian, tile_batch, device, previous_stage_seg,
+                                                cascade_labels).argmax(0)

@@ -2737,6 +2737,33 @@ def sliding_window_gather(volume, origins, flips, tile_size):
     return out
 
 
+SW_SEG_KINDS = {torch.int8: _C["MLAGG_SEG_INT8"], torch.uint8: _C["MLAGG_SEG_UINT8"], torch.int16: _C["MLAGG_SEG_INT16"]}
+
+
+def sliding_window_gather_onehot(volume, seg, labels, origins, flips, tile_size):
+    """K32: volume (C, X, Y, Z) fp32 and seg (X, Y, Z) int8 / uint8 / int16 labels -> network input (V * n, C + L, tx, ty, tz) of a
+    cascaded stage: channels 0 .. C-1 as sliding_window_gather, channel C + i the fp32 indicator seg == labels[i] of the same
+    (flipped) voxels.  labels: L values in 1 .. 255, L <= 64.  The one-hot volume is never built."""
+    _expect(volume, "volume", dim=4)
+    if not isinstance(seg, torch.Tensor) or seg.dtype not in SW_SEG_KINDS:
+        raise RuntimeError(f"seg: expected an int8, uint8 or int16 tensor, got {getattr(seg, 'dtype', type(seg))}")
+    _expect(seg, "seg", dtype=seg.dtype, shape=volume.shape[1:], like=volume)
+    flips = _sw_flips(flips)
+    tile = tuple(int(t) for t in tile_size)
+    if len(tile) != 3 or min(tile) < 1:
+        raise RuntimeError(f"tile_size {tile_size}: three positive sides")
+    labels = [int(v) for v in labels]
+    C, X, Y, Z = volume.shape
+    boxes = [_sw_box(o, tile, (X, Y, Z), "sliding_window_gather_onehot") for o in origins]
+    if not boxes:
+        raise RuntimeError("sliding_window_gather_onehot: no tiles")
+    out = torch.empty((len(flips) * len(boxes), C + len(labels)) + tile, device=volume.device, dtype=torch.float32)
+    # the entry refuses an empty or too long label list and labels outside 1 .. 255
+    _launch("mlagg_sw_gather_onehot", _ptr(volume), C, _ptr(seg), SW_SEG_KINDS[seg.dtype], _int_array(labels), len(labels), X, Y, Z,
+            _int_array([v for o in boxes for v in o]), len(boxes), _int_array(flips), len(flips), _ptr(out), *tile)
+    return out
+
+
 def sliding_window_fold(out, tile, n, flips, gaussian, origin, acc, weight):
     """Fold tile `tile` of the chunk output out (V * n, K, tx, ty, tz) into acc (K, X, Y, Z) and weight (X, Y, Z) at `origin`:
     acc += mean over the variants of the flipped-back outputs * gaussian, weight += gaussian (in place)."""

@@ -2,7 +2,8 @@
 (mlagg/nnunetv2/preprocessing/preprocessors/default_preprocessor.py:38-124) with the default plans: transpose by transpose_forward,
 crop to the non-zero box, normalise every channel, resample to the configuration's spacing with
 resample_data_or_seg_to_shape(order=3, order_z=0, force_separate_z=None) (default_experiment_planner.py:123-128).  preprocess_case
-does it for a test case (no segmentation); preprocess_training_case adds the segmentation (cropped with -1 outside the filled
+does it for a test case (no segmentation, or, for a cascaded configuration, the previous stage's segmentation as run_case's seg:
+inference/predict_from_raw_data.py:47-67); preprocess_training_case adds the segmentation (cropped with -1 outside the filled
 non-zero mask, resampled with resample_data_or_seg_to_shape(is_seg=True, order=1, order_z=0), :129-135) and the sampled
 class_locations (_sample_foreground_locations, :134-161); preprocess_dataset writes the case folder dataloading.Dataset reads.
 
@@ -20,10 +21,11 @@ to the rounding of numpy's fp32 mean / std (ZSCORE_TOLERANCE), since the device 
 host's except possibly where a label's interpolated indicator is within NEAR_TIE of the 0.5 threshold; class locations are
 integer work and identical for an identical segmentation.
 
-Not supported (NotImplementedError): cascade stages, region-based labels (regions_class_order or multi-value labels),
-preprocessors other than DefaultPreprocessor, data resamplers other than resample_data_or_seg_to_shape with order 3 and order_z 0 or
-1, segmentation resamplers other than resample_data_or_seg_to_shape with order 1 and order_z 0.  Experiment planning stays the
-reference's: the plans are an input (fingerprint.py computes the one entry CT normalisation needs).
+Not supported (NotImplementedError): training cases of cascaded configurations (previous_stage), region-based labels
+(regions_class_order or multi-value labels; with a cascade at prediction time too), preprocessors other than DefaultPreprocessor,
+data resamplers other than resample_data_or_seg_to_shape with order 3 and order_z 0 or 1, segmentation resamplers other than
+resample_data_or_seg_to_shape with order 1 and order_z 0.  Experiment planning stays the reference's: the plans are an input
+(fingerprint.py computes the one entry CT normalisation needs).
 File reading is the caller's: the input is the reader's (c, x, y, z) array and its properties (at least 'spacing').
 """
 import copy
@@ -90,8 +92,6 @@ def _check_orders(order, order_z):
 def _check_configuration(cfg, n_channels):
     if cfg.get("preprocessor_name", "DefaultPreprocessor") != "DefaultPreprocessor":
         raise NotImplementedError(f"preprocessor {cfg['preprocessor_name']}: only DefaultPreprocessor is implemented")
-    if cfg.get("previous_stage"):
-        raise NotImplementedError("cascade configurations (previous_stage) are not supported")
     schemes = list(cfg["normalization_schemes"])
     masks = list(cfg.get("use_mask_for_norm", [False] * len(schemes)))
     if len(schemes) < n_channels or len(masks) < n_channels:
@@ -356,31 +356,81 @@ def _target_shape(cfg, shape, original_spacing):
     return target, compute_new_shape(shape, original_spacing, target)
 
 
-def preprocess_case(image, properties, plans, configuration_name, device=None):
+def _check_previous_stage(cfg, seg_from_prev_stage, image):
+    """The checks of a cascaded prediction case -> the (1, x, y, z) view of the previous stage's segmentation, or None."""
+    if cfg.get("previous_stage") and seg_from_prev_stage is None:
+        # a NotImplementedError, which is a RuntimeError: without the segmentation the call asks for what a cascaded stage cannot do
+        raise NotImplementedError(f"a cascade configuration (previous_stage {cfg['previous_stage']!r}) needs seg_from_prev_stage: "
+                                  "the previous stage's segmentation of this case in the original geometry is missing")
+    if seg_from_prev_stage is None:
+        return None
+    if not cfg.get("previous_stage"):
+        raise RuntimeError("seg_from_prev_stage was given, but the configuration has no previous_stage: it is no cascaded stage")
+    seg = seg_from_prev_stage
+    if seg.ndim == 3:
+        seg = seg[None]
+    if seg.ndim != 4 or seg.shape[0] != 1 or tuple(seg.shape[1:]) != tuple(image.shape[1:]):
+        raise RuntimeError(f"preprocess_case: a (x, y, z) or (1, x, y, z) seg_from_prev_stage matching the image {tuple(image.shape)} "
+                           f"expected, got {tuple(seg_from_prev_stage.shape)}")
+    return seg
+
+
+def preprocess_case(image, properties, plans, configuration_name, device=None, seg_from_prev_stage=None, dataset_json=None):
     """DefaultPreprocessor.run_case for a test case: image (c, x, y, z) (numpy or tensor; cast to float32 as the reader delivers
     it), properties (the reader's, with 'spacing'), plans (the plans.json dict) -> (data (c, x', y', z') float32, a new properties
     dict with shape_before_cropping, bbox_used_for_cropping and shape_after_cropping_and_before_resampling).  A CUDA `device` (or a
-    device tensor when device is None) runs K22 and returns a device tensor; otherwise the host path returns a numpy array."""
+    device tensor when device is None) runs K22 and returns a device tensor; otherwise the host path returns a numpy array.
+
+    A cascaded configuration (previous_stage) takes seg_from_prev_stage, the previous stage's (x, y, z) or (1, x, y, z) label
+    volume in the ORIGINAL geometry (what predict_case of that stage returns), as run_case's seg (predict_from_raw_data.py:47-67):
+    transposed, cropped with the image's box (-1 outside the filled non-zero mask) and resampled as preprocess_training_case treats
+    a segmentation (K26 on the device); the masked ZScore takes seg >= 0 as its mask.  No class locations are sampled.
+    -> (data, seg (1, x', y', z') int8, or int16 with a label above 127, props).  dataset_json (its 'labels'; required on the
+    device): region-based labels are refused, and on the device labels outside -1 .. its largest label are."""
     cfg, dev, schemes, masks, fg, props, original_spacing, perm = _case_setup(image, properties, plans, configuration_name, device,
                                                                               "preprocess_case")
     order, order_z, force_separate_z, threshold = _data_resampling_kwargs(cfg)
+    max_label = None
+    if seg_from_prev_stage is not None or cfg.get("previous_stage"):
+        _, _, seg_force_separate_z, seg_threshold = _seg_resampling_kwargs(cfg)
+        if dataset_json is not None:
+            max_label = _label_lists(dataset_json)[1]              # refuses region-based labels
+    s = _check_previous_stage(cfg, seg_from_prev_stage, image)
+    if s is not None and dev is not None and max_label is None:
+        raise RuntimeError("preprocess_case: seg_from_prev_stage on the device needs dataset_json: its largest label bounds K26's tables")
     if dev is not None:
         x = torch.as_tensor(image).to(device=dev, dtype=torch.float32).permute(perm)
-        props["shape_before_cropping"] = tuple(int(s) for s in x.shape[1:])
-        data, bbox = _preprocess_device(x, schemes, masks, fg, dev)
+        props["shape_before_cropping"] = tuple(int(v) for v in x.shape[1:])
+        if s is None:
+            data, bbox = _preprocess_device(x, schemes, masks, fg, dev)
+        else:
+            s = _as_label_tensor(s, dev).permute(perm)
+            data, bbox, s, hist = _preprocess_device(x, schemes, masks, fg, dev, s[0], max_label)
+            s = s[None]
     else:
         x = image.cpu().numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
         x = np.array(x, dtype=np.float32).transpose(perm)
         props["shape_before_cropping"] = x.shape[1:]
-        data, seg, bbox = crop_to_nonzero(x)
+        if s is not None:
+            s = s.cpu().numpy() if isinstance(s, torch.Tensor) else np.asarray(s)
+            s = np.array(s, dtype=np.int16 if s.dtype.kind in "ub" else s.dtype).transpose(perm)      # -1 needs a signed dtype
+        data, seg, bbox = crop_to_nonzero(x, s)                 # seg: the cropped s, or the non-zero mask's stand-in without one
         data = np.array(data)
         for c in range(data.shape[0]):
             data[c] = _normalize_channel_host(data[c], seg[0], schemes[c], masks[c], fg.get(str(c), {}))
+        if s is not None:
+            s = seg
     props["bbox_used_for_cropping"] = bbox
-    props["shape_after_cropping_and_before_resampling"] = tuple(int(s) for s in data.shape[1:])
+    props["shape_after_cropping_and_before_resampling"] = tuple(int(v) for v in data.shape[1:])
     target, new_shape = _target_shape(cfg, data.shape[1:], original_spacing)
+    old_shape = tuple(int(v) for v in data.shape[1:])
     data = resample_data_to_shape(data, new_shape, original_spacing, target, order, order_z, force_separate_z, threshold)
-    return data, props
+    if s is None:
+        return data, props
+    sep, axis = separate_z_decision(original_spacing, target, seg_force_separate_z, seg_threshold)
+    s, hist = _resample_case_seg(s, old_shape, new_shape, sep, axis, hist if dev is not None else None, max_label,
+                                 "preprocess_case")
+    return data, _narrow_seg(s, hist), props
 
 
 # ------------------------------------------------------------------------------------------------
@@ -516,6 +566,31 @@ def resample_seg_to_shape(seg, new_shape, current_spacing, new_spacing, order=1,
     return _resample_seg_host(np.asarray(seg), new_shape, sep, axis)
 
 
+def _resample_case_seg(s, old_shape, new_shape, sep, axis, hist=None, max_label=None, what=None):
+    """A case's cropped segmentation (1, x, y, z) -> (the segmentation at new_shape, its label histogram on the host or None).  With
+    hist (the device path: K26's histogram of the crop) the labels are checked against -1 .. max_label on the way: the histogram's
+    read-back is the case's second and last."""
+    resize = tuple(int(v) for v in old_shape) != tuple(int(v) for v in new_shape)
+    if hist is None:
+        return (_resample_seg_host(s, new_shape, sep, axis) if resize else s), None
+    if resize:
+        foreign = hist[-1:]                                # a label outside the dataset's range may vanish in the resampling
+        s, hist = _resample_seg_device(s, new_shape, sep, axis, max_label)
+        hist[-1:] += foreign
+    hist = hist.cpu().numpy()
+    if hist[-1]:
+        raise RuntimeError(f"{what}: {int(hist[-1])} voxels carry a label outside -1 .. {max_label}, the largest label of dataset_json")
+    return s, hist
+
+
+def _narrow_seg(s, hist=None):
+    """run_case's last step (:120-123): int16 when a label above 127 is present, else int8; hist: the device path's histogram."""
+    if hist is None:
+        return s.astype(np.int16 if np.max(s) > 127 else np.int8)
+    present = np.flatnonzero(hist[:-1])
+    return s.to(torch.int16 if present.size and present[-1] - 1 > 127 else torch.int8)
+
+
 def _num_to_sample(n):
     """_sample_foreground_locations: at most 10000 voxels of a class, but at least 1 % of them."""
     return max(min(10000, n), int(np.ceil(n * 0.01)))
@@ -598,6 +673,8 @@ def preprocess_training_case(image, seg, properties, plans, configuration_name, 
                                                                               "preprocess_training_case")
     order, order_z, force_separate_z, threshold = _data_resampling_kwargs(cfg)
     _, _, seg_force_separate_z, seg_threshold = _seg_resampling_kwargs(cfg)
+    if cfg.get("previous_stage"):
+        raise NotImplementedError("training cases of cascade configurations (previous_stage) are not supported")
     collect, max_label = _label_lists(dataset_json)
     if seg.ndim != 4 or seg.shape[0] != 1 or tuple(seg.shape[1:]) != tuple(image.shape[1:]):
         raise RuntimeError(f"preprocess_training_case: a (1, x, y, z) segmentation matching the image {tuple(image.shape)} expected, "
@@ -624,25 +701,13 @@ def preprocess_training_case(image, seg, properties, plans, configuration_name, 
     old_shape = tuple(int(v) for v in data.shape[1:])
     data = resample_data_to_shape(data, new_shape, original_spacing, target, order, order_z, force_separate_z, threshold)
     sep, axis = separate_z_decision(original_spacing, target, seg_force_separate_z, seg_threshold)
-    resize = old_shape != tuple(int(v) for v in new_shape)
     if dev is not None:
-        if resize:
-            foreign = hist[-1:]                            # a label outside the dataset's range may vanish in the resampling
-            s, hist = _resample_seg_device(s, new_shape, sep, axis, max_label)
-            hist[-1:] += foreign
-        hist = hist.cpu().numpy()                          # the case's second and last read-back
-        if hist[-1]:
-            raise RuntimeError(f"preprocess_training_case: {int(hist[-1])} voxels carry a label outside -1 .. {max_label}, the "
-                               "largest label of dataset_json")
+        s, hist = _resample_case_seg(s, old_shape, new_shape, sep, axis, hist, max_label, "preprocess_training_case")
         props["class_locations"] = _sample_locations_device(s, collect, 1234, max_label, hist)
-        present = np.flatnonzero(hist[:-1])
-        s = s.to(torch.int16 if present.size and present[-1] - 1 > 127 else torch.int8)
     else:
-        if resize:
-            s = _resample_seg_host(s, new_shape, sep, axis)
+        s, hist = _resample_case_seg(s, old_shape, new_shape, sep, axis)
         props["class_locations"] = _sample_locations_host(s, collect, 1234)
-        s = s.astype(np.int16 if np.max(s) > 127 else np.int8)
-    return data, s, props
+    return data, _narrow_seg(s, hist), props
 
 
 def preprocess_dataset(cases, output_folder, plans, configuration_name, dataset_json, device=None, unpack=False):
