@@ -17,6 +17,8 @@ draws them, one sample after the other), the pixels never leave the device: ever
   * GaussianBlur: separable grouped convolution, scipy's "reflect" boundary, per-(sample, channel) sigma.
   * SimulateLowResolution: nearest down-sampling + cubic B-spline up-sampling on the half-pixel-centred grid of skimage.
   * Gamma (plain and inverted, retain_stats), Contrast (range-preserving), Brightness, Mirror, Gaussian noise: pointwise.
+The sampler (`sample`), the resampling tail (`resample`), the prefilter, the blur and the parameter draws take the number of axes:
+augmentation3d builds its 3-D and dummy-2-D chains on them.
 dataloading.to_device / PrefetchLoader(augmenter=...) run the chain between the H2D copy and the target pyramid
 (dataloading.targets_from_seg: label -1 -> 0, nearest down-sampling), on the loader's side stream.
 """
@@ -75,20 +77,35 @@ def _two_sided(rng, lo, hi):
 def draw_params(rng, batch, channels, rotation=(-math.pi, math.pi), mirror_axes=(0, 1)):
     """One parameter set per sample, drawn transform by transform in the order of get_training_transforms (B:690-733).
     Returns a dict of numpy arrays (`do_*`: whether the transform touches the sample / channel)."""
-    B, C = batch, channels
+    p = _param_table(batch, channels, 0, 2)
+    _draw_spatial(rng, p, (rotation,))
+    return _draw_intensity_and_mirror(rng, p, batch, channels, mirror_axes)
+
+
+def _param_table(B, C, angle_columns, mirror_columns):
+    """The parameters of a batch, every transform switched off; p["angle"] is (B,) for one angle (angle_columns 0), else
+    (B, angle_columns); p["mirror"] has one column per spatial axis."""
     p = {k: np.zeros(B, dtype=bool) for k in ("do_rot", "do_scale", "do_noise", "do_blur", "do_bright", "do_contrast", "do_lowres",
                                               "do_gamma_inv", "do_gamma")}
-    p.update(angle=np.zeros(B), scale=np.ones(B), noise_std=np.zeros(B), blur_ch=np.zeros((B, C), dtype=bool),
-             blur_sigma=np.ones((B, C)), bright=np.ones((B, C)), contrast=np.ones((B, C)), lowres_ch=np.zeros((B, C), dtype=bool),
-             lowres_zoom=np.ones((B, C)), gamma_inv=np.ones((B, C)), gamma=np.ones((B, C)), mirror=np.zeros((B, 2), dtype=bool))
-    for b in range(B):                                                     # SpatialTransform: p_rot 0.2, p_scale 0.2
+    p.update(angle=np.zeros((B, angle_columns) if angle_columns else B), scale=np.ones(B), noise_std=np.zeros(B),
+             blur_ch=np.zeros((B, C), dtype=bool), blur_sigma=np.ones((B, C)), bright=np.ones((B, C)), contrast=np.ones((B, C)),
+             lowres_ch=np.zeros((B, C), dtype=bool), lowres_zoom=np.ones((B, C)), gamma_inv=np.ones((B, C)), gamma=np.ones((B, C)),
+             mirror=np.zeros((B, mirror_columns), dtype=bool))
+    return p
+
+
+def _draw_spatial(rng, p, ranges):
+    """SpatialTransform's draws, p_rot 0.2 and p_scale 0.2: per sample, when rotation fires, one angle per (lo, hi) of `ranges`
+    (one in 2-D; about x, y, z in 3-D), each behind its own uniform() <= p_rot_per_axis; then the scale."""
+    angle = p["angle"].reshape(len(p["do_rot"]), -1)                        # a view: one column per angle
+    for b in range(len(angle)):
         if rng.uniform() < 0.2:
-            if rng.uniform() <= 1.0:                                       # p_rot_per_axis = 1 (B:670): drawn, always taken
-                p["angle"][b] = rng.uniform(rotation[0], rotation[1])
+            for ax, (lo, hi) in enumerate(ranges):
+                if rng.uniform() <= 1.0:                                   # p_rot_per_axis = 1 (B:670): drawn, always taken
+                    angle[b, ax] = rng.uniform(lo, hi)
             p["do_rot"][b] = True
         if rng.uniform() < 0.2:
             p["do_scale"][b], p["scale"][b] = True, _two_sided(rng, 0.7, 1.4)
-    return _draw_intensity_and_mirror(rng, p, B, C, mirror_axes)
 
 
 def _draw_intensity_and_mirror(rng, p, B, C, mirror_axes):
@@ -186,11 +203,15 @@ def _prefilter_matrix(n, device):
     return m
 
 
-def spline_coefficients(x):
-    """(.., H, W) image -> cubic B-spline coefficients with scipy's "mirror" boundary (what spline_filter computes for
-    mode "constant"): the recursive filter's impulse response decays as 0.268^|k|, so it is a 33-tap band matrix per axis."""
-    H, W = x.shape[-2:]
-    return _prefilter_matrix(H, x.device) @ x @ _prefilter_matrix(W, x.device).T
+def spline_coefficients(x, nd=2):
+    """(.., *sizes) image -> cubic B-spline coefficients along its last nd >= 2 axes with scipy's "mirror" boundary (what
+    spline_filter computes for mode "constant"): the recursive filter's impulse response decays as 0.268^|k|, so it is a 33-tap
+    band matrix per axis.  The last two axes are one left and one right product; an earlier one sees the later ones as columns."""
+    for ax in range(-nd, -2):
+        n = x.shape[ax]
+        x = (_prefilter_matrix(n, x.device) @ x.reshape(-1, n, math.prod(x.shape[ax + 1:]))).reshape(x.shape)
+    x = _prefilter_matrix(x.shape[-2], x.device) @ x                      # one statement per product: each input is released
+    return x @ _prefilter_matrix(x.shape[-1], x.device).T                  # before the next output is allocated
 
 
 def _mirror_index(i, n):
@@ -205,28 +226,30 @@ def _bspline3_weights(t):
 
 
 def sample(img, coords, order, cval):
-    """scipy.ndimage.map_coordinates(img, coords, order, mode="constant", cval) for a batch: img (B, C, H, W), coords
-    (B, 2, Ho, Wo) in pixel units (row, column) -> (B, C, Ho, Wo).  order 3 expects `img` to be spline coefficients.
-    All taps of all channels in one gather."""
-    B, C, H, W = img.shape
-    out_shape = coords.shape[2:]
-    y, x = coords[:, 0].reshape(B, -1), coords[:, 1].reshape(B, -1)                # (B, P)
-    inside = (y >= 0) & (y <= H - 1) & (x >= 0) & (x <= W - 1)
-    fy, fx = torch.floor(y), torch.floor(x)
-    ty, tx = y - fy, x - fx
-    if order == 3:
-        wy, wx, first, n = _bspline3_weights(ty), _bspline3_weights(tx), -1, 4      # (B, 4, P)
-    else:
-        wy, wx, first, n = torch.stack([1 - ty, ty], -2), torch.stack([1 - tx, tx], -2), 0, 2
+    """scipy.ndimage.map_coordinates(img, coords, order, mode="constant", cval) for a batch, in any number of axes: img
+    (B, C, *sizes), coords (B, nd, *out) in pixel units, one row per axis of `sizes`, fp32 or fp64 -> (B, C, *out).  order 3
+    expects `img` to be spline coefficients.  The fraction is fp32 whatever the coordinate type (as K25 and K31 form it).
+    All taps of all channels in one gather: the axes are folded in one after the other, the last one fastest."""
+    B, C = img.shape[:2]
+    first, n = (-1, 4) if order == 3 else (0, 2)
     taps = torch.arange(n, device=img.device).view(1, n, 1) + first
-    yi = _mirror_index(fy.long().unsqueeze(1) + taps, H)                            # (B, n, P)
-    xj = _mirror_index(fx.long().unsqueeze(1) + taps, W)
-    idx = (yi.unsqueeze(2) * W + xj.unsqueeze(1)).reshape(B, 1, -1)                 # (B, 1, n * n * P)
-    w = (wy.unsqueeze(2) * wx.unsqueeze(1)).reshape(B, 1, n * n, -1)
-    vals = img.reshape(B, C, H * W).gather(2, idx.expand(-1, C, -1)).view(B, C, n * n, -1)
-    out = (vals * w).sum(2)
+    for j, size in enumerate(img.shape[2:]):
+        c = coords[:, j].reshape(B, -1)                                             # (B, P)
+        f = torch.floor(c)
+        t = (c - f).float()
+        w_j = _bspline3_weights(t) if order == 3 else torch.stack([1 - t, t], -2)   # (B, n, P)
+        tap = _mirror_index(f.long().unsqueeze(1) + taps, size)
+        ok = (c >= 0) & (c <= size - 1)
+        if j == 0:
+            inside, idx, w = ok, tap, w_j
+        else:
+            inside = inside & ok
+            idx = (idx.unsqueeze(2) * size + tap.unsqueeze(1)).reshape(B, -1, c.shape[1])      # (B, n ** (j + 1), P)
+            w = (w.unsqueeze(2) * w_j.unsqueeze(1)).reshape(B, -1, c.shape[1])
+    vals = img.reshape(B, C, -1).gather(2, idx.reshape(B, 1, -1).expand(-1, C, -1)).view(B, C, *idx.shape[1:])
+    out = (vals * w.unsqueeze(1)).sum(2)
     out = torch.where(inside.unsqueeze(1), out, torch.full_like(out, cval))
-    return out.view(B, C, *out_shape)
+    return out.view(B, C, *coords.shape[2:])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -246,36 +269,81 @@ def spatial_transform(data, seg, patch_size, do, angle, scale, labels=None):
     # rotate_coords_2d: coords^T . [[cos, -sin], [sin, cos]]  -> y' = y cos + x sin, x' = -y sin + x cos; then * scale
     y = (cy * cos + cx * sin) * sc + (Hi / 2.0 - 0.5)
     x = (-cy * sin + cx * cos) * sc + (Wi / 2.0 - 0.5)
-    coords = torch.stack([y, x], 1)
-    out_d = sample(spline_coefficients(data), coords, 3, 0.0)
-    # segmentation: one linear interpolation per label value, ascending; the last label whose interpolated indicator reaches
-    # 0.5 is assigned, nothing where none does (interpolate_img, is_seg).  All indicator maps are channels of ONE gather.
-    if labels is None:
-        lab = torch.unique(seg)                                              # sorted; the dataset's label list avoids this pass
-    else:
-        lab = labels if torch.is_tensor(labels) else torch.tensor(sorted(labels), device=dev, dtype=seg.dtype)
-    onehot = (seg == lab.view(1, -1, 1, 1)).to(torch.float32)               # seg has one channel on this path
-    r = sample(onehot, coords, 1, -1.0)                                      # (B, K, Ho, Wo)
-    rank = ((r >= 0.5) * torch.arange(1, len(lab) + 1, device=dev).view(1, -1, 1, 1)).amax(1, keepdim=True)
-    out_s = torch.where(rank > 0, lab[(rank - 1).clamp_(min=0)], torch.zeros((), device=dev, dtype=seg.dtype))
-    # untouched samples: centre crop (crop() with crop_type "center")
-    y0, x0 = (Hi - Ho) // 2, (Wi - Wo) // 2
-    m = do.view(B, 1, 1, 1)
-    return (torch.where(m, out_d, data[:, :, y0:y0 + Ho, x0:x0 + Wo]), torch.where(m, out_s, seg[:, :, y0:y0 + Ho, x0:x0 + Wo]))
+    return resample(spline_coefficients(data), data, seg, torch.stack([y, x], 1), do, labels)
+
+
+def resample(coef, data, seg, coords, do, labels=None):
+    """The torch form of the spatial transforms behind their coordinates: coef (the spline coefficients of data) and data
+    (B, C, *lead, *in) fp32, seg (B, S, *lead, *in) fp32, coords (B, nd, *out) over the last nd axes (every plane of the `lead`
+    axes with its sample's map) -> (B, C, *lead, *out) and (B, S, *lead, *out).  Data: order 3, 0 outside.
+    Segmentation: one linear interpolation per label value, ascending; the last label whose interpolated indicator reaches 0.5
+    is assigned, nothing where none does (interpolate_img, is_seg).  All indicator maps are channels of ONE gather.  `labels`
+    names the values of seg channel 0 (the dataset's label list avoids the torch.unique pass).
+    Samples outside `do` (B,) are centre-cropped (crop() with crop_type "center"); do None: every sample is resampled, and
+    the input may be smaller than the output."""
+    B, dev, nd = data.shape[0], data.device, coords.shape[1]
+    size_in, size_out = data.shape[-nd:], coords.shape[2:]
+    ones = (1,) * (data.dim() - 2)
+
+    def planes(x, order, cval):                                              # the lead axes travel as channels
+        return sample(x.reshape(B, -1, *size_in), coords, order, cval).view(*x.shape[:-nd], *size_out)
+    out_d, out_s = planes(coef, 3, 0.0), []
+    for c, s in enumerate(seg.split(1, 1)):
+        if labels is None or c > 0:
+            lab = torch.unique(s)                                            # sorted
+        else:
+            lab = labels.to(dev) if torch.is_tensor(labels) else torch.tensor(sorted(labels), device=dev, dtype=seg.dtype)
+        r = planes((s == lab.view(1, -1, *ones)).to(torch.float32), 1, -1.0)                    # (B, K, *lead, *out)
+        rank = ((r >= 0.5) * torch.arange(1, len(lab) + 1, device=dev).view(1, -1, *ones)).amax(1, keepdim=True)
+        out_s.append(torch.where(rank > 0, lab[(rank - 1).clamp_(min=0)], torch.zeros((), device=dev, dtype=seg.dtype)))
+    out_s = out_s[0] if len(out_s) == 1 else torch.cat(out_s, 1)
+    if do is None:
+        return out_d, out_s
+    crop = (...,) + tuple(slice((i - o) // 2, (i - o) // 2 + o) for i, o in zip(size_in, size_out))
+    m = do.view(B, 1, *ones)
+    return torch.where(m, out_d, data[crop]), torch.where(m, out_s, seg[crop])
 
 
 def gaussian_blur(data, do, sigma, radius):
-    """scipy.ndimage.gaussian_filter(img, sigma, order=0) (truncate 4, mode "reflect") per (sample, channel) where `do`;
-    `radius` = int(4 max(sigma) + 0.5), from the host-side parameters (no device read-back)."""
-    B, C, H, W = data.shape
+    """scipy.ndimage.gaussian_filter(img, sigma, order=0) (one sigma on every axis, truncate 4, mode "reflect") per (sample,
+    channel) where `do`; data (B, C, H, W) or (B, C, X, Y, Z); `radius` = int(4 max(sigma) + 0.5), from the host-side
+    parameters (no device read-back)."""
+    B, C = data.shape[:2]
     if radius == 0:
         return data
     t = torch.arange(-radius, radius + 1, device=data.device, dtype=torch.float32).view(1, 1, -1)
     s = sigma.view(B, C, 1)
     w = torch.exp(-0.5 * (t / s) ** 2) * (t.abs() <= torch.floor(4.0 * s + 0.5))      # each channel's own truncation
     w = w / w.sum(-1, keepdim=True)
-    x = band_matrix(H, w, "symmetric", data.device) @ data @ band_matrix(W, w, "symmetric", data.device).transpose(-1, -2)
-    return torch.where(do.view(B, C, 1, 1), x, data)
+    band = lambda ax: band_matrix(data.shape[ax], w, "symmetric", data.device)         # noqa: E731  (B, C, n, n)
+    if data.dim() == 4:
+        x = band(2) @ data @ band(3).transpose(-1, -2)
+    else:                                                                              # X sees (Y, Z) as its columns
+        x = (band(2) @ data.reshape(B, C, data.shape[2], -1)).reshape(data.shape)
+        x = band(3).unsqueeze(2) @ x
+        x = x @ band(4).transpose(-1, -2).unsqueeze(2)
+    return torch.where(do.view(B, C, *(1,) * (data.dim() - 2)), x, data)
+
+
+def low_resolution_image(img, zoom, nd):
+    """The first half of SimulateLowResolutionTransform for one image (*lead, *sizes): skimage's resize of the last nd axes to
+    round(sizes * zoom) with order 0 -> the small image, and what its order-3 resize back (mode "edge") samples: the spline
+    coefficients (1, planes, *padded), the lead axes as planes."""
+    small = img
+    for ax in range(img.dim() - nd, img.dim()):
+        n = img.shape[ax]
+        m = int(round(n * zoom))
+        # order 0, half-pixel-centred grid: source index floor((i + 0.5) * n / m - 0.5 + 0.5)
+        i = torch.floor((torch.arange(m, device=img.device, dtype=torch.float64) + 0.5) * (n / m)).long().clamp_(0, n - 1)
+        small = small.index_select(ax, i)
+    # order 3, mode "edge": scipy pads 12 edge pixels before the prefilter; the half-pixel rim samples that padding
+    pad = F.pad(small.reshape(1, -1, *small.shape[-nd:]), (12,) * (2 * nd), mode="replicate")
+    return small, spline_coefficients(pad, nd).contiguous()
+
+
+def clip_to_range(up, small):
+    """skimage resize(clip=True): the up-sampled image stays inside the range of the (whole) small image."""
+    return torch.minimum(torch.maximum(up, small.min()), small.max())
 
 
 def simulate_low_resolution(data, do, zoom):
@@ -283,22 +351,13 @@ def simulate_low_resolution(data, do, zoom):
     B, C, H, W = data.shape
     out = data.clone()
     for b, c in np.argwhere(np.asarray(do)).tolist():         # few (p 0.25 x 0.5): each (sample, channel) has its own low-res size
-        z = float(zoom[b, c])
-        h, w = int(round(H * z)), int(round(W * z))
-        img = data[b, c]
-        # order 0, half-pixel-centred grid: source index floor((i + 0.5) * H / h - 0.5 + 0.5)
+        small, coef = low_resolution_image(data[b, c], float(zoom[b, c]), 2)
+        h, w = small.shape
         f64 = dict(device=data.device, dtype=torch.float64)
-        iy = torch.floor((torch.arange(h, **f64) + 0.5) * (H / h)).long().clamp_(0, H - 1)
-        ix = torch.floor((torch.arange(w, **f64) + 0.5) * (W / w)).long().clamp_(0, W - 1)
-        small = img[iy][:, ix]
-        # order 3, mode "edge": scipy pads 12 edge pixels before the prefilter; the half-pixel rim samples that padding
-        pad = F.pad(small[None, None], (12, 12, 12, 12), mode="replicate")
-        coef = spline_coefficients(pad)
         yy = (((torch.arange(H, **f64) + 0.5) * (h / H) - 0.5) + 12).float()
         xx = (((torch.arange(W, **f64) + 0.5) * (w / W) - 0.5) + 12).float()
         gy, gx = torch.meshgrid(yy, xx, indexing="ij")
-        up = sample(coef, torch.stack([gy, gx])[None], 3, 0.0)[0, 0]
-        out[b, c] = torch.minimum(torch.maximum(up, small.min()), small.max())      # skimage resize(clip=True)
+        out[b, c] = clip_to_range(sample(coef, torch.stack([gy, gx])[None], 3, 0.0)[0, 0], small)
     return out
 
 

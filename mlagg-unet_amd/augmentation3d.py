@@ -22,8 +22,9 @@ Parameters are drawn on the host in batchgenerators' 3-D order (`draw_params_3d`
     (csrc/augment3d.hip, ops.aug3d_resample_planar: 16 cubic taps, 4 bilinear label taps, X never resampled) -- and
     SimulateLowResolution ignores axis 0 (in-plane sizes, padding and prefilter, K31 for the up-sampling, the clip still to the
     small VOLUME's range).  Everything after the spatial transform is 3-D again and shared with the isotropic mode.
-CPU tensors take a torch composition of the same arithmetic (the sampler as one gather of all taps; scipy.ndimage for the cascade
-transforms), for tests at small sizes.
+CPU tensors take a torch composition of the same arithmetic (augmentation.resample on the float64 coordinates of `affine_coords`;
+scipy.ndimage for the cascade transforms), for tests at small sizes.  The sampler, the prefilter, the blur, the parameter table and
+the draws are the 2-D module's: they take the number of axes.
 
 Out of scope: the region / mask transforms (B:697-699, B:722-726), as in the 2-D augmenter.
 """
@@ -31,12 +32,10 @@ import math
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from . import augmentation as A2
-from .augmentation import band_matrix, contrast_transform, gamma_transform, get_patch_size, mirror_transform
-
-ANISO_THRESHOLD = 3                                  # nnunetv2.configuration.ANISO_THRESHOLD
+from .augmentation import contrast_transform, gamma_transform, gaussian_blur, get_patch_size, mirror_transform
+from .export import ANISO_THRESHOLD
 
 
 def rotation_for_3d(patch_size):
@@ -53,22 +52,9 @@ def draw_params_3d(rng, batch, channels, rotation=None, mirror_axes=(0, 1, 2)):
     """draw_params with batchgenerators' 3-D order: per sample, when rotation fires, a_x, a_y, a_z each behind its own
     uniform() <= p_rot_per_axis (1), then the scale; the intensity transforms and mirroring (three flags) as in 2-D.
     p["angle"] is (B, 3): the angles about x, y, z."""
-    rotation = rotation_for_3d((1, 1, 1)) if rotation is None else rotation
-    B, C = batch, channels
-    p = {k: np.zeros(B, dtype=bool) for k in ("do_rot", "do_scale", "do_noise", "do_blur", "do_bright", "do_contrast", "do_lowres",
-                                              "do_gamma_inv", "do_gamma")}
-    p.update(angle=np.zeros((B, 3)), scale=np.ones(B), noise_std=np.zeros(B), blur_ch=np.zeros((B, C), dtype=bool),
-             blur_sigma=np.ones((B, C)), bright=np.ones((B, C)), contrast=np.ones((B, C)), lowres_ch=np.zeros((B, C), dtype=bool),
-             lowres_zoom=np.ones((B, C)), gamma_inv=np.ones((B, C)), gamma=np.ones((B, C)), mirror=np.zeros((B, 3), dtype=bool))
-    for b in range(B):                                                     # SpatialTransform: p_rot 0.2, p_scale 0.2
-        if rng.uniform() < 0.2:
-            for ax in range(3):
-                if rng.uniform() <= 1.0:                                   # p_rot_per_axis = 1 (B:670): drawn, always taken
-                    p["angle"][b, ax] = rng.uniform(rotation[ax][0], rotation[ax][1])
-            p["do_rot"][b] = True
-        if rng.uniform() < 0.2:
-            p["do_scale"][b], p["scale"][b] = True, A2._two_sided(rng, 0.7, 1.4)
-    return A2._draw_intensity_and_mirror(rng, p, B, C, mirror_axes)
+    p = A2._param_table(batch, channels, 3, 3)
+    A2._draw_spatial(rng, p, (rotation_for_3d((1, 1, 1)) if rotation is None else rotation)[:3])
+    return A2._draw_intensity_and_mirror(rng, p, batch, channels, mirror_axes)
 
 
 def configure_3d(patch_size):
@@ -89,20 +75,9 @@ def draw_params_dummy_2d(rng, batch, channels, rotation=(-math.pi, math.pi), mir
     """The draws of the dummy-2-D chain: SpatialTransform sees (B, C * X, Y, Z), so per sample batchgenerators' 2-D order (one
     angle behind its uniform() <= p_rot_per_axis, then the scale: augmentation.draw_params' spatial part); after Convert2DTo3D the
     intensity transforms draw per channel over C (not C * X) and the mirroring draws three flags.  p["angle"] is (B,)."""
-    B, C = batch, channels
-    p = {k: np.zeros(B, dtype=bool) for k in ("do_rot", "do_scale", "do_noise", "do_blur", "do_bright", "do_contrast", "do_lowres",
-                                              "do_gamma_inv", "do_gamma")}
-    p.update(angle=np.zeros(B), scale=np.ones(B), noise_std=np.zeros(B), blur_ch=np.zeros((B, C), dtype=bool),
-             blur_sigma=np.ones((B, C)), bright=np.ones((B, C)), contrast=np.ones((B, C)), lowres_ch=np.zeros((B, C), dtype=bool),
-             lowres_zoom=np.ones((B, C)), gamma_inv=np.ones((B, C)), gamma=np.ones((B, C)), mirror=np.zeros((B, 3), dtype=bool))
-    for b in range(B):                                                     # SpatialTransform: p_rot 0.2, p_scale 0.2
-        if rng.uniform() < 0.2:
-            if rng.uniform() <= 1.0:                                       # p_rot_per_axis = 1 (B:670): drawn, always taken
-                p["angle"][b] = rng.uniform(rotation[0], rotation[1])
-            p["do_rot"][b] = True
-        if rng.uniform() < 0.2:
-            p["do_scale"][b], p["scale"][b] = True, A2._two_sided(rng, 0.7, 1.4)
-    return A2._draw_intensity_and_mirror(rng, p, B, C, mirror_axes)
+    p = A2._param_table(batch, channels, 0, 3)
+    A2._draw_spatial(rng, p, (rotation,))
+    return A2._draw_intensity_and_mirror(rng, p, batch, channels, mirror_axes)
 
 
 def rotation_matrix(ax, ay, az):
@@ -115,168 +90,76 @@ def rotation_matrix(ax, ay, az):
 
 
 def affines(p, in_shape, out_shape):
-    """Per sample the (3, 4) float64 map output voxel index -> input coordinate of augment_spatial: zero-centred mesh, rotated,
-    scaled, moved to the input centre (in / 2 - 0.5); and whether the sample is resampled at all (else: centre crop)."""
-    B = len(p["do_rot"])
-    A = np.zeros((B, 3, 4))
+    """Per sample the (nd, nd + 1) float64 map output index -> input coordinate of augment_spatial over nd = len(out_shape) axes:
+    zero-centred mesh, rotated, scaled, moved to the input centre (in / 2 - 0.5); and whether the sample is resampled at all
+    (else: centre crop).  p["angle"] (B, 3): `rotation_matrix` about x, y, z.  p["angle"] (B,): the 2-D transform that every
+    slice of a dummy-2-D sample goes through, coords^T . [[cos, -sin], [sin, cos]] over (y, z)."""
+    B, nd = len(p["do_rot"]), len(out_shape)
+    A = np.zeros((B, nd, nd + 1))
     do = np.asarray(p["do_rot"]) | np.asarray(p["do_scale"])
     half = (np.asarray(out_shape, dtype=np.float64) - 1) / 2.0
+    three = np.ndim(p["angle"]) == 2
     for b in range(B):
-        M = rotation_matrix(*p["angle"][b]) if p["do_rot"][b] else np.identity(3)
+        if three:
+            M = rotation_matrix(*p["angle"][b]) if p["do_rot"][b] else np.identity(3)
+        else:
+            cos, sin = (math.cos(p["angle"][b]), math.sin(p["angle"][b])) if p["do_rot"][b] else (1.0, 0.0)
+            M = np.array([[cos, -sin], [sin, cos]])
         L = (M * (p["scale"][b] if p["do_scale"][b] else 1.0)).T               # input_j = sum_i L[j, i] centred_i
-        A[b, :, :3] = L
-        A[b, :, 3] = np.asarray(in_shape, dtype=np.float64) / 2.0 - 0.5 - L @ half
+        A[b, :, :nd] = L
+        A[b, :, nd] = np.asarray(in_shape, dtype=np.float64) / 2.0 - 0.5 - L @ half
     return A, do
 
 
-def affines_planar(p, in_yz, out_yz):
-    """Per sample the (2, 3) float64 map output pixel (y, z) -> input (y, z) of the 2-D augment_spatial that every slice of a
-    dummy-2-D sample goes through: zero-centred mesh, rotated as coords^T . [[cos, -sin], [sin, cos]], scaled, moved to the input
-    centre (in / 2 - 0.5); and whether the sample is resampled at all (else: centre crop over (Y, Z))."""
-    B = len(p["do_rot"])
-    A = np.zeros((B, 2, 3))
-    do = np.asarray(p["do_rot"]) | np.asarray(p["do_scale"])
-    half = (np.asarray(out_yz, dtype=np.float64) - 1) / 2.0
-    for b in range(B):
-        cos, sin = (math.cos(p["angle"][b]), math.sin(p["angle"][b])) if p["do_rot"][b] else (1.0, 0.0)
-        M = np.array([[cos, -sin], [sin, cos]])
-        L = (M * (p["scale"][b] if p["do_scale"][b] else 1.0)).T               # input_j = sum_i L[j, i] centred_i
-        A[b, :, :2] = L
-        A[b, :, 2] = np.asarray(in_yz, dtype=np.float64) / 2.0 - 0.5 - L @ half
-    return A, do
-
-
-# ------------------------------------------------------------------------------------------------
-# host (CPU tensor) sampler; the device runs K25
-# ------------------------------------------------------------------------------------------------
-def spline_coefficients_3d(x):
-    """(.., X, Y, Z) -> cubic B-spline coefficients with scipy's "mirror" boundary: the 33-tap band matrix along each axis."""
-    X, Y, Z = x.shape[-3:]
-    lead = x.shape[:-3]
-    x = (A2._prefilter_matrix(X, x.device) @ x.reshape(-1, X, Y * Z)).reshape(*lead, X, Y, Z)
-    x = A2._prefilter_matrix(Y, x.device) @ x
-    return x @ A2._prefilter_matrix(Z, x.device).T
-
-
-def sample_3d(img, A, out_shape, order, cval):
-    """map_coordinates(img, coords, order, mode="constant", cval) with coords = A (B, 3, 4) float64 applied to the output voxel
-    grid: img (B, C, X, Y, Z) (spline coefficients for order 3) -> (B, C, *out_shape).  The coordinate is float64, its fractions
-    fp32 (as K25 forms them); all taps of all channels in one gather."""
-    B, C, X, Y, Z = img.shape
-    dev = img.device
-    grid = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=torch.float64, device=dev) for n in out_shape], indexing="ij"))
-    At = torch.as_tensor(A, dtype=torch.float64, device=dev)
-    coords = torch.einsum("bji,ip->bjp", At[:, :, :3], grid.reshape(3, -1)) + At[:, :, 3:]       # (B, 3, P)
-    inside = torch.ones(coords.shape[::2], dtype=torch.bool, device=dev)
-    taps, weights = [], []
-    first, n = (-1, 4) if order == 3 else (0, 2)
-    for j, size in enumerate((X, Y, Z)):
-        c = coords[:, j]
-        inside &= (c >= 0) & (c <= size - 1)
-        f = torch.floor(c)
-        t = (c - f).float()
-        w = A2._bspline3_weights(t) if order == 3 else torch.stack([1 - t, t], -2)          # (B, n, P)
-        taps.append(A2._mirror_index(f.long().unsqueeze(1) + torch.arange(n, device=dev).view(1, n, 1) + first, size))
-        weights.append(w)
-    ix, iy, iz = taps
-    idx = ((ix[:, :, None, None] * Y + iy[:, None, :, None]) * Z + iz[:, None, None, :]).reshape(B, 1, -1)
-    w = (weights[0][:, :, None, None] * weights[1][:, None, :, None] * weights[2][:, None, None, :]).reshape(B, 1, n ** 3, -1)
-    vals = img.reshape(B, C, -1).gather(2, idx.expand(-1, C, -1)).view(B, C, n ** 3, -1)
-    out = (vals * w).sum(2)
-    out = torch.where(inside.unsqueeze(1), out, torch.full_like(out, cval))
-    return out.view(B, C, *out_shape)
-
-
-def sample_planar(img, A, out_yz, order, cval):
-    """sample_3d for planes: img (B, N, Y, Z) (every slice of every channel as one of the N planes; coefficients prefiltered along
-    Y and Z for order 3), A (B, 2, 3) float64 applied to the output pixel grid -> (B, N, *out_yz).  The arithmetic of K31."""
-    B, N, Y, Z = img.shape
-    dev = img.device
-    grid = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=torch.float64, device=dev) for n in out_yz], indexing="ij"))
-    At = torch.as_tensor(A, dtype=torch.float64, device=dev)
-    coords = torch.einsum("bji,ip->bjp", At[:, :, :2], grid.reshape(2, -1)) + At[:, :, 2:]       # (B, 2, P)
-    inside = torch.ones(coords.shape[::2], dtype=torch.bool, device=dev)
-    taps, weights = [], []
-    first, n = (-1, 4) if order == 3 else (0, 2)
-    for j, size in enumerate((Y, Z)):
-        c = coords[:, j]
-        inside &= (c >= 0) & (c <= size - 1)
-        f = torch.floor(c)
-        t = (c - f).float()
-        weights.append(A2._bspline3_weights(t) if order == 3 else torch.stack([1 - t, t], -2))        # (B, n, P)
-        taps.append(A2._mirror_index(f.long().unsqueeze(1) + torch.arange(n, device=dev).view(1, n, 1) + first, size))
-    iy, iz = taps
-    idx = (iy[:, :, None] * Z + iz[:, None, :]).reshape(B, 1, -1)
-    w = (weights[0][:, :, None] * weights[1][:, None, :]).reshape(B, 1, n * n, -1)
-    vals = img.reshape(B, N, -1).gather(2, idx.expand(-1, N, -1)).view(B, N, n * n, -1)
-    out = (vals * w).sum(2)
-    out = torch.where(inside.unsqueeze(1), out, torch.full_like(out, cval))
-    return out.view(B, N, *out_yz)
+def affine_coords(A, out_shape, device):
+    """A (B, nd, nd + 1) float64 applied to the output index grid -> the float64 coordinates (B, nd, *out_shape) that
+    augmentation.sample takes on the host and K25 / K31 form on the device."""
+    grid = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=torch.float64, device=device) for n in out_shape], indexing="ij"))
+    At = torch.as_tensor(A, dtype=torch.float64, device=device)
+    nd = len(out_shape)
+    coords = torch.einsum("bji,ip->bjp", At[:, :, :nd], grid.reshape(nd, -1)) + At[:, :, nd:]     # (B, nd, P)
+    return coords.view(len(At), nd, *out_shape)
 
 
 # ------------------------------------------------------------------------------------------------
 # transforms
 # ------------------------------------------------------------------------------------------------
-def _prefiltered(data, do):
-    """The resampler's input volume: spline coefficients of the samples in `do`, the data itself for the others."""
+def _prefiltered(data, do, nd=3):
+    """The resampler's input volume: spline coefficients (along the last nd axes) of the samples in `do`, the data itself for
+    the others."""
     idx = np.flatnonzero(do)
     if len(idx) == len(do):
-        return spline_coefficients_3d(data).contiguous()
+        return A2.spline_coefficients(data, nd).contiguous()
     vol = data.clone()
     if len(idx):
         sel = torch.as_tensor(idx, device=data.device)
-        vol[sel] = spline_coefficients_3d(data[sel])
+        vol[sel] = A2.spline_coefficients(data[sel], nd)
     return vol
+
+
+def _spatial(data, seg, out_shape, p, labels, nd):
+    """The spatial transform over the last nd axes of (B, C, X, Y, Z): K25 (nd 3) or K31 (nd 2) on the device, a further seg
+    channel by a call without a volume (the labels only); augmentation.resample on the host."""
+    in_nd, out_nd = tuple(data.shape[-nd:]), out_shape[-nd:]
+    A, do = affines(p, in_nd, out_nd)
+    vol = _prefiltered(data.contiguous(), do, nd)
+    if not data.is_cuda:
+        keep = None if do.all() else torch.as_tensor(do)
+        return A2.resample(vol, data, seg.to(torch.float32), affine_coords(A, out_nd, data.device), keep, labels)
+    from . import ops
+    kernel = ops.aug3d_resample if nd == 3 else ops.aug3d_resample_planar
+    if seg.shape[1] == 1:
+        return kernel(vol, seg.to(torch.int16).contiguous(), A, do, out_nd)
+    segs = [s.to(torch.int16).contiguous() for s in seg.split(1, 1)]
+    out_d, first = kernel(vol, segs[0], A, do, out_nd)
+    return out_d, torch.cat([first] + [kernel(None, s, A, do, out_nd)[1] for s in segs[1:]], 1)
 
 
 def spatial_transform_3d(data, seg, patch_size, p, labels=None):
     """augment_spatial, 3-D, with the nnU-Net arguments: data (B, C, Xi, Yi, Zi) fp32, seg (B, S, Xi, Yi, Zi) (int16 on the
     device path; any integral-valued type on the host) -> (B, C, *patch) fp32 and (B, S, *patch) fp32 labels.  Every seg channel
     is resampled with the same affines and the same indicator rule (`labels` names the values of channel 0 on the host path)."""
-    if seg.shape[1] > 1:
-        out_d, first = spatial_transform_3d(data, seg[:, :1], patch_size, p, labels)
-        if data.is_cuda:                                              # K25 without a volume: the labels only
-            from . import ops
-            A, do = affines(p, tuple(data.shape[2:]), tuple(int(v) for v in patch_size))
-            rest = [ops.aug3d_resample(None, seg[:, c:c + 1].to(torch.int16).contiguous(), A, do, patch_size)[1]
-                    for c in range(1, seg.shape[1])]
-        else:
-            rest = [spatial_transform_3d(data[:, :1], seg[:, c:c + 1], patch_size, p)[1] for c in range(1, seg.shape[1])]
-        return out_d, torch.cat([first] + rest, 1)
-    in_shape, out_shape = tuple(data.shape[2:]), tuple(int(v) for v in patch_size)
-    A, do = affines(p, in_shape, out_shape)
-    vol = _prefiltered(data.contiguous(), do)
-    if data.is_cuda:
-        from . import ops
-        return ops.aug3d_resample(vol, seg.to(torch.int16).contiguous(), A, do, out_shape)
-    B = data.shape[0]
-    out_d = sample_3d(vol, A, out_shape, 3, 0.0)
-    segf = seg.to(torch.float32)
-    lab = torch.unique(segf) if labels is None else labels.to(segf.device)
-    onehot = (segf == lab.view(1, -1, 1, 1, 1)).to(torch.float32)
-    r = sample_3d(onehot, A, out_shape, 1, -1.0)
-    rank = ((r >= 0.5) * torch.arange(1, len(lab) + 1).view(1, -1, 1, 1, 1)).amax(1, keepdim=True)
-    out_s = torch.where(rank > 0, lab[(rank - 1).clamp_(min=0)], torch.zeros(()))
-    o = [(i - s) // 2 for i, s in zip(in_shape, out_shape)]
-    crop = (slice(o[0], o[0] + out_shape[0]), slice(o[1], o[1] + out_shape[1]), slice(o[2], o[2] + out_shape[2]))
-    m = torch.as_tensor(do).view(B, 1, 1, 1, 1)
-    if (~do).any():
-        out_d = torch.where(m, out_d, data[(slice(None), slice(None)) + crop])
-        out_s = torch.where(m, out_s, segf[(slice(None), slice(None)) + crop])
-    return out_d, out_s
-
-
-def _prefiltered_planar(data, do):
-    """The planar resampler's input: coefficients prefiltered along Y and Z only of the samples in `do`, the data itself for the
-    others."""
-    idx = np.flatnonzero(do)
-    if len(idx) == len(do):
-        return A2.spline_coefficients(data).contiguous()
-    vol = data.clone()
-    if len(idx):
-        sel = torch.as_tensor(idx, device=data.device)
-        vol[sel] = A2.spline_coefficients(data[sel])
-    return vol
+    return _spatial(data, seg, tuple(int(v) for v in patch_size), p, labels, 3)
 
 
 def spatial_transform_dummy_2d(data, seg, patch_size, p, labels=None):
@@ -288,52 +171,7 @@ def spatial_transform_dummy_2d(data, seg, patch_size, p, labels=None):
     if data.dim() != 5 or len(out_shape) != 3 or out_shape[0] != data.shape[2]:
         raise RuntimeError(f"spatial_transform_dummy_2d: data {tuple(data.shape)} to patch {out_shape}: axis 0 is never resampled, "
                            "the loader delivers patch[0] slices")
-    in_yz, out_yz = tuple(data.shape[3:]), out_shape[1:]
-    A, do = affines_planar(p, in_yz, out_yz)
-    if seg.shape[1] > 1:
-        out_d, first = spatial_transform_dummy_2d(data, seg[:, :1], patch_size, p, labels)
-        if data.is_cuda:                                              # K31 without a volume: the labels only
-            from . import ops
-            rest = [ops.aug3d_resample_planar(None, seg[:, c:c + 1].to(torch.int16).contiguous(), A, do, out_yz)[1]
-                    for c in range(1, seg.shape[1])]
-        else:
-            rest = [spatial_transform_dummy_2d(data[:, :1], seg[:, c:c + 1], patch_size, p)[1] for c in range(1, seg.shape[1])]
-        return out_d, torch.cat([first] + rest, 1)
-    vol = _prefiltered_planar(data.contiguous(), do)
-    if data.is_cuda:
-        from . import ops
-        return ops.aug3d_resample_planar(vol, seg.to(torch.int16).contiguous(), A, do, out_yz)
-    B, C, X = data.shape[:3]
-    out_d = sample_planar(vol.reshape(B, C * X, *in_yz), A, out_yz, 3, 0.0).view(B, C, *out_shape)
-    segf = seg.to(torch.float32)
-    lab = torch.unique(segf) if labels is None else labels.to(segf.device)
-    onehot = (segf == lab.view(1, -1, 1, 1, 1)).to(torch.float32)                           # (B, L, X, Yi, Zi)
-    r = sample_planar(onehot.reshape(B, len(lab) * X, *in_yz), A, out_yz, 1, -1.0).view(B, len(lab), *out_shape)
-    rank = ((r >= 0.5) * torch.arange(1, len(lab) + 1).view(1, -1, 1, 1, 1)).amax(1, keepdim=True)
-    out_s = torch.where(rank > 0, lab[(rank - 1).clamp_(min=0)], torch.zeros(()))
-    o = [(i - s) // 2 for i, s in zip(in_yz, out_yz)]
-    crop = (slice(None), slice(None), slice(None), slice(o[0], o[0] + out_yz[0]), slice(o[1], o[1] + out_yz[1]))
-    m = torch.as_tensor(do).view(B, 1, 1, 1, 1)
-    if (~do).any():
-        out_d = torch.where(m, out_d, data[crop])
-        out_s = torch.where(m, out_s, segf[crop])
-    return out_d, out_s
-
-
-def gaussian_blur_3d(data, do, sigma, radius):
-    """scipy.ndimage.gaussian_filter(img, sigma) (same sigma on the three axes, truncate 4, "reflect") per (sample, channel)
-    where `do`; `radius` = int(4 max(sigma) + 0.5) from the host-side parameters."""
-    B, C, X, Y, Z = data.shape
-    if radius == 0:
-        return data
-    t = torch.arange(-radius, radius + 1, device=data.device, dtype=torch.float32).view(1, 1, -1)
-    s = sigma.view(B, C, 1)
-    w = torch.exp(-0.5 * (t / s) ** 2) * (t.abs() <= torch.floor(4.0 * s + 0.5))
-    w = w / w.sum(-1, keepdim=True)
-    x = (band_matrix(X, w, "symmetric", data.device) @ data.reshape(B, C, X, Y * Z)).reshape(B, C, X, Y, Z)
-    x = band_matrix(Y, w, "symmetric", data.device).unsqueeze(2) @ x
-    x = x @ band_matrix(Z, w, "symmetric", data.device).transpose(-1, -2).unsqueeze(2)
-    return torch.where(do.view(B, C, 1, 1, 1), x, data)
+    return _spatial(data, seg, out_shape, p, labels, 2)
 
 
 def simulate_low_resolution_3d(data, do, zoom, ignore_axes=None):
@@ -346,36 +184,20 @@ def simulate_low_resolution_3d(data, do, zoom, ignore_axes=None):
     if ignore_axes not in ((), (0,)):
         raise RuntimeError(f"simulate_low_resolution_3d: ignore_axes {ignore_axes}: None or (0,) expected")
     out = data.clone()
-    shape = tuple(data.shape[2:])
+    nd = 2 if ignore_axes else 3
+    shape = tuple(data.shape[-nd:])
     for b, c in np.argwhere(np.asarray(do)).tolist():
-        small_shape = tuple(int(v) for v in np.round(np.array(shape, dtype=float) * float(zoom[b, c])))
-        if ignore_axes:
-            small_shape = (shape[0],) + small_shape[1:]
-        f64 = dict(device=data.device, dtype=torch.float64)
-        ix, iy, iz = (torch.floor((torch.arange(m, **f64) + 0.5) * (n / m)).long().clamp_(0, n - 1)
-                      for n, m in zip(shape, small_shape))
-        small = data[b, c][ix][:, iy][:, :, iz]
-        if ignore_axes:
-            coef = A2.spline_coefficients(F.pad(small[None], (12,) * 4, mode="replicate")).contiguous()      # (1, X, h + 24, w + 24)
-            A = np.zeros((1, 2, 3))
-            for j, (n, m) in enumerate(zip(shape[1:], small_shape[1:])):
-                A[0, j, j], A[0, j, 2] = m / n, 0.5 * m / n - 0.5 + 12
-            if data.is_cuda:
-                from . import ops
-                up = ops.aug3d_resample_planar(coef[None], None, A, [True], shape[1:])[0][0, 0]
-            else:
-                up = sample_planar(coef, A, shape[1:], 3, 0.0)[0]
+        small, coef = A2.low_resolution_image(data[b, c], float(zoom[b, c]), nd)     # coef (1, 1 or X, *small + 24)
+        A = np.zeros((1, nd, nd + 1))
+        for j, (n, m) in enumerate(zip(shape, small.shape[-nd:])):
+            A[0, j, j], A[0, j, nd] = m / n, 0.5 * m / n - 0.5 + 12
+        if data.is_cuda:
+            from . import ops
+            kernel = ops.aug3d_resample if nd == 3 else ops.aug3d_resample_planar
+            up = kernel(coef.view(1, 1, *coef.shape[-3:]), None, A, [True], shape)[0]
         else:
-            coef = spline_coefficients_3d(F.pad(small[None, None], (12,) * 6, mode="replicate")).contiguous()
-            A = np.zeros((1, 3, 4))
-            for j, (n, m) in enumerate(zip(shape, small_shape)):
-                A[0, j, j], A[0, j, 3] = m / n, 0.5 * m / n - 0.5 + 12
-            if data.is_cuda:
-                from . import ops
-                up = ops.aug3d_resample(coef, None, A, [True], shape)[0][0, 0]
-            else:
-                up = sample_3d(coef, A, shape, 3, 0.0)[0, 0]
-        out[b, c] = torch.minimum(torch.maximum(up, small.min()), small.max())
+            up = A2.sample(coef, affine_coords(A, shape, data.device), 3, 0.0)
+        out[b, c] = A2.clip_to_range(up.view(data.shape[2:]), small)
     return out
 
 
@@ -671,7 +493,7 @@ class GpuAugmenter3D:
         data = data + noise * T(p["noise_std"] * p["do_noise"]).view(-1, 1, 1, 1, 1)
         blur = p["blur_ch"] & p["do_blur"][:, None]
         radius = int(4.0 * float(p["blur_sigma"][blur].max()) + 0.5) if blur.any() else 0
-        data = gaussian_blur_3d(data, T(blur, torch.bool), T(p["blur_sigma"]), radius)
+        data = gaussian_blur(data, T(blur, torch.bool), T(p["blur_sigma"]), radius)
         data = torch.where(T(p["do_bright"], torch.bool).view(-1, 1, 1, 1, 1),
                            data * T(p["bright"]).view(*p["bright"].shape, 1, 1, 1), data)
         data = contrast_transform(data, T(p["do_contrast"], torch.bool), T(p["contrast"]))

@@ -3239,28 +3239,33 @@ def aug3d_resample(vol, lab, affine, resample, out_shape):
     int16 or None, affine (B, 3, 4) float64 host array (output voxel index -> input coordinate), resample (B,) host bools ->
     (out (B, C, *out_shape) fp32, out_lab (B, 1, *out_shape) fp32 or None).  vol None with lab: the labels only (a further seg
     channel of a batch whose volume is already resampled), out is None.  See include/mlagg_hip.h, K25."""
+    return _aug3d_launch("aug3d_resample", 3, vol, lab, affine, resample, out_shape)
+
+
+def _aug3d_launch(name, nd, vol, lab, affine, resample, out_nd):
+    """K25 (nd 3) and K31 (nd 2: the map covers (Y, Z) only) take the same arguments: the checks, the outputs and the launch."""
     if vol is None:
         _expect(lab, "lab", torch.int16, dim=5)
-        B, C, (Xi, Yi, Zi) = int(lab.shape[0]), 0, (int(v) for v in lab.shape[2:])
+        B, C, size_in = int(lab.shape[0]), 0, tuple(int(v) for v in lab.shape[2:])
         vol = lab                                         # shape and device of the checks below
     else:
         _expect(vol, "vol", dim=5)
-        B, C, Xi, Yi, Zi = (int(v) for v in vol.shape)
-    Xo, Yo, Zo = (int(v) for v in out_shape)
-    if min(Xo, Yo, Zo) < 1:
-        raise RuntimeError(f"aug3d_resample: output shape {tuple(out_shape)}")
+        B, C, *size_in = (int(v) for v in vol.shape)
+    if len(out_nd) != nd or min(int(v) for v in out_nd) < 1:
+        raise RuntimeError(f"{name}: output shape {tuple(out_nd)}")
+    size_out = (*size_in[:3 - nd], *(int(v) for v in out_nd))
     if lab is not None:
-        _expect(lab, "lab", torch.int16, shape=(B, 1, Xi, Yi, Zi), like=vol)
-    A = np.ascontiguousarray(np.asarray(affine, dtype=np.float64).reshape(B, 12))
+        _expect(lab, "lab", torch.int16, shape=(B, 1, *size_in), like=vol)
+    A = np.ascontiguousarray(np.asarray(affine, dtype=np.float64).reshape(B, nd * (nd + 1)))
     rs = np.asarray(resample, dtype=bool).reshape(-1)
     if rs.shape[0] != B:
-        raise RuntimeError(f"aug3d_resample: {rs.shape[0]} resample flags for {B} samples")
-    if (~rs).any() and (Xo > Xi or Yo > Yi or Zo > Zi):
-        raise RuntimeError(f"aug3d_resample: a cropped sample needs an input ({Xi}, {Yi}, {Zi}) at least the output ({Xo}, {Yo}, {Zo})")
-    out = torch.empty((B, C, Xo, Yo, Zo), device=vol.device, dtype=torch.float32) if C else None
-    out_lab = torch.empty((B, 1, Xo, Yo, Zo), device=vol.device, dtype=torch.float32) if lab is not None else None
-    _launch("mlagg_aug3d_resample", _ptr(vol) if C else None, _ptr(lab), B, C, Xi, Yi, Zi, A.ctypes.data, _int_array(rs.astype(int)), _ptr(out),
-            _ptr(out_lab), Xo, Yo, Zo)
+        raise RuntimeError(f"{name}: {rs.shape[0]} resample flags for {B} samples")
+    if (~rs).any() and any(o > i for o, i in zip(size_out, size_in)):
+        raise RuntimeError(f"{name}: a cropped sample needs an input {tuple(size_in)} at least the output {size_out}")
+    out = torch.empty((B, C, *size_out), device=vol.device, dtype=torch.float32) if C else None
+    out_lab = torch.empty((B, 1, *size_out), device=vol.device, dtype=torch.float32) if lab is not None else None
+    _launch("mlagg_" + name, _ptr(vol) if C else None, _ptr(lab), B, C, *size_in, A.ctypes.data, _int_array(rs.astype(int)), _ptr(out),
+            _ptr(out_lab), *size_out[3 - nd:])
     return out, out_lab
 
 
@@ -3272,29 +3277,7 @@ def aug3d_resample_planar(vol, lab, affine, resample, out_yz):
     (B, 1, X, Yi, Zi) int16 or None, affine (B, 2, 3) float64 host array (output pixel (y, z) -> input (y, z), the same for every
     slice and channel of the sample), resample (B,) host bools -> (out (B, C, X, *out_yz) fp32, out_lab (B, 1, X, *out_yz) fp32 or
     None).  vol None with lab: the labels only, out is None.  See include/mlagg_hip.h, K31."""
-    if vol is None:
-        _expect(lab, "lab", torch.int16, dim=5)
-        B, C, (X, Yi, Zi) = int(lab.shape[0]), 0, (int(v) for v in lab.shape[2:])
-        vol = lab                                         # shape and device of the checks below
-    else:
-        _expect(vol, "vol", dim=5)
-        B, C, X, Yi, Zi = (int(v) for v in vol.shape)
-    if len(out_yz) != 2 or min(int(v) for v in out_yz) < 1:
-        raise RuntimeError(f"aug3d_resample_planar: output plane {tuple(out_yz)}")
-    Yo, Zo = (int(v) for v in out_yz)
-    if lab is not None:
-        _expect(lab, "lab", torch.int16, shape=(B, 1, X, Yi, Zi), like=vol)
-    A = np.ascontiguousarray(np.asarray(affine, dtype=np.float64).reshape(B, 6))
-    rs = np.asarray(resample, dtype=bool).reshape(-1)
-    if rs.shape[0] != B:
-        raise RuntimeError(f"aug3d_resample_planar: {rs.shape[0]} resample flags for {B} samples")
-    if (~rs).any() and (Yo > Yi or Zo > Zi):
-        raise RuntimeError(f"aug3d_resample_planar: a cropped sample needs input planes ({Yi}, {Zi}) at least the output ({Yo}, {Zo})")
-    out = torch.empty((B, C, X, Yo, Zo), device=vol.device, dtype=torch.float32) if C else None
-    out_lab = torch.empty((B, 1, X, Yo, Zo), device=vol.device, dtype=torch.float32) if lab is not None else None
-    _launch("mlagg_aug3d_resample_planar", _ptr(vol) if C else None, _ptr(lab), B, C, X, Yi, Zi, A.ctypes.data, _int_array(rs.astype(int)),
-            _ptr(out), _ptr(out_lab), Yo, Zo)
-    return out, out_lab
+    return _aug3d_launch("aug3d_resample_planar", 2, vol, lab, affine, resample, out_yz)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -97,7 +97,7 @@ def test_draw_order_is_batchgenerators_2d_then_3d():
 
 def test_planar_affine_matches_the_oracle_coordinates():
     p = K.forced_params()
-    A, do = AUG3.affines_planar(p, K.IN[1:], K.OUT[1:])
+    A, do = AUG3.affines(p, K.IN[1:], K.OUT[1:])
     assert A.shape == (K.B, 2, 3) and A.dtype == np.float64
     grid = np.stack(np.meshgrid(*[np.arange(n) for n in K.OUT[1:]], indexing="ij")).reshape(2, -1).astype(float)
     for b in range(K.B):

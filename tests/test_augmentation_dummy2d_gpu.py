@@ -67,7 +67,7 @@ def test_k31_labels_only_over_two_launches():
     angles = [None if b % 5 == 4 else 0.41 * (b + 1) for b in range(n)]          # samples 4, 9, 14 are cropped
     scales = [None if b % 5 == 4 or b % 3 == 0 else 0.7 + 0.04 * b for b in range(n)]
     p = K.spatial_params(angles, scales)
-    A, do = AUG3.affines_planar(p, shape_in[1:], shape_out[1:])
+    A, do = AUG3.affines(p, shape_in[1:], shape_out[1:])
     assert do.sum() == 14
     out, lab = ops.aug3d_resample_planar(None, torch.from_numpy(seg).cuda().to(torch.int16), A, do, shape_out[1:])
     assert out is None and lab.shape == (n, 1) + shape_out
@@ -82,8 +82,8 @@ def test_k31_labels_only_over_two_launches():
 def test_k31_is_run_to_run_identical_and_refuses_bad_arguments():
     data, seg = K.volumes(seed=3)
     p = K.only(K.forced_params(seed=4), ["do_rot", "do_scale"])
-    A, do = AUG3.affines_planar(p, K.IN[1:], K.OUT[1:])
-    vol = AUG3._prefiltered_planar(torch.from_numpy(data).cuda(), do)
+    A, do = AUG3.affines(p, K.IN[1:], K.OUT[1:])
+    vol = AUG3._prefiltered(torch.from_numpy(data).cuda(), do, 2)
     lab = torch.from_numpy(seg).cuda().to(torch.int16)
     a = ops.aug3d_resample_planar(vol, lab, A, do, K.OUT[1:])
     b = ops.aug3d_resample_planar(vol, lab, A, do, K.OUT[1:])

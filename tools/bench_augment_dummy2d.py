@@ -85,8 +85,8 @@ def measure(dev, patch, iters, repeats, n=B):
     pieces = {}
     if dev.type == "cuda":
         from mlagg_unet_amd import ops
-        A, do = AUG3.affines_planar(p, init[1:], patch[1:])
-        vol = AUG3._prefiltered_planar(data, do)
+        A, do = AUG3.affines(p, init[1:], patch[1:])
+        vol = AUG3._prefiltered(data, do, 2)
         pieces["prefilter_ms"] = round(timed(lambda: A2.spline_coefficients(data), iters, sync), 3)
         pieces["k31_kernel_ms"] = round(timed(lambda: ops.aug3d_resample_planar(vol, seg, A, do, patch[1:]), iters, sync), 3)
         nbytes = n * int(np.prod(init)) * (4 + 2) + n * int(np.prod(patch)) * (4 + 4)

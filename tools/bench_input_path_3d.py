@@ -18,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mlagg_unet_amd  # noqa: E402,F401
+from mlagg_unet_amd import augmentation as AUG  # noqa: E402
 from mlagg_unet_amd import augmentation3d as AUG3  # noqa: E402
 from mlagg_unet_amd import dataloading as DL  # noqa: E402
 from mlagg_unet_amd import ops  # noqa: E402
@@ -120,7 +121,7 @@ def main():
     p["scale"][:] = [0.74, 1.37]
     A, do = AUG3.affines(p, init, PATCH)
     vol = AUG3._prefiltered(data, do)
-    prefilter_ms = timed(lambda: AUG3.spline_coefficients_3d(data), a.batches)
+    prefilter_ms = timed(lambda: AUG.spline_coefficients(data, 3), a.batches)
     k25_ms = timed(lambda: ops.aug3d_resample(vol, seg, A, do, PATCH), a.batches)
     crop = np.zeros(B, dtype=bool)
     k25_crop_ms = timed(lambda: ops.aug3d_resample(data, seg, A, crop, PATCH), a.batches)
