@@ -309,6 +309,10 @@ int mlagg_conv1x1_fwd_ragged(const float *x, long x_batch, const float *w, const
  * same input, MONAI structure behind T:1340-1368) is added to the first one's inside the kernel instead of by an add_ over the map. */
 int mlagg_conv1x1_fwd_acc(const float *x, long x_batch, const float *w, const float *bias, float *y, long y_batch, int B, int O, int I,
                           int I_valid, long P, int dtype, int accumulate, void *stream);
+/* The tile the launchers choose (host only, nothing is launched; the launchers call the same code, MLAGG_K18_TILE included): to * 4 + tp
+ * of the forward form for O output channels -- (32 to) channels x (32 tp) pixels per wave -- and to * 4 + ti of the weight gradient. */
+int mlagg_conv1x1_fwd_tile(int O);
+int mlagg_conv1x1_wgrad_tile(int O, int I);
 
 /* ------------------------------------------------------------------------------------------
  * K19: dense 3 x 3 convolutions (stride 1, zero padding 1, groups 1) on channel-major maps as nine shifted GEMMs on the 16-bit matrix
@@ -350,6 +354,15 @@ int mlagg_conv3x3_fwd_lp(const float *x, long x_batch, const float *w, int trans
                          void *workspace, int B, int O, int I, int H, int W, int dtype, void *stream);
 int mlagg_conv3x3_wgrad_lp(const float *dy, long dy_batch, const float *x, long x_batch, float *dW, float *workspace, int B, int O,
                            int I, int H, int W, int dtype, void *stream);
+/* What the launchers choose (host only, nothing is launched; the launchers call the same code, MLAGG_K19_TILE / MLAGG_K19W16 included):
+ *   fwd_tile:   to * 4 + tp of the forward form for O output channels on a (D, H, W) map (D = 1: 2-D) -- (32 to) channels x (32 tp)
+ *               pixels per wave;
+ *   wgrad_form: form * 4 + ti of the weight gradient in the operand form `dtype`.  form 0: 32 x 32 tiles, nine taps per wave (every
+ *               volume, D > 1), ti reported as 0; form 1: (48 x 16 ti)-channel tiles, fragment-shaped loads; form 2: the same tiles,
+ *               operands staged through LDS in full lines (needs a 16-byte-aligned x, else the launcher runs form 1).
+ *               MLAGG_E_UNSUPPORTED for a `dtype` that is no operand form. */
+int mlagg_conv3x3_fwd_tile(int O, int D, int H, int W);
+int mlagg_conv3x3_wgrad_form(int O, int I, int D, int dtype);
 
 /* ------------------------------------------------------------------------------------------
  * K19t: the 3 x 3, stride-2, padding-1 transposed convolution of PatchExpand (nnUNetTrainer_MLAgg_2D_dt_MS.py:506-513, conv1 =

@@ -230,14 +230,27 @@ int make_wgeom(W1Geom &g, int B, int O, int I, int P, long dy_batch, long x_batc
     return 0;
 }
 
-void pick_fwd_tile(int B, int O, int I, int P, int &to, int &tp)
+// to * 4 + tp of the forward launch: tile = (32 TO output channels) x (32 TP pixels) per wave.  MLAGG_K18_TILE="TO,TP" overrides (tuning
+// only).  Measured (tools/bench_conv1x1.py, MLAGG_K18_TILE sweeps): 3 x 2 tiles for wide outputs (two waves per SIMD cover the short
+// contraction loops' load latency), 3 pixel tiles when the output has at most 64 channels.  mlagg_conv1x1_fwd_acc launches what this
+// returns and mlagg_conv1x1_fwd_tile reports it.
+int fwd_tile(int O)
 {
+    int to = O <= 32 ? 1 : (O <= 64 ? 2 : 3), tp = O <= 64 ? 3 : 2;
     static const char *env = getenv("MLAGG_K18_TILE");
     if (env && env[0] >= '1' && env[0] <= '3' && env[1] == ',' && env[2] >= '1' && env[2] <= '3') {
         to = env[0] - '0';
         tp = env[2] - '0';
         if (32 * (to - 1) >= O) to = (O + 31) / 32;
     }
+    return to * 4 + tp;
+}
+
+// to * 4 + ti of the weight-gradient launch (32-channel tiles of dy rows x x rows); reported by mlagg_conv1x1_wgrad_tile
+int wgrad_tile(int O, int I)
+{
+    const int to = O > 64 ? 3 : (O + 31) / 32, ti = I > 64 ? 3 : (I + 31) / 32;
+    return to * 4 + ti;
 }
 
 template <int TO, int TP>
@@ -290,12 +303,7 @@ extern "C" int mlagg_conv1x1_fwd_acc(const float *x, long x_batch, const float *
     C1Geom g{B, O, I, (int)P, x_batch, y_batch, I_valid, accumulate ? 1 : 0};
     hipStream_t st = static_cast<hipStream_t>(stream);
     MLAGG_TIMED(K_CONV1X1, st);
-    // tile = (32 TO output channels) x (32 TP pixels) per wave.  MLAGG_K18_TILE="TO,TP" overrides (tuning only).
-    // measured (tools/bench_conv1x1.py, MLAGG_K18_TILE sweeps): 3 x 2 tiles for wide outputs (two waves per SIMD cover the short
-    // contraction loops' load latency), 3 pixel tiles when the output has at most 64 channels
-    int to = O <= 32 ? 1 : (O <= 64 ? 2 : 3), tp = O <= 64 ? 3 : 2;
-    pick_fwd_tile(B, O, I, (int)P, to, tp);
-    switch (to * 4 + tp) {
+    switch (fwd_tile(O)) {
     case 1 * 4 + 1: launch_fwd<1, 1>(x, w, bias, y, g, dtype, st); break;
     case 1 * 4 + 2: launch_fwd<1, 2>(x, w, bias, y, g, dtype, st); break;
     case 1 * 4 + 3: launch_fwd<1, 3>(x, w, bias, y, g, dtype, st); break;
@@ -321,6 +329,10 @@ extern "C" int mlagg_conv1x1_fwd(const float *x, long x_batch, const float *w, c
     return mlagg_conv1x1_fwd_lp(x, x_batch, w, bias, y, y_batch, B, O, I, P, MLAGG_DTYPE_BF16X3, stream);
 }
 
+// the tiles the launchers choose (host only): to * 4 + tp of the forward / data gradient, to * 4 + ti of the weight gradient
+extern "C" int mlagg_conv1x1_fwd_tile(int O) { return fwd_tile(O); }
+extern "C" int mlagg_conv1x1_wgrad_tile(int O, int I) { return wgrad_tile(O, I); }
+
 extern "C" size_t mlagg_conv1x1_wgrad_workspace_floats(int B, int O, int I, long P)
 {
     W1Geom g;
@@ -339,8 +351,7 @@ extern "C" int mlagg_conv1x1_wgrad_lp(const float *dy, long dy_batch, const floa
     if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x)) & 15) return MLAGG_E_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     MLAGG_TIMED(K_CONV1X1, st);
-    const int to = O > 64 ? 3 : (O + 31) / 32, ti = I > 64 ? 3 : (I + 31) / 32;
-    switch (to * 4 + ti) {
+    switch (wgrad_tile(O, I)) {
     case 1 * 4 + 1: launch_wgrad<1, 1>(dy, x, workspace, g, dtype, st); break;
     case 1 * 4 + 2: launch_wgrad<1, 2>(dy, x, workspace, g, dtype, st); break;
     case 1 * 4 + 3: launch_wgrad<1, 3>(dy, x, workspace, g, dtype, st); break;

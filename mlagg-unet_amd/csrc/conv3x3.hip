@@ -796,6 +796,29 @@ namespace {
 // 2^32 / 36 - 1 elements (about 492^3); larger ones are refused, not wrapped
 constexpr long K19_MAX_PLANE = (1LL << 32) / 36 - 1;
 
+// to * 4 + tp of the launch: tile per wave = (32 TO output channels) x (32 TP pixels); measured on the step's shapes
+// (tools/bench_conv3x3.py with MLAGG_K19_TILE, profiles/round3_h_conv3x3_k19_vs_miopen_tiles.log): 2 x 2 (two workgroups per CU, most
+// waves) everywhere except outputs that fill 96-channel groups exactly on large maps.  conv_fwd launches what this returns and
+// mlagg_conv3x3_fwd_tile reports it.
+int fwd_tile(int O, long P, int W)
+{
+    int to = O <= 32 ? 1 : 2, tp = 2;
+    if (O % 96 == 0 && P >= 16384) {
+        to = 3;
+        tp = P >= 65536 ? 2 : 1;
+    }
+    if (W % tp) tp = 1;                                     // the kernel wants a lane's pixel run inside one image row
+    static const char *env = getenv("MLAGG_K19_TILE");
+    if (env && env[0] >= '1' && env[0] <= '3' && env[1] == ',' && env[2] >= '1' && env[2] <= '3') {
+        to = env[0] - '0';
+        tp = env[2] - '0';
+        if (32 * (to - 1) >= O) to = (O + 31) / 32;
+        if (W % tp) tp = 1;
+    }
+    if (tp == 3) tp = 2 - (W & 1);                          // three-pixel runs are not instantiated
+    return to * 4 + tp;
+}
+
 int conv_fwd(const float *x, long x_batch, const float *w, int transposed, const float *bias, float *y, long y_batch, void *workspace,
              int B, int O, int I, int D, int H, int W, int dt, void *stream)
 {
@@ -819,24 +842,7 @@ int conv_fwd(const float *x, long x_batch, const float *w, int transposed, const
         hipLaunchKernelGGL(conv3x3_weight_image_kernel<MLAGG_DTYPE_F16>, igrid, dim3(256), 0, st, w, img, O, I, ntaps, transposed ? 1 : 0);
     else
         hipLaunchKernelGGL(conv3x3_weight_image_kernel<MLAGG_DTYPE_BF16X3>, igrid, dim3(256), 0, st, w, img, O, I, ntaps, transposed ? 1 : 0);
-    // tile per wave = (32 TO output channels) x (32 TP pixels); measured on the step's shapes (tools/bench_conv3x3.py with
-    // MLAGG_K19_TILE, profiles/round3_h_conv3x3_k19_vs_miopen_tiles.log): 2 x 2 (two workgroups per CU, most waves) everywhere
-    // except outputs that fill 96-channel groups exactly on large maps
-    int to = O <= 32 ? 1 : 2, tp = 2;
-    if (O % 96 == 0 && P >= 16384) {
-        to = 3;
-        tp = P >= 65536 ? 2 : 1;
-    }
-    if (W % tp) tp = 1;                                     // the kernel wants a lane's pixel run inside one image row
-    static const char *env = getenv("MLAGG_K19_TILE");
-    if (env && env[0] >= '1' && env[0] <= '3' && env[1] == ',' && env[2] >= '1' && env[2] <= '3') {
-        to = env[0] - '0';
-        tp = env[2] - '0';
-        if (32 * (to - 1) >= O) to = (O + 31) / 32;
-        if (W % tp) tp = 1;
-    }
-    if (tp == 3) tp = 2 - (W & 1);                          // three-pixel runs are not instantiated
-    switch (to * 4 + tp) {
+    switch (fwd_tile(O, P, W)) {
     case 1 * 4 + 1: launch<1, 1>(x, img, bias, y, g, dt, st); break;
     case 1 * 4 + 2: launch<1, 2>(x, img, bias, y, g, dt, st); break;
     case 2 * 4 + 1: launch<2, 1>(x, img, bias, y, g, dt, st); break;
@@ -854,6 +860,9 @@ extern "C" int mlagg_conv3x3_supported(int O, int I, int H, int W)
     return O > 0 && I > 0 && (I % 16) == 0 && H > 0 && W > 0 && (long)H * W >= 96 && (long)H * W <= (1LL << 32) / 36 - 1 &&
            (long)I * H * W * 4 < (1L << 31) - 64;
 }
+
+// to * 4 + tp of the tile conv_fwd launches for O output channels on a (D, H, W) map (D = 1: 2-D); host only
+extern "C" int mlagg_conv3x3_fwd_tile(int O, int D, int H, int W) { return fwd_tile(O, (long)D * H * W, W); }
 
 // bytes of the weight image: 3 pieces x 9 taps x O x I bf16
 extern "C" size_t mlagg_conv3x3_workspace_bytes(int O, int I) { return O > 0 && I > 0 ? (size_t)3 * 9 * O * I * 2 : 0; }
@@ -901,10 +910,18 @@ extern "C" int mlagg_conv3x3x3_wgrad_supported(int O, int I, int D, int H, int W
 }
 
 namespace {
+// the form of a weight gradient: 0 = 32 x 32 tiles with nine taps per wave (every volume), 1 / 2 = the 16-wide tiles (2-D layers) with
+// fragment-shaped / LDS-staged loads (w16_tiles).  wgrad3 launches what this returns and mlagg_conv3x3_wgrad_form reports it.
+int wgrad_form(int O, int I, int D, int dt, int &to, int &ti)
+{
+    to = ti = 0;
+    return D == 1 ? w16_tiles(O, I, dt, to, ti) : 0;
+}
+
 size_t wgrad_ws(int B, int O, int I, int D, int H, int W)
 {
     int to = 0, ti = 0;
-    if (D == 1 && w16_tiles(O, I, MLAGG_DTYPE_BF16X3, to, ti)) {
+    if (wgrad_form(O, I, D, MLAGG_DTYPE_BF16X3, to, ti)) {
         W16Geom g16;
         if (make_w16geom(g16, B, O, I, H, W, (long)O * H * W, (long)I * H * W, to, ti)) return 0;
         return (size_t)g16.nbs * 9 * O * I;
@@ -922,7 +939,7 @@ int wgrad3(const float *dy, long dy_batch, const float *x, long x_batch, float *
     if ((reinterpret_cast<uintptr_t>(dy) & 15) || (reinterpret_cast<uintptr_t>(x) & 3)) return MLAGG_E_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int to = 0, ti = 0;
-    const int w16 = D == 1 ? w16_tiles(O, I, dt, to, ti) : 0;
+    const int w16 = wgrad_form(O, I, D, dt, to, ti);
     // the LDS-staged form loads 16-byte chunks of x and addresses rows with 32-bit float offsets
     const bool lds_ok = !(reinterpret_cast<uintptr_t>(x) & 15) && (long)max(O, I) * H * W < (1L << 30);
     if (w16) {
@@ -964,6 +981,16 @@ int wgrad3(const float *dy, long dy_batch, const float *x, long x_batch, float *
     return (int)hipGetLastError();
 }
 }  // namespace
+
+// form * 4 + ti of the weight gradient wgrad3 launches (D = 1: 2-D) in the operand form `dtype`: form 0 (ti reported as 0), 1 or 2 as
+// wgrad_form names them; the LDS-staged form 2 stands for an x that is 16-byte aligned.  Host only.
+extern "C" int mlagg_conv3x3_wgrad_form(int O, int I, int D, int dtype)
+{
+    if (!opmode::valid(dtype) || O <= 0 || I <= 0 || D <= 0) return MLAGG_E_UNSUPPORTED;
+    int to = 0, ti = 0;
+    const int form = wgrad_form(O, I, D, dtype, to, ti);
+    return form * 4 + (form ? ti : 0);
+}
 
 extern "C" size_t mlagg_conv3x3_wgrad_workspace_floats(int B, int O, int I, int H, int W) { return wgrad_ws(B, O, I, 1, H, W); }
 extern "C" size_t mlagg_conv3x3x3_wgrad_workspace_floats(int B, int O, int I, int D, int H, int W) { return D > 1 ? wgrad_ws(B, O, I, D, H, W) : 0; }

@@ -2484,12 +2484,34 @@ K19_3D = _os.environ.get("MLAGG_K19_3D", "1") == "1"
 K19_3D_WGRAD = _os.environ.get("MLAGG_K19_3D_WGRAD", "1") == "1"
 
 
+# K19 adds every product of an output element into ONE fp32 accumulator chain (DESIGN 4i), and the chain's rounding error grows with
+# its length: measured against float64 as a share of the output's maximum, 4.5e-7 at 144 products, 1.0e-6 at 864, 1.3e-6 at 1728 and
+# 2.65e-6 at the 2592 of a 96-channel 3 x 3 x 3 contraction (tests/test_conv_kernel_paths_gpu.py, F16) -- past the 2e-6 of an fp32
+# convolution that the kernel is held to.  With 27 taps per channel the volumes get there at 3 x fewer channels than the maps, so their
+# contraction runs in blocks of at most this many channels (864 products), each a launch of its own on a channel block of x, and the
+# partial outputs are added: a blocked sum.
+K19_3D_CHAIN_CH = 32
+
+
+def _k19_3d_blocks(I):
+    """[(first channel, end)] of the contraction blocks of a 3 x 3 x 3 product: equal multiples of 16, at most K19_3D_CHAIN_CH each."""
+    n = -(-I // K19_3D_CHAIN_CH)
+    step = -(-I // (16 * n)) * 16
+    return [(c0, min(c0 + step, I)) for c0 in range(0, I, step)]
+
+
 def _conv3x3x3_k19(x, xb, w, transposed, O, I, dims):
     B = x.shape[0]
     D, H, W = dims
-    y = torch.empty(B, O, D, H, W, device=x.device, dtype=torch.float32)
-    ws = torch.empty(_lib.lib().mlagg_conv3x3x3_workspace_bytes(O, I), device=x.device, dtype=torch.uint8)
-    _launch("mlagg_conv3x3x3_fwd", _ptr(x), xb, _ptr(w), int(transposed), None, _ptr(y), O * D * H * W, _ptr(ws), B, O, I, D, H, W)
+    y = None
+    for c0, c1 in _k19_3d_blocks(I):
+        # the block's weight: rows of the layer's forward weight (contraction first) for a data gradient, else a copy of its columns
+        xc, wc = (x, w) if (c0, c1) == (0, I) else (x[:, c0:c1], w[c0:c1] if transposed else w[:, c0:c1].contiguous())
+        part = torch.empty(B, O, D, H, W, device=x.device, dtype=torch.float32)
+        ws = torch.empty(_lib.lib().mlagg_conv3x3x3_workspace_bytes(O, c1 - c0), device=x.device, dtype=torch.uint8)
+        _launch("mlagg_conv3x3x3_fwd", _ptr(xc), xb, _ptr(wc), int(transposed), None, _ptr(part), O * D * H * W, _ptr(ws), B, O, c1 - c0,
+                D, H, W)
+        y = part if y is None else y.add_(part)
     return y
 
 

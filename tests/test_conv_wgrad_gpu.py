@@ -4,6 +4,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests._conv_kernel_cases import rounded_products as _rounded_products
+
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -287,17 +289,6 @@ def test_conv1x1_accumulates_into_its_output(B, I, O, H, W):
     want = y0.double() + F.conv2d(x.double(), w.double().view(I, O, 1, 1))
     err = float((y.double() - want).abs().max() / want.abs().max())
     assert err < 2e-6, err
-
-
-def _rounded_products(x, w, gy, pad, t):
-    """The three products of a stride-1 convolution as the reference's autocast step computes them (nnUNetTrainer.py:848): operands
-    rounded to the 16-bit type `t`, exact sums (float64 here; the kernels sum in fp32)."""
-    r = lambda v: v.to(t).double()                                                          # noqa: E731
-    xr, wr, gr = r(x), r(w), r(gy)
-    y = F.conv2d(xr, wr, None, 1, pad)
-    dx = torch.nn.grad.conv2d_input(xr.shape, wr, gr, 1, pad)
-    dW = torch.nn.grad.conv2d_weight(xr, wr.shape, gr, 1, pad)
-    return y, dx, dW
 
 
 @pytest.mark.gpu
