@@ -184,6 +184,10 @@ int mlagg_linear_lp_fwd(const float *x, int x_stride, const float *w, const floa
 int mlagg_linear_lp_dgrad(const float *dy, int dy_stride, const float *w, float *dx, int dx_stride, int M, int O, int I,
                           int dtype, void *stream);
 size_t mlagg_linear_wgrad_workspace_floats(int M, int O, int I);
+/* The launch geometry of K5w for contiguous operands (host arithmetic, what the launcher itself decides with): out5 = {to, ti: 32-wide
+ * tiles per wave along O and I; slab: tokens per wave; nslabs; ogroups * 65536 + igroups: 96-wide column groups}.  0, or the error of
+ * the launch for these sizes. */
+int mlagg_linear_wgrad_geometry(int M, int O, int I, int *out5);
 int mlagg_linear_wgrad(const float *dy, int dy_stride, const float *x, int x_stride, float *dW, float *db,
                        float *workspace, int M, int O, int I, void *stream);
 /* The same gradient with every fp32 operand as three bf16 pieces on v_mfma_f32_32x32x16_bf16 (six partial products, fp32
@@ -659,6 +663,9 @@ size_t mlagg_weight_image_bytes(int rows, int cols);
 int mlagg_weight_image(const float *w, int w_stride, void *img, void *img_t, int N, int K, void *stream);
 int mlagg_weight_images(const void *jobs, int n_jobs, int max_tiles, void *stream);
 int mlagg_linear_x3_supported(int M, int N, int K);
+/* nw * 10 + tn of the default dispatch (workgroup = nw waves of 32 rows x tn column tiles of 32: 22, 42, 23 or 43; host arithmetic, the
+ * launcher's own rule), MLAGG_E_UNSUPPORTED where mlagg_linear_x3_supported is 0. */
+int mlagg_linear_x3_tile(int M, int N, int K);
 int mlagg_linear_x3(const float *x, int x_stride, const void *w_image, const float *bias, float *y, int y_stride, float *y_act,
                     const float *pre, int pre_stride, int M, int N, int K, int epilogue, void *stream);
 

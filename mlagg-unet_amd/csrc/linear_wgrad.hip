@@ -342,6 +342,13 @@ int make_geom(WGeom &g, int M, int O, int I, int dys, int xs)
     return 0;
 }
 
+// tiles per wave (to, ti): full 3x3 groups when a dimension exceeds 96, else exactly what the dimension needs
+void wave_tiles(const WGeom &g, int &to, int &ti)
+{
+    to = g.ogroups > 1 ? TMAX : (g.O + 31) / 32;
+    ti = g.igroups > 1 ? TMAX : (g.I + 31) / 32;
+}
+
 template <int TO, int TI>
 void launch(const float *dy, const float *x, float *part, const WGeom &g, hipStream_t st, bool x3)
 {
@@ -360,6 +367,18 @@ extern "C" size_t mlagg_linear_wgrad_workspace_floats(int M, int O, int I)
     return (size_t)g.nslabs * ((size_t)O * I + O);
 }
 
+extern "C" int mlagg_linear_wgrad_geometry(int M, int O, int I, int *out5)
+{
+    if (!out5) return MLAGG_E_NULLPTR;
+    WGeom g;
+    if (int rc = make_geom(g, M, O, I, O, I)) return rc;
+    wave_tiles(g, out5[0], out5[1]);
+    out5[2] = g.slab;
+    out5[3] = g.nslabs;
+    out5[4] = (int)((unsigned)g.ogroups * 65536u + (unsigned)g.igroups);
+    return 0;
+}
+
 namespace {
 int wgrad(const float *dy, int dy_stride, const float *x, int x_stride, float *dW, float *db, float *workspace, int M, int O, int I,
           bool x3, void *stream)
@@ -368,9 +387,8 @@ int wgrad(const float *dy, int dy_stride, const float *x, int x_stride, float *d
     WGeom g;
     if (int rc = make_geom(g, M, O, I, dy_stride, x_stride)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // tiles per wave: full 3x3 groups when a dimension exceeds 96, else exactly what the dimension needs
-    const int to = g.ogroups > 1 ? TMAX : (O + 31) / 32;
-    const int ti = g.igroups > 1 ? TMAX : (I + 31) / 32;
+    int to, ti;
+    wave_tiles(g, to, ti);
     {
         MLAGG_TIMED(K_LINEAR_WGRAD, st);
         switch (to * 4 + ti) {

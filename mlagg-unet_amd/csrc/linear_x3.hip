@@ -89,10 +89,12 @@ linear_x3_kernel(const float *__restrict__ X, const unsigned short *__restrict__
 #pragma unroll
         for (int j = 0; j < NLD; ++j) R.rb[j] = *reinterpret_cast<const u32x4 *>(Wimg + (size_t)src_off[j] + kc);
         // K % 4 == 0: a float4 lies inside the row or (zero-padded tail of the last chunk) outside it as a whole; outside: a valid
-        // address is read and the value dropped WHEN IT IS STAGED (a select here would make the wave wait for the load at once)
+        // address is read and the value dropped WHEN IT IS STAGED (a select here would make the wave wait for the load at once).
+        // The valid address is the row's FIRST float4: the thread's own column of chunk 0 lies past the row where K < 32
         R.ok = kc + 4 * (tid & 7) < g.K;
+        const int koff = R.ok ? kc : -4 * (tid & 7);
 #pragma unroll
-        for (int i = 0; i < NLA; ++i) R.ra[i] = *reinterpret_cast<const float4 *>(xa[i] + (R.ok ? kc : 0));
+        for (int i = 0; i < NLA; ++i) R.ra[i] = *reinterpret_cast<const float4 *>(xa[i] + koff);
     };
     auto stage = [&](const Regs &R) {
         // unconditional stores: the threads past the last item repeat it (same address, same value)
@@ -303,6 +305,26 @@ extern "C" int mlagg_linear_x3_supported(int M, int N, int K)
     return M > 0 && N > 0 && K > 0 && (K & 7) == 0 && (size_t)3 * N * ((K + 31) & ~31) < (1ull << 32);
 }
 
+namespace {
+// nw * 10 + tn of a launch (profiles/round4_d_linear_x3_variants.log): 96-column tiles only where N is a multiple of 96 AND the grid is
+// long (stage 0 / 1 projections: >= 1024 workgroups); everywhere else 64-column tiles -- a third more workgroups per CU, 10-15 % faster
+// on the 10 240- and 2 560-token shapes; 64-row workgroups for the pooled branch's few hundred rows.  `forced` = <NW><TN> takes the
+// place of the rule (MLAGG_X3_TILE: benchmarks); reported with forced = 0 by mlagg_linear_x3_tile
+int x3_tile(int M, int N, int forced)
+{
+    int nw = M <= 1024 ? 2 : 4, tn = 2;
+    if (N % 96 == 0 && (long)((M + 127) / 128) * (N / 96) >= 1024) tn = 3;
+    if (forced) { nw = forced / 10; tn = forced % 10; }
+    return nw * 10 + tn;
+}
+}  // namespace
+
+extern "C" int mlagg_linear_x3_tile(int M, int N, int K)
+{
+    if (!mlagg_linear_x3_supported(M, N, K)) return MLAGG_E_UNSUPPORTED;
+    return x3_tile(M, N, 0);
+}
+
 extern "C" int mlagg_linear_x3(const float *x, int x_stride, const void *w_image, const float *bias, float *y, int y_stride,
                                float *y_act, const float *pre, int pre_stride, int M, int N, int K, int epilogue, void *stream)
 {
@@ -313,17 +335,13 @@ extern "C" int mlagg_linear_x3(const float *x, int x_stride, const void *w_image
     hipStream_t st = static_cast<hipStream_t>(stream);
     MLAGG_TIMED(K_LINEAR_FWD, st);
     const unsigned short *img = static_cast<const unsigned short *>(w_image);
-    // tile shape (profiles/round4_d_linear_x3_variants.log): 96-column tiles only where N is a multiple of 96 AND the grid is long
-    // (stage 0 / 1 projections: >= 1024 workgroups); everywhere else 64-column tiles -- a third more workgroups per CU, 10-15 % faster
-    // on the 10 240- and 2 560-token shapes; 64-row workgroups for the pooled branch's few hundred rows.
     // MLAGG_X3_TILE=<NW><TN> forces one variant (benchmarks)
     static const int forced = mlagg_internal::env_int("MLAGG_X3_TILE", 0);
-    int nw = M <= 1024 ? 2 : 4, tn = 2;
-    if (N % 96 == 0 && (long)((M + 127) / 128) * (N / 96) >= 1024) tn = 3;
-    if (forced) { nw = forced / 10; tn = forced % 10; }
-    if (nw == 4 && tn == 3) return launch_x3<4, 3>(x, img, bias, y, y_act, pre, g, epilogue, st);
-    if (nw == 4 && tn == 2) return launch_x3<4, 2>(x, img, bias, y, y_act, pre, g, epilogue, st);
-    if (nw == 2 && tn == 3) return launch_x3<2, 3>(x, img, bias, y, y_act, pre, g, epilogue, st);
-    if (nw == 2 && tn == 2) return launch_x3<2, 2>(x, img, bias, y, y_act, pre, g, epilogue, st);
+    switch (x3_tile(M, N, forced)) {
+    case 43: return launch_x3<4, 3>(x, img, bias, y, y_act, pre, g, epilogue, st);
+    case 42: return launch_x3<4, 2>(x, img, bias, y, y_act, pre, g, epilogue, st);
+    case 23: return launch_x3<2, 3>(x, img, bias, y, y_act, pre, g, epilogue, st);
+    case 22: return launch_x3<2, 2>(x, img, bias, y, y_act, pre, g, epilogue, st);
+    }
     return MLAGG_E_UNSUPPORTED;
 }

@@ -40,8 +40,10 @@ SHAPES = [(16384, 192, 96), (4100, 140, 96), (2560, 768, 1536), (640, 384, 768),
 
 @pytest.mark.parametrize("M,N,K", SHAPES)
 def test_linear_x3_matches_float64(M, N, K):
-    """Forward (bias) and the data gradient on the W^T image against float64: strided rows, ragged M / N, K % 32 != 0; the shapes
-    reach the 128 x 96, 128 x 64 and 64 x 64 tile variants of the default dispatch."""
+    """Forward (bias) and the data gradient on the W^T image against float64: strided rows, ragged M / N, K % 32 != 0.  Under the
+    default rule the shapes reach the 128 x 64 and 64 x 64 tile variants only (<4,2> and, from 1024 rows down, <2,2>): the 96-column
+    tile needs ceil(M / 128) * (N / 96) >= 1024 workgroups and the largest shape here, (16384, 192, 96), has 256.  The 128 x 96 and
+    64 x 96 variants are compared with float64 in tests/test_linear_kernel_paths_gpu.py."""
     from mlagg_unet_amd import _lib
     lib = _lib.lib()
     st = torch.cuda.current_stream().cuda_stream
