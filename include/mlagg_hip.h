@@ -87,6 +87,18 @@ int mlagg_selscan_lowrank_bwd(const float *u, const float *dtr, const float *Wdt
                               const float *chunk_state, float *du, float *ddtr, float *dWdt, float *dA, float *dB,
                               float *dC, float *dD, float *ddelta_bias, float *workspace, int batch, int dim, int L,
                               int N, int G, int delta_softplus, void *stream);
+/* What the K1 launchers choose for (dim, L, G) in the direct form (R = 0) or the low-rank form of rank R (host only, nothing is
+ * launched; the launchers decide through the same code, MLAGG_SELSCAN_BWD_BLOCKED included): form * 2 + fast, or
+ * MLAGG_E_UNSUPPORTED for a geometry the launchers refuse (and for R outside 0..4).
+ *   fast: 1 when the forward and the backward's local pass run the instantiation without range checks (32-channel blocks that
+ *         divide the group of H = dim / G channels, L % 4 == 0);
+ *   form: the backward's main kernel.  0: channel blocks (H > 96, or the override), dB / dC / d(dtr) by float atomics when a group
+ *         has more than one block.  1..5: one wave per group, selscan_bwd_group_kernel<RT, VEC, FULL, WHOLE> with RT the
+ *         compile-time rank (0: direct form, 3: rank 3, 4: any rank, read at run time), VEC: L % 4 == 0, FULL: H % 16 == 0,
+ *         WHOLE: L % 64 == 0 --
+ *           1 <0 or 3, true, true, true>    2 <0 or 3, true, true, false>    3 <4, true, true, false>
+ *           4 <0 or 4, true, false, false>  5 <0 or 4, false, false, false> */
+int mlagg_selscan_path(int dim, int L, int G, int R);
 
 /* ------------------------------------------------------------------------------------------
  * K3: 3x3-window differential attention + RMSNorm + LePE, the `local=True` branch of

@@ -1177,6 +1177,34 @@ extern "C" size_t mlagg_selscan_bwd_workspace_floats(int batch, int dim, int L, 
 
 namespace {
 
+// What the launchers below choose for a geometry: scan_fast (both passes) and scan_path = (backward form) * 2 + fast, which
+// mlagg_selscan_path reports.
+//   fast: the forward / backward-local instantiation with every lane active and every access in range -- 32-channel blocks that
+//         divide the group, L a multiple of 4 (the model's shapes at 256^2);
+//   form: groups of up to 96 channels (every MLAgg-UNet shape: 96) take the group-per-wave kernel <RT, VEC, FULL, WHOLE> (VEC:
+//         L % 4 == 0, FULL: Hc % 16 == 0, WHOLE: L % 64 == 0; the direct form and rank 3 have instantiations of their own, every
+//         other rank and every shape that is not VEC and FULL runs the run-time-rank one); wider groups, or all with
+//         MLAGG_SELSCAN_BWD_BLOCKED=1, the channel-block kernel with float-atomic accumulation of dB / dC across the blocks.
+enum { PATH_BLOCKED = 0, PATH_GROUP_WHOLE = 1, PATH_GROUP_FAST = 2, PATH_GROUP_FULL = 3, PATH_GROUP_VEC = 4, PATH_GROUP_SCALAR = 5 };
+
+bool scan_fast(const ScanGeom &gm, bool LR, int R)
+{
+    return (gm.L & 3) == 0 && gm.Hc % gm.CB == 0 && block_threads(gm) == 128 && 4 * gm.CB == 128 && (!LR || R >= 1);
+}
+
+int scan_path(const ScanGeom &gm, bool LR, int R)
+{
+    const int L = gm.L;
+    int form;
+    const bool vecL = (L & 3) == 0, full = (gm.Hc & 15) == 0, whole = L % TC == 0;
+    if (gm.Hc > 96 || mlagg_internal::getenv_flag("MLAGG_SELSCAN_BWD_BLOCKED")) form = PATH_BLOCKED;
+    else if ((!LR || R == 3) && vecL && full) form = whole ? PATH_GROUP_WHOLE : PATH_GROUP_FAST;
+    else if (vecL && full) form = PATH_GROUP_FULL;
+    else if (vecL) form = PATH_GROUP_VEC;
+    else form = PATH_GROUP_SCALAR;
+    return form * 2 + (scan_fast(gm, LR, R) ? 1 : 0);
+}
+
 template <bool LR>
 int scan_forward(const float *u, const float *delta, const float *Wdt, int R, const float *A, const float *B,
                  const float *C, const float *D, const float *delta_bias, float *out, float *chunk_state, int batch,
@@ -1191,7 +1219,7 @@ int scan_forward(const float *u, const float *delta, const float *Wdt, int R, co
     const dim3 grid(gm.nchunks, G * gm.nblk, batch), block(block_threads(gm));
     const size_t lds = (size_t)(2 * gm.CB * UP + 2 * ST * BP + (LR ? 2 * RMAX * ST : 0)) * sizeof(float);
     // every lane active, every access in range (see the kernel): the model's shapes at 256^2
-    const bool fast = (L & 3) == 0 && gm.Hc % gm.CB == 0 && block.x == 128 && 4 * gm.CB == 128 && (!LR || R >= 1);
+    const bool fast = scan_fast(gm, LR, R);                    // the forward does not read the backward's override
     { MLAGG_TIMED(K_SELSCAN_FWD_LOCAL, st);
       if (fast) hipLaunchKernelGGL((selscan_fwd_kernel<false, LR, true>), grid, block, lds, st, u, delta, Wdt, R, A, B, C, D,
                                    delta_bias, out, cstate, cdsum, csub, gm, delta_softplus);
@@ -1231,7 +1259,8 @@ int scan_backward(const float *u, const float *delta, const float *Wdt, int R, c
     const dim3 gridb(gb.nchunks, G * gb.nblk, batch), blockb(block_threads(gb));
     // groups of up to 96 channels (every MLAgg-UNet shape: 96): the group-per-wave kernel; wider groups: the channel-block
     // kernel with float-atomic accumulation of dB / dC across the blocks of a group
-    const bool group_form = gm.Hc <= 96 && !mlagg_internal::getenv_flag("MLAGG_SELSCAN_BWD_BLOCKED");
+    const int path = scan_path(gm, LR, R), form = path >> 1;
+    const bool group_form = form != PATH_BLOCKED;
     const int atomic_bc = !group_form && gb.nblk > 1;
     if (atomic_bc) {
         const size_t bytes = (size_t)batch * G * NS * L * sizeof(float);
@@ -1240,7 +1269,7 @@ int scan_backward(const float *u, const float *delta, const float *Wdt, int R, c
         if (LR) (void)hipMemsetAsync(ddelta, 0, (size_t)batch * G * R * L * sizeof(float), st);
     }
     const size_t lds1 = (size_t)(2 * gm.CB * UP + ST * BP + (LR ? 2 * RMAX * ST : 0)) * sizeof(float);
-    const bool fast = (L & 3) == 0 && gm.Hc % gm.CB == 0 && block.x == 128 && 4 * gm.CB == 128 && (!LR || R >= 1);
+    const bool fast = path & 1;
     { MLAGG_TIMED(K_SELSCAN_BWD_LOCAL, st);
       if (fast) hipLaunchKernelGGL((selscan_bwd_local_kernel<LR, true>), grid, block, lds1, st, delta, Wdt, R, A, C, delta_bias,
                                    dout, cq, gm, delta_softplus);
@@ -1255,15 +1284,14 @@ int scan_backward(const float *u, const float *delta, const float *Wdt, int R, c
 #define MLAGG_GROUP_LAUNCH(RT, VEC, FULL, WHOLE) hipLaunchKernelGGL((selscan_bwd_group_kernel<RT, VEC, FULL, WHOLE>), gridg, dim3(64), 0, st, u, delta, \
             Wdt, R, A, B, C, D, delta_bias, dout, cstate, csub, cq, du, ddelta, dB, dC, part, gm, delta_softplus)
         constexpr int RGEN = LR ? RMAX : 0;
-        const bool vecL = (L & 3) == 0, full = (gm.Hc & 15) == 0, whole = L % TC == 0;
         constexpr int RFAST = LR ? 3 : 0;
-        if ((!LR || R == 3) && vecL && full) {                    // the model's shapes: rank 3, 96-channel groups
-            if (whole) MLAGG_GROUP_LAUNCH(RFAST, true, true, true);
-            else MLAGG_GROUP_LAUNCH(RFAST, true, true, false);
+        switch (form) {
+        case PATH_GROUP_WHOLE: MLAGG_GROUP_LAUNCH(RFAST, true, true, true); break;   // the model's shapes: rank 3, 96-channel groups
+        case PATH_GROUP_FAST: MLAGG_GROUP_LAUNCH(RFAST, true, true, false); break;
+        case PATH_GROUP_FULL: MLAGG_GROUP_LAUNCH(RGEN, true, true, false); break;
+        case PATH_GROUP_VEC: MLAGG_GROUP_LAUNCH(RGEN, true, false, false); break;
+        default: MLAGG_GROUP_LAUNCH(RGEN, false, false, false); break;
         }
-        else if (vecL && full) MLAGG_GROUP_LAUNCH(RGEN, true, true, false);
-        else if (vecL) MLAGG_GROUP_LAUNCH(RGEN, true, false, false);
-        else MLAGG_GROUP_LAUNCH(RGEN, false, false, false);
 #undef MLAGG_GROUP_LAUNCH
     } else {
         const size_t lds3 = (size_t)(3 * gb.CB * UP + 2 * ST * BP + 2 * ST * NS + (LR ? 2 * RMAX * ST + 8 * 128 : 0) + UP + gb.CB * UP) * sizeof(float);
@@ -1325,4 +1353,12 @@ extern "C" int mlagg_selscan_lowrank_bwd(const float *u, const float *dtr, const
     if (R < 1 || R > RMAX) return MLAGG_E_UNSUPPORTED;
     return scan_backward<true>(u, dtr, Wdt, R, A, B, C, D, delta_bias, dout, chunk_state, du, ddtr, dWdt, dA, dB, dC, dD,
                                ddelta_bias, workspace, batch, dim, L, N, G, delta_softplus, stream);
+}
+
+extern "C" int mlagg_selscan_path(int dim, int L, int G, int R)
+{
+    if (R < 0 || R > RMAX) return MLAGG_E_UNSUPPORTED;
+    ScanGeom gm;
+    if (int rc = make_geom(gm, 1, dim, L, NS, G, SCAN_CB)) return rc;
+    return scan_path(gm, R > 0, R);
 }

@@ -67,28 +67,31 @@ def sel1_orders(L, K, g):
 # ------------------------------------------------------------------------------------------------
 # the two scans on (b, d, L) sequences
 # ------------------------------------------------------------------------------------------------
-def oracle_scan(u, delta, A, B, C, D, bias, dout):
+def oracle_scan(u, delta, A, B, C, D, bias, dout, softplus=True):
     """oracle/selscan_ref.c: y and (du, ddelta, dA, dB, dC, dD, dbias), computed in double and rounded to float once."""
     n = lambda t: None if t is None else t.contiguous().numpy()                                  # noqa: E731
-    y = CO.selscan_fwd(n(u), n(delta), n(A), n(B), n(C), n(D), n(bias), True)
-    grads = CO.selscan_bwd(n(u), n(delta), n(A), n(B), n(C), n(D), n(bias), n(dout), True)
+    y = CO.selscan_fwd(n(u), n(delta), n(A), n(B), n(C), n(D), n(bias), softplus)
+    grads = CO.selscan_bwd(n(u), n(delta), n(A), n(B), n(C), n(D), n(bias), n(dout), softplus)
     return torch.from_numpy(y), tuple(torch.from_numpy(v) for v in grads)
 
 
-def plain_fp32_scan(u, delta, A, B, C, D, bias, dout):
+def plain_fp32_scan(u, delta, A, B, C, D, bias, dout, softplus=True):
     """The same recurrence one step after the other in float32 on the host, gradients by autograd.  Not the truth: the error
     ordinary fp32 arithmetic makes on these inputs."""
     leaves = [t.detach().clone().float().requires_grad_(True) for t in (u, delta, A, B, C, D, bias)]
     u_, x_, A_, B_, C_, D_, b_ = leaves
     b, d, L = u_.shape
     Hc = d // B_.shape[1]
-    dl = F.softplus(x_ + b_[None, :, None])                                                      # threshold 20, as the oracle
+    dl = x_ + b_[None, :, None]
+    if softplus:
+        dl = F.softplus(dl)                                                                      # threshold 20, as the oracle
     Bd, Cd = B_.repeat_interleave(Hc, dim=1), C_.repeat_interleave(Hc, dim=1)                    # (b, d, n, L)
     h = torch.zeros(b, d, A_.shape[1])
     ys = []
-    for l in range(L):
-        h = torch.exp(dl[:, :, l, None] * A_) * h + (dl[:, :, l] * u_[:, :, l])[:, :, None] * Bd[..., l]
-        ys.append((Cd[..., l] * h).sum(-1) + D_ * u_[:, :, l])
+    # one unbind per operand: a select per step would hand autograd a full-size zero tensor per step and operand
+    for dl_l, u_l, B_l, C_l in zip(dl.unbind(-1), u_.unbind(-1), Bd.unbind(-1), Cd.unbind(-1)):
+        h = torch.exp(dl_l[:, :, None] * A_) * h + (dl_l * u_l)[:, :, None] * B_l
+        ys.append((C_l * h).sum(-1) + D_ * u_l)
     y = torch.stack(ys, -1)
     y.backward(dout.float())
     return y.detach(), tuple(t.grad for t in leaves)
