@@ -400,6 +400,11 @@ int mlagg_conv3x3_s2_dgrad(const float *dy, long dy_batch, long dy_chan_stride, 
 size_t mlagg_conv3x3_s2t_wgrad_workspace_floats(int B, int O, int I, int H, int W);
 int mlagg_conv3x3_s2t_wgrad(const float *x, long x_batch, const float *dy, long dy_batch, long dy_chan_stride, long dy_row_stride,
                             float *dW, float *workspace, int B, int O, int I, int H, int W, int dtype, void *stream);
+/* Host arithmetic, what the launchers themselves decide with.  mlagg_conv3x3_s2t_tile: the 32-row tiles per workgroup (1 or 2) of the
+ * forward (R = O) / data gradient (R = I) kernel.  mlagg_conv3x3_s2t_wgrad_geometry: out3 = {cw: 16-pixel blocks per input row;
+ * per_part: blocks per partial sum; nparts: partial sums per sample}; 0, or the error of the launch for these sizes. */
+int mlagg_conv3x3_s2t_tile(int R);
+int mlagg_conv3x3_s2t_wgrad_geometry(int B, int O, int I, int H, int W, int *out3);
 
 /* ------------------------------------------------------------------------------------------
  * K17: key / value reduction of the pooled attention branch, pooled (B, (H/r)(W/r), d) = r x r window mean of GELU(s), s (B, H W, d)
@@ -656,6 +661,12 @@ int mlagg_conv_taps(const float *xp, long x_batch, long x_row, const float *weig
                     int ntaps, float *y, int B, int O, int I, int D, int H, int W, void *stream);
 int mlagg_conv_wgrad_taps(const float *A, long a_batch, long a_row, const float *B, long b_batch, long b_row, const long *tap_off,
                           int ntaps, long Q, int O, int I, int batch, float *dW, int accumulate, float *workspace, void *stream);
+/* The launch geometry of mlagg_conv_wgrad_taps (host arithmetic, what the launcher itself decides with): out5 = {slab: voxels per
+ * wave; nslabs; tap groups of at most nine taps; 32-wide tiles along O; along I}.  0, or the error of the launch for these sizes. */
+int mlagg_conv_wgrad_taps_geometry(int batch, long Q, int O, int I, int ntaps, int *out5);
+/* The launch geometry of mlagg_conv_taps: out4 = {Q: voxels of the padded box; workgroups of 512 voxels; 32-row output tiles; bytes
+ * of the LDS weight image}.  0, or the error of the launch for these sizes. */
+int mlagg_conv_taps_geometry(int O, int I, int D, int H, int W, int ntaps, long *out4);
 
 /* ------------------------------------------------------------------------------------------
  * K5, round-4 form (csrc/linear_x3.hip): y (M, N) = x (M, K) . W (N, K)^T for token-major activations, fp32 in / out, split-bf16

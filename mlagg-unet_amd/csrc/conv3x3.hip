@@ -886,7 +886,8 @@ extern "C" int mlagg_conv3x3_fwd_lp(const float *x, long x_batch, const float *w
 // the same for 3 x 3 x 3 kernels on (B, C, D, H, W) volumes (nine kernel rows (kz, ky) of three taps each)
 extern "C" int mlagg_conv3x3x3_supported(int O, int I, int D, int H, int W)
 {
-    return O > 0 && I > 0 && (I % 16) == 0 && D > 0 && H > 0 && W > 0 && (long)D * H * W >= 96 && (long)D * H * W <= (1LL << 32) / 36 - 1 &&
+    // D > 1, as mlagg_conv3x3x3_fwd asks: a one-slice volume is the tap GEMMs' (K16 / K15)
+    return O > 0 && I > 0 && (I % 16) == 0 && D > 1 && H > 0 && W > 0 && (long)D * H * W >= 96 && (long)D * H * W <= (1LL << 32) / 36 - 1 &&
            (long)I * D * H * W * 4 < (1L << 31) - 64;
 }
 

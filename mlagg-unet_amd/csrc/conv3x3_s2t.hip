@@ -347,6 +347,9 @@ bool shape_ok(int O, int I, int H, int W)
     return P <= (1L << 26) && (long)I * P * 4 < (1L << 31) - 64 && (long)O * 4 * P * 4 < (1L << 31) - 64 && (long)max(O, I) * P * 4 < (1L << 31) - 64;
 }
 
+// TO of s2t_gemm_kernel: 64-row tiles where the rows fill them, else 32 (the forward of up_0 has 96 output channels)
+int gemm_tile(int R) { return R % 64 == 0 ? 2 : 1; }
+
 template <int MODE, int TO>
 void launch_gemm(const float *src, const unsigned short *img, float *dst, const S2Geom &g, int dt, hipStream_t st)
 {
@@ -385,8 +388,7 @@ int gemm(int mode, const float *src, long src_batch, long src_chan, long src_row
         hipLaunchKernelGGL(s2t_weight_image_kernel<MLAGG_DTYPE_F16>, igrid, dim3(256), 0, st, w, img, g.R, g.K, mode);
     else
         hipLaunchKernelGGL(s2t_weight_image_kernel<MLAGG_DTYPE_BF16X3>, igrid, dim3(256), 0, st, w, img, g.R, g.K, mode);
-    // 64-row tiles where the rows fill them, else 32 (the forward of up_0 has 96 output channels)
-    const bool wide = g.R % 64 == 0;
+    const bool wide = gemm_tile(g.R) == 2;
     if (mode == 0) {
         if (wide) launch_gemm<0, 2>(src, img, dst, g, dt, st);
         else launch_gemm<0, 1>(src, img, dst, g, dt, st);
@@ -421,6 +423,18 @@ extern "C" size_t mlagg_conv3x3_s2t_wgrad_workspace_floats(int B, int O, int I, 
     SWGeom g;
     make_swgeom(g, B, O, I, H, W);
     return (size_t)B * g.nparts * 9 * O * I;
+}
+
+extern "C" int mlagg_conv3x3_s2t_tile(int R) { return R > 0 ? gemm_tile(R) : 0; }
+
+extern "C" int mlagg_conv3x3_s2t_wgrad_geometry(int B, int O, int I, int H, int W, int *out3)
+{
+    if (!out3) return MLAGG_E_NULLPTR;
+    if (B <= 0 || B > (1 << 20) || !shape_ok(O, I, H, W)) return MLAGG_E_UNSUPPORTED;
+    SWGeom g;
+    make_swgeom(g, B, O, I, H, W);
+    out3[0] = g.cw; out3[1] = g.per_part; out3[2] = g.nparts;
+    return 0;
 }
 
 extern "C" int mlagg_conv3x3_s2t_wgrad(const float *x, long x_batch, const float *dy, long dy_batch, long dy_chan_stride, long dy_row_stride,

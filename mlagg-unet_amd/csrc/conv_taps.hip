@@ -117,7 +117,33 @@ conv_taps_kernel(const float *__restrict__ xp, const float *__restrict__ Wt, flo
     }
 }
 
+// the sizes mlagg_conv_taps launches with: the padded box, the workgroups over its voxels and the bytes of the LDS weight image (the
+// launcher and mlagg_conv_taps_geometry both ask here)
+int make_cgeom(CGeom &g, long &nwg, size_t &lds, int O, int I, int D, int H, int W, int ntaps)
+{
+    if (O <= 0 || I <= 0 || D <= 0 || H <= 0 || W <= 0 || (W & 3) || ntaps <= 0 || ntaps > MAXTAPS) return MLAGG_E_UNSUPPORTED;
+    g.O = O; g.I = I; g.ntaps = ntaps; g.D = D; g.H = H; g.W = W;
+    g.Dq = D == 1 ? 1 : D + 2; g.Hq = H + 2; g.Wq = W + 8; g.orgz = D == 1 ? 0 : 1;
+    g.Q = (long)g.Dq * g.Hq * g.Wq;
+    lds = (size_t)ntaps * CCH * 32 * sizeof(float);
+    if (lds > 160 * 1024) return MLAGG_E_UNSUPPORTED;
+    nwg = (g.Q + WG_VOX - 1) / WG_VOX;
+    if (nwg > 2147483647L || (O + 31) / 32 > 65535) return MLAGG_E_UNSUPPORTED;
+    return 0;
+}
+
 }  // namespace
+
+extern "C" int mlagg_conv_taps_geometry(int O, int I, int D, int H, int W, int ntaps, long *out4)
+{
+    if (!out4) return MLAGG_E_NULLPTR;
+    CGeom g;
+    long nwg;
+    size_t lds;
+    if (int rc = make_cgeom(g, nwg, lds, O, I, D, H, W, ntaps)) return rc;
+    out4[0] = g.Q; out4[1] = nwg; out4[2] = (O + 31) / 32; out4[3] = (long)lds;
+    return 0;
+}
 
 // y (B, O, D, H, W) = sum_t sum_i W[o * w_so + i * w_si + t'] * xp[b][i][q + tap_off[t]], t' = t or ntaps - 1 - t (flip), over the
 // padded box (Dq, Hq, Wq) of mlagg_volume_pad's wide stride-1 form holding a (D, H, W) map; xp points at the first box element of
@@ -126,19 +152,16 @@ extern "C" int mlagg_conv_taps(const float *xp, long x_batch, long x_row, const 
                                const long *tap_off, int ntaps, float *y, int B, int O, int I, int D, int H, int W, void *stream)
 {
     if (!xp || !weight || !tap_off || !y) return MLAGG_E_NULLPTR;
-    if (B <= 0 || O <= 0 || I <= 0 || D <= 0 || H <= 0 || W <= 0 || (W & 3) || ntaps <= 0 || ntaps > MAXTAPS || B > 65535) return MLAGG_E_UNSUPPORTED;
+    if (B <= 0 || B > 65535) return MLAGG_E_UNSUPPORTED;
     CGeom g;
-    g.O = O; g.I = I; g.ntaps = ntaps; g.D = D; g.H = H; g.W = W;
-    g.Dq = D == 1 ? 1 : D + 2; g.Hq = H + 2; g.Wq = W + 8; g.orgz = D == 1 ? 0 : 1;
-    g.Q = (long)g.Dq * g.Hq * g.Wq; g.x_row = x_row; g.x_batch = x_batch; g.w_so = w_so; g.w_si = w_si; g.flip = flip;
+    long nwg;
+    size_t lds;
+    if (int rc = make_cgeom(g, nwg, lds, O, I, D, H, W, ntaps)) return rc;
+    g.x_row = x_row; g.x_batch = x_batch; g.w_so = w_so; g.w_si = w_si; g.flip = flip;
     for (int t = 0; t < MAXTAPS; ++t) g.off[t] = tap_off[t < ntaps ? t : 0];
-    const size_t lds = (size_t)ntaps * CCH * 32 * sizeof(float);
-    if (lds > 160 * 1024) return MLAGG_E_UNSUPPORTED;
     if (lds > 48 * 1024)
         if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_taps_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
             return (int)e;
-    const long nwg = (g.Q + WG_VOX - 1) / WG_VOX;
-    if (nwg > 2147483647L || (O + 31) / 32 > 65535) return MLAGG_E_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     MLAGG_TIMED(K_CONV_TAPS, st);
     hipLaunchKernelGGL(conv_taps_kernel, dim3((unsigned)nwg, (O + 31) / 32, B), dim3(256), lds, st, xp, weight, y, g);

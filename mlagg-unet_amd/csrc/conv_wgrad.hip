@@ -252,12 +252,35 @@ static int slab_len(long Q, long waves_per_slab)
     return slab;
 }
 
+// the sizes mlagg_conv_wgrad_taps launches with: tap groups, channel tiles, slab, nslabs (the launcher, the workspace size and
+// mlagg_conv_wgrad_taps_geometry all ask here)
+static int make_tapgeom(TapGeom &g, int batch, long Q, int O, int I, int ntaps)
+{
+    if (ntaps <= 0 || ntaps > MAXTAPS || Q <= 0 || (Q & 7) || O <= 0 || I <= 0 || batch <= 0 || batch > 65535) return MLAGG_E_UNSUPPORTED;
+    g.O = O; g.I = I; g.ntaps = ntaps; g.ngroups = (ntaps + NT - 1) / NT;
+    g.otiles = (O + 31) / 32; g.itiles = (I + 31) / 32;
+    g.Q = Q;
+    const long tiles = (long)g.otiles * g.itiles * g.ngroups;
+    if (tiles > 65535) return MLAGG_E_UNSUPPORTED;
+    g.slab = slab_len(Q, tiles * batch);
+    g.nslabs = (int)((Q + g.slab - 1) / g.slab);
+    return 0;
+}
+
 extern "C" size_t mlagg_conv_wgrad_taps_workspace_floats(int batch, long Q, int O, int I, int ntaps)
 {
-    if (batch <= 0 || Q <= 0 || O <= 0 || I <= 0 || ntaps <= 0) return 0;
-    const long tiles = (long)((O + 31) / 32) * ((I + 31) / 32) * ((ntaps + NT - 1) / NT);
-    const int slab = slab_len(Q, tiles * batch);
-    return (size_t)batch * ((Q + slab - 1) / slab) * (size_t)ntaps * O * I;
+    TapGeom g;
+    if (make_tapgeom(g, batch, Q, O, I, ntaps)) return 0;                   // sizes the launch refuses
+    return (size_t)batch * g.nslabs * (size_t)ntaps * O * I;
+}
+
+extern "C" int mlagg_conv_wgrad_taps_geometry(int batch, long Q, int O, int I, int ntaps, int *out5)
+{
+    if (!out5) return MLAGG_E_NULLPTR;
+    TapGeom g;
+    if (int rc = make_tapgeom(g, batch, Q, O, I, ntaps)) return rc;
+    out5[0] = g.slab; out5[1] = g.nslabs; out5[2] = g.ngroups; out5[3] = g.otiles; out5[4] = g.itiles;
+    return 0;
 }
 
 // dW (O, I, ntaps) (+)= sum over batch and q of A[b][o][q] * B[b][i][q + tap_off[t]]: rows of a_row / b_row floats, samples
@@ -268,17 +291,12 @@ extern "C" int mlagg_conv_wgrad_taps(const float *A, long a_batch, long a_row, c
                                      float *workspace, void *stream)
 {
     if (!A || !B || !tap_off || !dW || !workspace) return MLAGG_E_NULLPTR;
-    if (ntaps <= 0 || ntaps > MAXTAPS || Q <= 0 || (Q & 7) || O <= 0 || I <= 0 || batch <= 0 || batch > 65535) return MLAGG_E_UNSUPPORTED;
     if ((a_row & 3) || (a_batch & 3) || (((uintptr_t)A) & 15)) return MLAGG_E_UNSUPPORTED;
     TapGeom g;
-    g.O = O; g.I = I; g.ntaps = ntaps; g.ngroups = (ntaps + NT - 1) / NT;
-    g.otiles = (O + 31) / 32; g.itiles = (I + 31) / 32;
-    g.Q = Q; g.a_row = a_row; g.a_batch = a_batch; g.b_row = b_row; g.b_batch = b_batch;
+    if (int rc = make_tapgeom(g, batch, Q, O, I, ntaps)) return rc;
+    g.a_row = a_row; g.a_batch = a_batch; g.b_row = b_row; g.b_batch = b_batch;
     for (int t = 0; t < MAXTAPS; ++t) g.off[t] = tap_off[t < ntaps ? t : 0];
     const long tiles = (long)g.otiles * g.itiles * g.ngroups;
-    if (tiles > 65535) return MLAGG_E_UNSUPPORTED;
-    g.slab = slab_len(Q, tiles * batch);
-    g.nslabs = (int)((Q + g.slab - 1) / g.slab);
     hipStream_t st = static_cast<hipStream_t>(stream);
     {
         MLAGG_TIMED(K_CONV_WGRAD, st);
