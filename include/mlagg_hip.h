@@ -584,6 +584,46 @@ int mlagg_dice_ce_grad(const float *logits, const float *target, const float *g_
                        int C, long HW, int ignore_label, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K33: top-k cross-entropy of one deep-supervision level -- TopKLoss (loss/robust_ce_loss.py:19-32: the mean of the k largest
+ * per-pixel cross-entropies, k = int(N kpercent / 100) of the N = B HW pixels, ignored ones counted) alone or, with the Dice
+ * statistics of K9 from the same pass, DC_and_topk_loss (loss/compound_losses.py:103-151) -- the losses of the reference's
+ * nnUNetTrainerTopk10Loss, nnUNetTrainerTopk10LossLS01 and nnUNetTrainerDiceTopK10Loss (variants/loss/nnUNetTrainerTopkLoss.py).
+ * Replaces log_softmax + nll, the device-wide torch.topk, the mean and their backward kernels.  Tensors and layout as K9's.
+ *
+ * stats:  one pass over the logits.  ce_pix (B HW) receives CrossEntropyLoss(reduction='none', ignore_index, label_smoothing) per pixel:
+ *         (1 - e)(lse - z_y) + (e / C) sum_c (lse - z_c), exactly 0.0f where the pixel carries ignore_label.  stats_ip, stats_g, ce_sum
+ *         and workspace (mlagg_dice_ce_stats_workspace_floats floats) are K9's, with K9's ignore semantics and fixed-order partial rows
+ *         (ce_sum is the plain, unsmoothed sum); all four NULL (the pure top-k trainers): the Dice work is skipped.
+ * select: the exact k-th largest value t of ce_pix (n = B HW values, 1 <= k <= n; the host refuses k = 0, where the reference
+ *         returns NaN) by a radix select on an order-preserving integer image of the floats (-0 and +0 are one key): per digit one
+ *         histogram launch (integer atomics, LDS then global: independent of the order of arrival) and one single-workgroup launch
+ *         that picks the bin; then the values above t are summed as one double per workgroup, added in a fixed order.  record
+ *         (mlagg_topk_ce_record_floats() = 8 four-byte words, 8-byte aligned) receives
+ *             float t | float share = (k - n_gt) / n_eq | float topk_sum = sum_{ce > t} ce + (k - n_gt) t | float topk_sum / k |
+ *             int64 n_gt = #{ce > t} | int64 n_eq = #{ce == t}.
+ *         workspace: mlagg_topk_ce_select_workspace_bytes(n) bytes, 8-byte aligned.  No workgroup waits on another one, no float
+ *         atomics, nothing is read back: bit-reproducible and capturable.
+ * grad:   dlogits = p_k (g_k - sum_c p_c g_c)  [K9's Dice term, g_c = gI[b][c] [y == c] + gP[b][c]; left out when g_ip is NULL]
+ *                   + g_topk[0] w_p / k ((1 - e)(p_k - [y == k]) + e (p_k - 1 / C)),
+ *         w_p = 1 where ce_pix > t, share where ce_pix == t, 0 below; ignored pixels get 0.  g_ip, g_topk: device tensors as in
+ *         mlagg_dice_ce_grad (g_topk is the upstream gradient of topk_sum / k).
+ * Ties at the threshold share the weight that remains, k - n_gt, equally: a valid subgradient of the sum of the k largest values,
+ * free of any order and the same in every run.  torch.topk's choice among equal values is unspecified and differs between its own
+ * back ends, so gradients of tied pixels may differ from a torch run; the value does not.
+ * MLAGG_E_NULLPTR for a missing pointer, MLAGG_E_UNSUPPORTED for C outside 2 .. mlagg_dice_ce_max_classes(), k outside 1 .. n or a
+ * label smoothing outside [0, 1].
+ * ------------------------------------------------------------------------------------------ */
+int mlagg_topk_ce_record_floats(void);
+int mlagg_topk_ce_select_elements_per_workgroup(void);
+size_t mlagg_topk_ce_select_workspace_bytes(long n);
+int mlagg_topk_ce_stats(const float *logits, const float *target, float *stats_ip, float *stats_g, float *ce_sum, float *ce_pix,
+                        float *workspace, int B, int C, long HW, int ignore_label, float label_smoothing, void *stream);
+int mlagg_topk_ce_select(const float *ce_pix, float *record, void *workspace, long n, long k, void *stream);
+int mlagg_topk_ce_grad(const float *logits, const float *target, const float *ce_pix, const float *record, const float *g_ip,
+                       const float *g_topk, float *dlogits, int B, int C, long HW, long k, int ignore_label, float label_smoothing,
+                       void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K10: per-plane normalisation of an NCHW map fused with the activation that follows it:
  *   y = act((x - mean_bc) * rstd_bc * gamma_c + beta_c),  statistics over the HW pixels of each (batch, channel) plane.
  * gamma / beta (C) may be NULL (1 / 0).  act: 0 none, 1 LeakyReLU(slope), 2 SiLU.  res (B, C, HW) or NULL is added before the

@@ -20,6 +20,8 @@ What the class overrides, and why the inherited method cannot stay (B = nnUNetTr
                     all-reduce; the ignore label of partially annotated datasets is handled in K9; region datasets
                     (sigmoid heads, B:330-336) get the fused Dice + BCE loss (K29) on the region planes nnU-Net delivers; a
                     label manager that says ``has_regions`` without naming its ``foreground_regions`` keeps the reference's classes.
+                    ``loss=`` of the factories selects one of the reference's loss-variant trainers instead (variants/loss/:
+                    top-k cross-entropy on K33, Dice only, CE only, smooth 0): ``trainer.loss_variant_deep_supervision_loss``.
 """
 import os
 
@@ -58,9 +60,42 @@ def _region_loss(batch_dice, ddp, ignore_label):
     return loss
 
 
-def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32"):
+DEFAULT_LOSS = "dice_ce"
+
+
+def _check_loss(loss):
+    if loss != DEFAULT_LOSS and loss not in trainer.LOSS_VARIANTS:
+        raise RuntimeError(f"loss {loss!r}: {DEFAULT_LOSS!r} or one of {tuple(trainer.LOSS_VARIANTS)}")
+
+
+def _variant_loss(variant, label_manager, batch_dice, ddp, ignore_label):
+    """The loss of one of the reference's loss-variant trainers (variants/loss/nnUNetTrainer{TopkLoss,DiceLoss,CELoss}.py) as
+    ``trainer.loss_variant_deep_supervision_loss``.  Region-based label managers: "dice" and "dice_ce_nosmooth" take the fused K29
+    loss on the region planes; the top-k and cross-entropy trainers refuse them with the reference's message."""
+    regions = bool(getattr(label_manager, "has_regions", False))
+    if regions and variant not in ("dice", "dice_ce_nosmooth"):
+        raise RuntimeError(trainer.REGIONS_REFUSED)
+    if regions and not _describes_regions(label_manager):
+        raise RuntimeError(f"loss {variant!r}: the label manager says has_regions without naming its foreground_regions")
+
+    def loss(output, target):
+        if not isinstance(output, (list, tuple)):                                   # deep supervision off
+            output, target = [output], [target if torch.is_tensor(target) else target[0]]
+        return trainer.loss_variant_deep_supervision_loss(list(output), list(target[:len(output)]), variant, batch_dice, ddp,
+                                                          ignore_label, regions=regions)
+
+    return loss
+
+
+def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAULT_LOSS):
+    """loss: "dice_ce" (the reference trainer's DC_and_CE_loss / DC_and_BCE_loss) or one of ``trainer.LOSS_VARIANTS`` -- the loss of
+    the reference's nnUNetTrainerTopk10Loss ("topk10"), ...Topk10LossLS01 ("topk10_ls01"), ...DiceTopK10Loss ("dice_topk10"),
+    ...DiceLoss ("dice"), ...CELoss ("ce") or ...DiceCELoss_noSmooth ("dice_ce_nosmooth").  Every one of them is device-fused, so the
+    step is replayed as a hipGraph with any of them; the choice is kept in ``mlagg_loss_variant``."""
     if precision not in PRECISIONS:
         raise RuntimeError(f"precision {precision!r}: this build of the MI355X path offers {PRECISIONS}")
+    _check_loss(loss)
+    loss_variant = loss
 
     class nnUNetTrainer_MLAgg_2D_dt_MS(nnUNetTrainer):
         def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=None):
@@ -79,6 +114,7 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32"):
             if precision != "fp16":
                 self.grad_scaler = None
             self.mlagg_precision = precision
+            self.mlagg_loss_variant = loss_variant                                  # for logs and checkpoints
             self._graphed, self._graph_key, self._graph_eager, self._graph_failed = None, None, 0, None
             # run_training.py:123-125 sets cudnn.benchmark (MIOpen's exhaustive find); here: the committed find-db, which
             # holds the fp32 convolutions of the 256 x 256 step only.  Any other patch size or precision takes MIOpen's
@@ -116,6 +152,8 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32"):
             lm = self.label_manager
             batch_dice, ddp = bool(self.configuration_manager.batch_dice), bool(self.is_ddp)
             ignore = getattr(lm, "ignore_label", None)                              # T:116: partially annotated datasets
+            if loss_variant != DEFAULT_LOSS:
+                return _variant_loss(loss_variant, lm, batch_dice, ddp, ignore)
             if getattr(lm, "has_regions", False):                                   # DC_and_BCE_loss on region planes (T:107-112)
                 return _region_loss(batch_dice, ddp, ignore) if _describes_regions(lm) else super()._build_loss()
 
@@ -191,19 +229,23 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32"):
     return nnUNetTrainer_MLAgg_2D_dt_MS
 
 
-def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer):
+def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS):
     """``nnUNetTrainerUMambaEnc_SS3D`` (reference variants/mamba/nnUNetTrainerUMambaEnc_SS3D.py:8-31) on the MI355X 3-D network
     (model3d.UMambaEnc; BASELINE configs[3]).  The reference class overrides ``build_network_architecture`` only and inherits the
     base trainer's recipe (SGD momentum 0.99 Nesterov + PolyLR, nnUNetTrainer.py:448-452; DC_and_CE deep-supervision loss,
     :330-352); so does this one, plus what the device network needs from the loop: the fp32 step without autocast / GradScaler
-    (B:848-858), the fused K9 loss, ``trainer.wrap_ddp``, and the deep-supervision switch on the unwrapped module."""
+    (B:848-858), the fused K9 loss, ``trainer.wrap_ddp``, and the deep-supervision switch on the unwrapped module.
+    loss: as in ``make_trainer_class``."""
     from . import model3d
+    _check_loss(loss)
+    loss_variant = loss
 
     class nnUNetTrainerUMambaEnc_SS3D(nnUNetTrainer):
         def __init__(self, plans, configuration, fold, dataset_json, unpack_dataset=True, device=None):
             super().__init__(plans, configuration, fold, dataset_json, unpack_dataset,
                              device if device is not None else torch.device("cuda"))
             self.grad_scaler = None                                                  # fp32 step: no loss scaling (B:152)
+            self.mlagg_loss_variant = loss_variant                                   # for logs and checkpoints
             miopen_tuning.use_tuned_convolutions(enabled=False)                      # no committed records for 3-D convolutions
 
         @staticmethod
@@ -236,6 +278,8 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer):
             lm = self.label_manager
             batch_dice, ddp = bool(self.configuration_manager.batch_dice), bool(self.is_ddp)
             ignore = getattr(lm, "ignore_label", None)
+            if loss_variant != DEFAULT_LOSS:
+                return _variant_loss(loss_variant, lm, batch_dice, ddp, ignore)
             if getattr(lm, "has_regions", False):
                 return _region_loss(batch_dice, ddp, ignore) if _describes_regions(lm) else super()._build_loss()
 

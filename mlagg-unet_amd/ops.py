@@ -1754,6 +1754,101 @@ def dice_ce_stats(logits, targets, ignore_label=None):
     return DiceCEStatsFn.apply(len(logits), -1 if ignore_label is None else int(ignore_label), *logits, *targets)
 
 
+_TOPK_WORKSPACES = {}
+TOPK_RECORD_WORDS = 8              # mlagg_topk_ce_record_floats: t, share, topk_sum, topk_sum / k, int64 n_gt, int64 n_eq
+
+
+def topk_count(n, kpercent):
+    """k of TopKLoss.forward (reference loss/robust_ce_loss.py:30-31): ``int(num_voxels * k / 100)`` in Python float arithmetic, with
+    every pixel counted, ignored ones too.  k == 0 is refused: the reference takes the mean of an empty tensor there and returns NaN."""
+    k = int(n * kpercent / 100)
+    if k <= 0:
+        raise RuntimeError(f"top-k loss: {kpercent} % of {n} pixels is less than one pixel (the reference returns NaN here)")
+    return k
+
+
+class TopKCEStatsFn(torch.autograd.Function):
+    """K33: per-level top-k cross-entropy of ALL deep-supervision levels, with K9's Dice statistics from the same pass over the logits.
+
+    ``TopKCEStatsFn.apply(n_levels, ignore_label, label_smoothing, kpercent, with_dice, *logits, *targets)`` -> (ip (L, B, 2, C), gt
+    (L, B, C): K9's statistics, or None, None without Dice; rec (L, 8): the select's record per level -- [:, 0] the threshold t, [:, 1]
+    the share of a pixel that ties with it, [:, 2] the sum of the k largest per-pixel cross-entropies, [:, 3] that sum / k, i.e.
+    TopKLoss, and [:, 4:8].view(torch.int64) the counts n_gt, n_eq).  Gradients flow to the logits from ip and rec[:, 3] only.
+    Per level: the statistics pass, the select (9 small launches) and, backward, one gradient pass; every launch is on the current
+    stream, the select's workspace is cached per size and device, nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, n, ignore_label, label_smoothing, kpercent, with_dice, *tensors):
+        logits, targets = tensors[:n], tensors[n:]
+        ctx.ignore, ctx.eps, ctx.with_dice = int(ignore_label), float(label_smoothing), bool(with_dice)
+        B, C = logits[0].shape[:2]
+        dev = logits[0].device
+        lib = _lib.lib()
+        if not 2 <= C <= lib.mlagg_dice_ce_max_classes():
+            raise RuntimeError(f"topk_ce_stats: {C} classes, 2 to {lib.mlagg_dice_ce_max_classes()} are supported")
+        W = TOPK_RECORD_WORDS
+        npix = [z.numel() // C for z in logits]
+        ks = [topk_count(m, kpercent) for m in npix]
+        # [records | ip | gt | ce]: the records first, their int64 counts need 8-byte alignment; every entry is written by the kernels
+        buf = torch.empty(n * W + (n * B * 3 * C + n if with_dice else 0), device=dev, dtype=torch.float32)
+        rec = buf[:n * W].view(n, W)
+        ip = gt = ce = None
+        if with_dice:
+            ip = buf[n * W:n * W + n * B * 2 * C].view(n, B, 2, C)
+            gt = buf[n * W + n * B * 2 * C:n * W + n * B * 3 * C].view(n, B, C)
+            ce = buf[n * W + n * B * 3 * C:]
+        ce_pix = torch.empty(sum(npix), device=dev, dtype=torch.float32)
+        saved, at = [], 0
+        for i, (z, t) in enumerate(zip(logits, targets)):
+            z = _require(z.contiguous(), "logits")
+            t = _require(t.contiguous(), "target")
+            if z.shape[:2] != (B, C) or t.numel() * C != z.numel():
+                raise RuntimeError("topk_ce_stats: logits / target shapes of a level do not match")
+            hw, cp = npix[i] // B, ce_pix[at:at + npix[i]]
+            at += npix[i]
+            key = (npix[i], str(dev))
+            ws = _TOPK_WORKSPACES.get(key)
+            if ws is None:
+                ws = _TOPK_WORKSPACES[key] = torch.empty(lib.mlagg_topk_ce_select_workspace_bytes(npix[i]) // 8, device=dev,
+                                                         dtype=torch.int64)
+            part = torch.empty(lib.mlagg_dice_ce_stats_workspace_floats(B, C, hw), device=dev, dtype=torch.float32) if with_dice else None
+            _launch("mlagg_topk_ce_stats", _ptr(z), _ptr(t), _ptr(ip[i]) if with_dice else None, _ptr(gt[i]) if with_dice else None,
+                    ce.data_ptr() + 4 * i if with_dice else None, _ptr(cp), _ptr(part), B, C, hw, ctx.ignore, ctx.eps)
+            _launch("mlagg_topk_ce_select", _ptr(cp), _ptr(rec[i]), _ptr(ws), npix[i], ks[i])
+            saved += [z, t]
+        ctx.save_for_backward(ce_pix, rec, *saved)
+        ctx.n, ctx.npix, ctx.ks = n, npix, ks
+        if with_dice:
+            ctx.mark_non_differentiable(gt)
+        return ip, gt, rec
+
+    @staticmethod
+    def backward(ctx, g_ip, g_gt, g_rec):
+        n, W = ctx.n, TOPK_RECORD_WORDS
+        ce_pix, rec, *saved = ctx.saved_tensors
+        B, C = saved[0].shape[:2]
+        dev = saved[0].device
+        if ctx.with_dice:
+            g_ip = torch.zeros(n, B, 2, C, device=dev) if g_ip is None else _require(g_ip.contiguous(), "g_ip")
+        g_rec = torch.zeros(n, W, device=dev) if g_rec is None else _require(g_rec.contiguous(), "g_rec")
+        grads, at = [], 0
+        for i in range(n):
+            z, t = saved[2 * i], saved[2 * i + 1]
+            dz = torch.empty_like(z)
+            _launch("mlagg_topk_ce_grad", _ptr(z), _ptr(t), ce_pix.data_ptr() + 4 * at, _ptr(rec[i]),
+                    _ptr(g_ip[i]) if ctx.with_dice else None, g_rec.data_ptr() + 4 * (W * i + 3), _ptr(dz), B, C, ctx.npix[i] // B,
+                    ctx.ks[i], ctx.ignore, ctx.eps)
+            at += ctx.npix[i]
+            grads.append(dz)
+        return (None, None, None, None, None, *grads, *([None] * n))
+
+
+def topk_ce_stats(logits, targets, ignore_label=None, label_smoothing=0.0, kpercent=10, with_dice=False):
+    """K33 over all levels in one apply: see TopKCEStatsFn."""
+    return TopKCEStatsFn.apply(len(logits), -1 if ignore_label is None else int(ignore_label), float(label_smoothing), kpercent,
+                               bool(with_dice), *logits, *targets)
+
+
 _REGION_TABLES = {}
 _REGION_WORKSPACES = {}
 REGION_LOSS_MAX_REGIONS = 16       # heads held in registers by K29 (mlagg_dice_bce_max_regions)

@@ -9,6 +9,8 @@ Mirrors the reference's trainer surface on the hot path:
                               (loss/compound_losses.py:31-57, loss/dice.py:73-117, loss/robust_ce_loss.py:12-16)
   * ``region_deep_supervision_loss``  the same wrapper over DC_and_BCE_loss (loss/compound_losses.py:60-100), the loss of
                               region-based datasets with sigmoid heads (nnUNetTrainer.py:330-336)
+  * ``loss_variant_deep_supervision_loss``  the wrapper over the losses of the loss-variant trainers (variants/loss/: TopKLoss,
+                              DC_and_topk_loss, Dice alone, cross-entropy alone, Dice + CE with smooth 0)
   * ``wrap_ddp``              reference nnUNetTrainer.py:205-207, without its ``dummy_tensor`` hazard
   * ``split_batch_size``      reference nnUNetTrainer.py:283-328 with the zero/negative per-rank sizes fixed (7c)
 One process per GPU; ``torch.distributed`` backend "nccl" is RCCL on ROCm (xGMI inside a node).
@@ -135,6 +137,125 @@ def deep_supervision_loss(outputs, targets, batch_dice=True, ddp=False, smooth=1
 
 
 # ------------------------------------------------------------------------------------------------
+# loss variants (reference training/nnUNetTrainer/variants/loss)
+# ------------------------------------------------------------------------------------------------
+# variant -> (top-k percent or None, label smoothing, Dice term, cross-entropy term, Dice smooth)
+LOSS_VARIANTS = {
+    "topk10": (10, 0.0, False, False, None),              # nnUNetTrainerTopk10Loss: TopKLoss(k=10)
+    "topk10_ls01": (10, 0.1, False, False, None),         # nnUNetTrainerTopk10LossLS01: TopKLoss(k=10, label_smoothing=0.1)
+    "dice_topk10": (10, 0.0, True, False, 1e-5),          # nnUNetTrainerDiceTopK10Loss: DC_and_topk_loss, SoftDiceLoss, weights 1 / 1
+    "dice": (None, 0.0, True, False, 1e-5),               # nnUNetTrainerDiceLoss: MemoryEfficientSoftDiceLoss alone
+    "ce": (None, 0.0, False, True, None),                 # nnUNetTrainerCELoss: RobustCrossEntropyLoss
+    "dice_ce_nosmooth": (None, 0.0, True, True, 0.0),     # nnUNetTrainerDiceCELoss_noSmooth: DC_and_CE_loss with smooth 0
+}
+REGIONS_REFUSED = "regions not supported by this trainer"        # the reference's assertion message (nnUNetTrainerTopkLoss.py:10)
+
+
+def _loss_variant(variant):
+    if variant not in LOSS_VARIANTS:
+        raise RuntimeError(f"loss variant {variant!r}: one of {tuple(LOSS_VARIANTS)}")
+    return LOSS_VARIANTS[variant]
+
+
+def topk_loss(logits, target, kpercent=10, ignore_label=None, label_smoothing=0.0):
+    """TopKLoss.forward (loss/robust_ce_loss.py:27-32) in torch ops, one level: the mean of the k largest per-pixel cross-entropies,
+    k = int(N kpercent / 100) of ALL N pixels; ignored pixels have the value 0.  k == 0 raises (the reference returns NaN)."""
+    from . import ops
+    ce = F.cross_entropy(logits, target[:, 0].long(), reduction="none", ignore_index=-100 if ignore_label is None else int(ignore_label),
+                         label_smoothing=label_smoothing)
+    return torch.topk(ce.reshape(-1), ops.topk_count(ce.numel(), kpercent), sorted=False)[0].mean()
+
+
+def loss_variant_level_eager(logits, target, variant, batch_dice=True, ddp=False, ignore_label=None):
+    """One level of a loss variant as the reference composes it, in torch ops."""
+    kpercent, eps, with_dice, with_ce, smooth = _loss_variant(variant)
+    if variant == "dice":                                   # nnUNetTrainerDiceLoss passes no loss mask: the ignore label plays no part
+        return soft_dice_loss(logits, target, batch_dice, smooth, ddp)
+    total = None
+    if with_dice:                                           # the ignore branch of DC_and_CE_loss / DC_and_topk_loss (compound_losses.py:38-50)
+        if ignore_label is None:
+            total = soft_dice_loss(logits, target, batch_dice, smooth, ddp)
+        else:
+            mask = target != ignore_label
+            total = soft_dice_loss(logits, torch.where(mask, target, torch.zeros_like(target)), batch_dice, smooth, ddp, mask)
+    if ignore_label is not None and int((target != ignore_label).sum()) == 0:
+        # nothing to classify: DC_and_CE_loss / DC_and_topk_loss skip the term (`num_fg > 0`); so do the pure variants here, where
+        # the reference's CrossEntropyLoss gives NaN (mean over no pixel) and its TopKLoss 0
+        return total if total is not None else logits.sum() * 0.0
+    if kpercent is not None:
+        term = topk_loss(logits, target, kpercent, ignore_label, eps)
+    else:
+        term = F.cross_entropy(logits, target[:, 0].long(), ignore_index=-100 if ignore_label is None else int(ignore_label))
+    return term if total is None else term + total
+
+
+def loss_variant_deep_supervision_loss_eager(outputs, targets, variant, batch_dice=True, ddp=False, ignore_label=None):
+    """A loss variant under the DeepSupervisionWrapper, level by level in torch ops, ``torch.topk`` included (host tensors, CPU tests)."""
+    ws = deep_supervision_weights(len(outputs))
+    total = None
+    for w, o, t in zip(ws, outputs, targets):
+        level = w * loss_variant_level_eager(o, t, variant, batch_dice, ddp, ignore_label)
+        total = level if total is None else total + level
+    return total
+
+
+def _dice_levels(ip, gt, batch_dice, ddp, smooth):
+    """-mean dice per level (L,) from K9's statistics, background dropped; batch dice crosses the ranks in one all-reduce each way."""
+    inter, pred, gts = ip[:, :, 0, 1:], ip[:, :, 1, 1:], gt[:, :, 1:]
+    if batch_dice:
+        stats = torch.stack([inter.sum(1), pred.sum(1), gts.sum(1)])        # (3, L, C-1)
+        if ddp:
+            stats = _AllGatherSum.apply(stats)
+        inter, pred, gts = stats[0], stats[1], stats[2]
+    dc = (2 * inter + smooth) / torch.clip(gts + pred + smooth, 1e-8)
+    return -dc.flatten(1).mean(1)
+
+
+def loss_variant_deep_supervision_loss(outputs, targets, variant, batch_dice=True, ddp=False, ignore_label=None, regions=False):
+    """The losses of the reference's loss-variant trainers (variants/loss/nnUNetTrainer{TopkLoss,DiceLoss,CELoss}.py) under the
+    DeepSupervisionWrapper, weights ``deep_supervision_weights``.  variant:
+      "topk10"            nnUNetTrainerTopk10Loss          TopKLoss(k=10): mean of the 10 % largest per-pixel cross-entropies
+      "topk10_ls01"       nnUNetTrainerTopk10LossLS01      ... with label smoothing 0.1
+      "dice_topk10"       nnUNetTrainerDiceTopK10Loss      DC_and_topk_loss: SoftDiceLoss (do_bg False, smooth 1e-5) + TopKLoss, weights 1 / 1;
+                                                           the Dice statistics cross the ranks, the top-k is local to the rank
+      "dice"              nnUNetTrainerDiceLoss            MemoryEfficientSoftDiceLoss alone (no loss mask: ignore_label plays no part)
+      "ce"                nnUNetTrainerCELoss              RobustCrossEntropyLoss
+      "dice_ce_nosmooth"  nnUNetTrainerDiceCELoss_noSmooth DC_and_CE_loss with smooth 0
+    On the MI355X the top-k variants run K33 (per level one pass for the per-pixel values and the Dice statistics, an exact radix
+    select of the k-th largest value, one gradient pass); the others are K9's statistics plus algebra.  All of them are device-fused
+    and record into a hipGraph.  k = int(N 10 / 100) counts ignored pixels, as the reference does; k == 0 raises where the reference
+    returns NaN; pixels that tie with the k-th value share the remaining weight equally (``torch.topk`` picks among them in an
+    unspecified order: the value is the same, the gradient of the tied pixels may differ).  A level without a valid pixel contributes
+    no cross-entropy term.  CPU tensors take ``loss_variant_deep_supervision_loss_eager``.
+    regions: False for label datasets.  For region-based datasets (sigmoid heads) True when the targets are region planes, or the label
+    manager's ``foreground_regions`` when they are label maps: "dice" and "dice_ce_nosmooth" then go through
+    ``region_deep_supervision_loss``; the other variants refuse regions as the reference's trainers do."""
+    kpercent, eps, with_dice, with_ce, smooth = _loss_variant(variant)
+    if regions is not False and regions is not None:
+        if variant not in ("dice", "dice_ce_nosmooth"):
+            raise RuntimeError(REGIONS_REFUSED)
+        return region_deep_supervision_loss(outputs, targets, None if regions is True else regions, batch_dice, ddp, smooth, ignore_label,
+                                            weight_ce=1.0 if with_ce else 0.0)
+    if not outputs[0].is_cuda:
+        return loss_variant_deep_supervision_loss_eager(outputs, targets, variant, batch_dice, ddp, ignore_label)
+    if variant == "dice_ce_nosmooth":
+        return deep_supervision_loss(outputs, targets, batch_dice, ddp, smooth, ignore_label)
+    from . import ops
+    w_ce, w = _level_constants(tuple(o.numel() // o.shape[1] for o in outputs), outputs[0].device)
+    if kpercent is not None:
+        ip, gt, rec = ops.topk_ce_stats(list(outputs), list(targets), ignore_label, eps, kpercent, with_dice)
+        total = (w * rec[:, 3]).sum()                                           # (L,) TopKLoss per level
+        return total + (w * _dice_levels(ip, gt, batch_dice, ddp, smooth)).sum() if with_dice else total
+    if variant == "dice":
+        ip, gt, _ = ops.dice_ce_stats(list(outputs), list(targets), None)
+        return (w * _dice_levels(ip, gt, batch_dice, ddp, smooth)).sum()
+    _, gt, ce = ops.dice_ce_stats(list(outputs), list(targets), ignore_label)     # "ce"
+    if ignore_label is not None:
+        w_ce = w / gt.sum((1, 2)).clamp(min=1.0)                                # the mean over the valid pixels, as in deep_supervision_loss
+    return (w_ce * ce).sum()
+
+
+# ------------------------------------------------------------------------------------------------
 # loss of region-based datasets (sigmoid heads)
 # ------------------------------------------------------------------------------------------------
 def regions_from_label_map(target, regions, ignore_label=None):
@@ -149,10 +270,11 @@ def regions_from_label_map(target, regions, ignore_label=None):
     return torch.cat(planes, 1).to(target.dtype)
 
 
-def dc_and_bce_loss(logits, target, batch_dice=True, ddp=False, use_ignore_label=False, smooth=1e-5):
+def dc_and_bce_loss(logits, target, batch_dice=True, ddp=False, use_ignore_label=False, smooth=1e-5, weight_ce=1.0, weight_dice=1.0):
     """DC_and_BCE_loss.forward (loss/compound_losses.py:84-100) as nnUNetTrainer.py:330-336 builds it, in torch ops, one level:
     MemoryEfficientSoftDiceLoss(apply_nonlin=sigmoid, do_bg=True, smooth=1e-5) + BCEWithLogitsLoss.  target: region planes
-    (B, R, ...); with use_ignore_label the ignore plane follows them (B, R + 1, ...) and masks both terms."""
+    (B, R, ...); with use_ignore_label the ignore plane follows them (B, R + 1, ...) and masks both terms.  weight_ce / weight_dice:
+    the weights of DC_and_BCE_loss; (0, 1) is the Dice term alone, the loss of nnUNetTrainerDiceLoss for regions."""
     axes = tuple(range(2, logits.ndim))
     probs = torch.sigmoid(logits)
     if use_ignore_label:
@@ -174,25 +296,30 @@ def dc_and_bce_loss(logits, target, batch_dice=True, ddp=False, use_ignore_label
             stats = _AllGatherSum.apply(stats)
         intersect, sum_pred, sum_gt = stats[0], stats[1], stats[2]
     dc = -((2 * intersect + smooth) / torch.clip(sum_gt + sum_pred + smooth, 1e-8)).mean()
+    if weight_ce == 0:
+        return weight_dice * dc
     if mask is None:
-        return F.binary_cross_entropy_with_logits(logits, target) + dc
-    bce = (F.binary_cross_entropy_with_logits(logits, target, reduction="none") * mask).sum() / torch.clip(mask.sum(), min=1e-8)
-    return bce + dc
+        bce = F.binary_cross_entropy_with_logits(logits, target)
+    else:
+        bce = (F.binary_cross_entropy_with_logits(logits, target, reduction="none") * mask).sum() / torch.clip(mask.sum(), min=1e-8)
+    return bce + dc if weight_ce == 1 and weight_dice == 1 else weight_ce * bce + weight_dice * dc
 
 
-def region_deep_supervision_loss_eager(outputs, targets, regions=None, batch_dice=True, ddp=False, smooth=1e-5, ignore_label=None):
+def region_deep_supervision_loss_eager(outputs, targets, regions=None, batch_dice=True, ddp=False, smooth=1e-5, ignore_label=None,
+                                       weight_ce=1.0, weight_dice=1.0):
     """The region loss as the reference composes it, level by level in torch ops (host tensors, CPU tests, more than 16 heads)."""
     if regions is not None:
         targets = [regions_from_label_map(t, regions, ignore_label) for t in targets]
     ws = deep_supervision_weights(len(outputs))
     total = None
     for w, o, t in zip(ws, outputs, targets):
-        level = w * dc_and_bce_loss(o, t, batch_dice, ddp, ignore_label is not None, smooth)
+        level = w * dc_and_bce_loss(o, t, batch_dice, ddp, ignore_label is not None, smooth, weight_ce, weight_dice)
         total = level if total is None else total + level
     return total
 
 
-def region_deep_supervision_loss(outputs, targets, regions=None, batch_dice=True, ddp=False, smooth=1e-5, ignore_label=None):
+def region_deep_supervision_loss(outputs, targets, regions=None, batch_dice=True, ddp=False, smooth=1e-5, ignore_label=None,
+                                 weight_ce=1.0, weight_dice=1.0):
     """DeepSupervisionWrapper(DC_and_BCE_loss) of reference nnUNetTrainer.py:330-352, the loss of region-based datasets.
     regions: the label manager's ``foreground_regions`` -- the targets are then LABEL MAPS (B, 1, ...) and ``ignore_label`` is the label
     value that masks a pixel; None: the targets are REGION PLANES (B, R, ...) as ConvertSegmentationToRegionsTransform delivers them,
@@ -201,10 +328,12 @@ def region_deep_supervision_loss(outputs, targets, regions=None, batch_dice=True
     below is torch, vectorised over the levels, and the batch-dice statistics of all levels cross the ranks in ONE all-reduce each way.
     Dice keeps all R heads (do_bg=True).  Without an ignore label the cross-entropy is the mean over B R HW elements; with one it is
     the masked sum over clip(mask sum, 1e-8) -- the mask sum has no factor R and is local to the rank (compound_losses.py:96) -- so a
-    fully ignored level gives 0 there and -1 from the dice.  CPU tensors, and more than 16 heads, take the eager composition."""
+    fully ignored level gives 0 there and -1 from the dice.  CPU tensors, and more than 16 heads, take the eager composition.
+    weight_ce / weight_dice: the weights of DC_and_BCE_loss (1 / 1 as the trainer builds it; 0 / 1 with smooth 1e-5 is the Dice-only
+    loss of nnUNetTrainerDiceLoss, 1 / 1 with smooth 0 the loss of nnUNetTrainerDiceCELoss_noSmooth)."""
     from . import ops
     if not outputs[0].is_cuda or outputs[0].shape[1] > ops.REGION_LOSS_MAX_REGIONS:
-        return region_deep_supervision_loss_eager(outputs, targets, regions, batch_dice, ddp, smooth, ignore_label)
+        return region_deep_supervision_loss_eager(outputs, targets, regions, batch_dice, ddp, smooth, ignore_label, weight_ce, weight_dice)
     member = None if regions is None else ops.region_member_table(regions, outputs[0].device)
     ip, gt, sums = ops.dice_bce_stats(list(outputs), list(targets), member, ignore_label)     # (L, B, 2, R), (L, B, R), (L, 2)
     inter, pred = ip[:, :, 0], ip[:, :, 1]
@@ -218,7 +347,11 @@ def region_deep_supervision_loss(outputs, targets, regions=None, batch_dice=True
     w_bce, w_dice = _level_constants(tuple(o.numel() for o in outputs), sums.device)      # BCE mean over B * R * HW elements
     if ignore_label is not None:
         w_bce = w_dice / sums[:, 1].clamp(min=1e-8)
-    return (w_bce * sums[:, 0] + w_dice * dice).sum()
+    if weight_ce == 1 and weight_dice == 1:
+        return (w_bce * sums[:, 0] + w_dice * dice).sum()
+    if weight_ce == 0:
+        return weight_dice * (w_dice * dice).sum()
+    return (weight_ce * (w_bce * sums[:, 0]) + weight_dice * (w_dice * dice)).sum()
 
 
 # ------------------------------------------------------------------------------------------------
