@@ -752,6 +752,36 @@ int mlagg_adamw_clip_step_dev(const void *tensor_table, const void *work_list, i
                               int *step_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K34: clip_grad_norm_ + the step of the OTHER optimizers of the reference's trainers, for every parameter in two launches (three
+ * with the norm's fixed-order reduce).  Replaces clip_grad_norm_(parameters, 12) + optimizer.step() (nnUNetTrainer.py:855-857) with
+ *   MLAGG_OPT_SGD_NESTEROV   torch.optim.SGD(momentum, nesterov=True, dampening 0, L2 weight decay): the base trainer's optimizer
+ *                            (nnUNetTrainer.py:448-452).  g = coef g + wd p; buf = momentum buf + g; p -= lr (g + momentum buf); a
+ *                            zero buffer gives torch's first step (buf = g).  beta1 carries the momentum; beta2, eps, step unused.
+ *   MLAGG_OPT_ADAMW_AMSGRAD  torch.optim.AdamW(amsgrad=True) of nnUNetTrainerAdam (variants/optimizer/nnUNetTrainerAdam.py):
+ *                            decoupled decay, moments and double-precision bias corrections as K11; vmax = max(vmax, v);
+ *                            denom = sqrt(vmax) / sqrt(bias_c2) + eps.
+ *   MLAGG_OPT_ADAM_L2        torch.optim.Adam of nnUNetTrainerVanillaAdam: g = coef g + wd p before the moments, no decoupled decay.
+ * tensor_table, work_list, sumsq, max_norm: K11's, with the SAME 5 x 8-byte rows {param*, grad*, state0*, state1*, int64 numel}:
+ * state0 is momentum_buffer (SGD) or exp_avg, state1 exp_avg_sq (not read by SGD: may be null).  extra_table: device array of one
+ * pointer per table row, the third state tensor max_exp_avg_sq of ADAMW_AMSGRAD; not read by the other kinds (may be null).  The
+ * float4 path is taken by a work item whose param, grad and state pointers (those its kind has) are all 16-byte aligned.
+ * beta1, beta2 are doubles: the bias corrections 1 - beta^step are formed from them in double, as torch does (K11 forms them from the
+ * float values; beta2 = 0.999 rounded to float is 1.3e-8 off, its 1000th power 1.3e-5, which a learning rate of 1e-2 carries into the
+ * parameters); the moment updates use beta and 1 - beta each rounded to float from the double, the weights torch hands to its kernels.
+ * The _dev form is for a hipGraph capture: lr_dev one device float, step_dev one device int32 advanced by the call for every kind
+ * (SGD does not read it: it counts the steps that replays have taken).
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_OPT_SGD_NESTEROV 0
+#define MLAGG_OPT_ADAMW_AMSGRAD 1
+#define MLAGG_OPT_ADAM_L2 2
+int mlagg_optimizer_clip_step(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
+                              double *sumsq, float lr, double beta1, double beta2, float eps, float weight_decay, float max_norm, int step,
+                              void *stream);
+int mlagg_optimizer_clip_step_dev(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
+                                  double *sumsq, const float *lr_dev, int *step_dev, double beta1, double beta2, float eps,
+                                  float weight_decay, float max_norm, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K20: 3-D sliding-window inference (reference nnunetv2/inference/sliding_window_prediction.py:60-210 for a 3-D tile_size).
  * fp32 throughout, Z the contiguous axis, 64-bit volume offsets.  flips: HOST array of the V mirror variants (V in {1, 2, 4, 8}),
  * each a bitmask of flipped tile axes (bit a = axis a), in the reference's order none, 0, 1, 2, (0,1), (0,2), (1,2), (0,1,2)

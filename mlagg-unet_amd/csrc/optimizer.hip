@@ -13,6 +13,11 @@
 //              (torch rewrites them: 216 MB of extra traffic).
 // Tensors are addressed through a device table of (param, grad, exp_avg, exp_avg_sq, numel) rows and a work list of
 // (tensor, chunk) pairs, both built by the host wrapper.  HBM-bound: 28 bytes per parameter for the update, 4 for the norm.
+//
+// K34 -- the same two steps for the other optimizers of the reference's trainers: SGD with Nesterov momentum (the base trainer,
+// nnUNetTrainer.py:448-452), AdamW with amsgrad (nnUNetTrainerAdam) and Adam with L2 decay (nnUNetTrainerVanillaAdam).  The norm
+// kernels, the table rows and the work list are K11's; the update kernel is instantiated per kind and reads / writes only the state
+// tensors its kind has: 20 (SGD), 36 (amsgrad) and 28 (Adam) bytes per parameter, 4 more for the norm.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -83,6 +88,16 @@ struct AdamArgs {
     float lr, beta1, beta2, eps, weight_decay, max_norm, bias_c1, bias_c2_sqrt;
 };
 
+// min(1, max_norm / (norm + 1e-6)) from the squared norm the reduce kernel left in *sumsq; 1 without clipping
+__device__ __forceinline__ float clip_coef(float max_norm, const double *__restrict__ sumsq)
+{
+    if (!(max_norm > 0.f)) return 1.f;
+    const float norm = (float)sqrt(*sumsq);
+    // a non-finite norm poisons EVERY parameter, as clip_grad_norm_'s NaN coefficient does (fminf(NaN, 1) = 1 would
+    // keep stepping the finite gradients and hide the failure)
+    return (norm == norm && norm < __builtin_huge_valf()) ? fminf(max_norm / (norm + 1e-6f), 1.f) : __builtin_nanf("");
+}
+
 __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, const AdamArgs &a, float coef)
 {
     g *= coef;
@@ -109,13 +124,7 @@ adamw_update_kernel(const TensorRow *__restrict__ table, const int2 *__restrict_
     const TensorRow t = table[w.x];
     const long long lo = (long long)w.y * CHUNK, hi = min(lo + CHUNK, t.n);
     const long long n = hi - lo;
-    float coef = 1.f;
-    if (a.max_norm > 0.f) {
-        const float norm = (float)sqrt(*sumsq);
-        // a non-finite norm poisons EVERY parameter, as clip_grad_norm_'s NaN coefficient does (fminf(NaN, 1) = 1 would
-        // keep stepping the finite gradients and hide the failure)
-        coef = (norm == norm && norm < __builtin_huge_valf()) ? fminf(a.max_norm / (norm + 1e-6f), 1.f) : __builtin_nanf("");
-    }
+    const float coef = clip_coef(a.max_norm, sumsq);
     float *p = t.p + lo, *m = t.m + lo, *v = t.v + lo;
     const float *g = t.g + lo;
     const bool al = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
@@ -132,6 +141,121 @@ adamw_update_kernel(const TensorRow *__restrict__ table, const int2 *__restrict_
         reinterpret_cast<float4 *>(v)[i] = v4;
     }
     for (long long i = 4 * n4 + threadIdx.x; i < n; i += OPT_TPB) adam_one(p[i], g[i], m[i], v[i], a, coef);
+}
+
+// ---- K34: the other optimizers of the reference's trainers on the same table, work list and norm kernels ----------------------
+// KIND (MLAGG_OPT_* of the header) and the state tensors of a row: SGD_NESTEROV m = momentum_buffer (v unused, may be null);
+// ADAMW_AMSGRAD m, v and a third tensor max_exp_avg_sq, whose address comes from `extra` (one pointer per table row: the 5 x 8-byte
+// row of K11 stays as it is); ADAM_L2 m, v.  a.beta1 carries the momentum of SGD.
+template <int KIND>
+__device__ __forceinline__ void opt_one(float &p, float g, float &m, float &v, float &vmax, const AdamArgs &a, float coef, float omb1,
+                                        float omb2)
+{
+    g *= coef;
+    if (KIND == MLAGG_OPT_SGD_NESTEROV) {
+        g += a.weight_decay * p;                          // torch.optim.SGD: L2 decay, dampening 0
+        m = a.beta1 * m + g;                              // a zero buffer gives torch's first step (buf = g)
+        p -= a.lr * (g + a.beta1 * m);
+        return;
+    }
+    if (KIND == MLAGG_OPT_ADAM_L2)
+        g += a.weight_decay * p;
+    else
+        p *= 1.f - a.lr * a.weight_decay;
+    m = a.beta1 * m + omb1 * g;                           // omb = 1 - beta rounded from double, the weight torch passes to lerp_ /
+    v = a.beta2 * v + omb2 * g * g;                       // addcmul_ (1.f - 0.999f is 1.3e-5 off 0.001)
+    float s = v;
+    if (KIND == MLAGG_OPT_ADAMW_AMSGRAD) {
+        vmax = (v > vmax || v != v) ? v : vmax;           // torch.maximum: a NaN moment stays a NaN
+        s = vmax;
+    }
+    const float denom = sqrtf(s) / a.bias_c2_sqrt + a.eps;
+    p -= (a.lr / a.bias_c1) * (m / denom);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(OPT_TPB)
+opt_update_kernel(const TensorRow *__restrict__ table, float *const *__restrict__ extra, const int2 *__restrict__ work,
+                  const double *__restrict__ sumsq, AdamArgs a, double beta1, double beta2, const float *__restrict__ lr_dev,
+                  const int *__restrict__ step_dev)
+{
+    constexpr bool SGD = KIND == MLAGG_OPT_SGD_NESTEROV, AMS = KIND == MLAGG_OPT_ADAMW_AMSGRAD;
+    if (lr_dev) {
+        a.lr = *lr_dev;
+        if (!SGD) {
+            // from the betas in double, as torch forms them: beta2 rounded to float first is 1.3e-8 off, its 1000th power 1.3e-5, and
+            // at a learning rate of 1e-2 that shows in the parameters
+            const double step = (double)*step_dev;
+            a.bias_c1 = (float)(1.0 - pow(beta1, step));
+            a.bias_c2_sqrt = (float)sqrt(1.0 - pow(beta2, step));
+        }
+    }
+    const int2 w = work[blockIdx.x];
+    const TensorRow t = table[w.x];
+    const long long lo = (long long)w.y * CHUNK, hi = min(lo + CHUNK, t.n);
+    const long long n = hi - lo;
+    const float coef = clip_coef(a.max_norm, sumsq);
+    const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+    // a kind reads and writes only the state tensors it has; the others alias m and are never touched
+    float *p = t.p + lo, *m = t.m + lo, *v = SGD ? m : t.v + lo, *x = AMS ? extra[w.x] + lo : m;
+    const float *g = t.g + lo;
+    const bool al = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)x)) & 15) == 0;
+    const long long n4 = al ? n >> 2 : 0;
+    for (long long i = threadIdx.x; i < n4; i += OPT_TPB) {
+        float4 p4 = reinterpret_cast<float4 *>(p)[i], m4 = reinterpret_cast<float4 *>(m)[i];
+        const float4 g4 = reinterpret_cast<const float4 *>(g)[i];
+        float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f), x4 = v4;
+        if (!SGD) v4 = reinterpret_cast<float4 *>(v)[i];
+        if (AMS) x4 = reinterpret_cast<float4 *>(x)[i];
+        opt_one<KIND>(p4.x, g4.x, m4.x, v4.x, x4.x, a, coef, omb1, omb2);
+        opt_one<KIND>(p4.y, g4.y, m4.y, v4.y, x4.y, a, coef, omb1, omb2);
+        opt_one<KIND>(p4.z, g4.z, m4.z, v4.z, x4.z, a, coef, omb1, omb2);
+        opt_one<KIND>(p4.w, g4.w, m4.w, v4.w, x4.w, a, coef, omb1, omb2);
+        reinterpret_cast<float4 *>(p)[i] = p4;
+        reinterpret_cast<float4 *>(m)[i] = m4;
+        if (!SGD) reinterpret_cast<float4 *>(v)[i] = v4;
+        if (AMS) reinterpret_cast<float4 *>(x)[i] = x4;
+    }
+    for (long long i = 4 * n4 + threadIdx.x; i < n; i += OPT_TPB) {
+        float pi = p[i], mi = m[i], vi = SGD ? 0.f : v[i], xi = AMS ? x[i] : 0.f;
+        opt_one<KIND>(pi, g[i], mi, vi, xi, a, coef, omb1, omb2);
+        p[i] = pi;
+        m[i] = mi;
+        if (!SGD) v[i] = vi;
+        if (AMS) x[i] = xi;
+    }
+}
+
+// norm launches (K11's kernels) + the update of `kind`; lr_dev / step_dev null: the launch-argument form
+int opt_launch(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work, double *sumsq,
+               AdamArgs a, double beta1, double beta2, const float *lr_dev, int *step_dev, hipStream_t st)
+{
+    const TensorRow *table = static_cast<const TensorRow *>(tensor_table);
+    float *const *extra = static_cast<float *const *>(extra_table);
+    const int2 *work = static_cast<const int2 *>(work_list);
+    const bool clip = a.max_norm > 0.f;
+    MLAGG_TIMED(K_OPT_VARIANTS, st);
+    if (clip) hipLaunchKernelGGL(adamw_sumsq_kernel, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq);
+    // device form: without clipping the reduce launch still runs (over zero partials) to advance the step counter
+    if (clip || step_dev)
+        hipLaunchKernelGGL(adamw_sumsq_reduce_kernel, dim3(1), dim3(OPT_TPB), 0, st, sumsq, clip ? n_work : 0, step_dev);
+    const int *step = step_dev;
+    if (kind == MLAGG_OPT_SGD_NESTEROV)
+        hipLaunchKernelGGL(opt_update_kernel<MLAGG_OPT_SGD_NESTEROV>, dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work, sumsq, a,
+                           beta1, beta2, lr_dev, step);
+    else if (kind == MLAGG_OPT_ADAMW_AMSGRAD)
+        hipLaunchKernelGGL(opt_update_kernel<MLAGG_OPT_ADAMW_AMSGRAD>, dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work, sumsq, a,
+                           beta1, beta2, lr_dev, step);
+    else
+        hipLaunchKernelGGL(opt_update_kernel<MLAGG_OPT_ADAM_L2>, dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work, sumsq, a,
+                           beta1, beta2, lr_dev, step);
+    return (int)hipGetLastError();
+}
+
+bool opt_kind_ok(int kind, const void *extra_table)
+{
+    if (kind != MLAGG_OPT_SGD_NESTEROV && kind != MLAGG_OPT_ADAMW_AMSGRAD && kind != MLAGG_OPT_ADAM_L2) return false;
+    return kind != MLAGG_OPT_ADAMW_AMSGRAD || extra_table != nullptr;
 }
 
 }  // namespace
@@ -180,4 +304,35 @@ extern "C" int mlagg_adamw_clip_step_dev(const void *tensor_table, const void *w
     hipLaunchKernelGGL(adamw_update_kernel, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, a, lr_dev,
                        (const int *)step_dev);
     return (int)hipGetLastError();
+}
+
+// K34 -- clip + SGD-Nesterov / AdamW-amsgrad / Adam-L2 (the optimizers of the reference's base trainer and of its nnUNetTrainerAdam /
+// nnUNetTrainerVanillaAdam) in the launch-argument form; `step` feeds the bias corrections of the Adam kinds and is ignored by SGD.
+// The betas arrive as doubles: the bias corrections are formed from them as torch forms them, the moments use their float values.
+extern "C" int mlagg_optimizer_clip_step(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
+                                         double *sumsq, float lr, double beta1, double beta2, float eps, float weight_decay,
+                                         float max_norm, int step, void *stream)
+{
+    if (!tensor_table || !work_list || !sumsq) return MLAGG_E_NULLPTR;
+    if (!opt_kind_ok(kind, extra_table) || n_work <= 0 || (kind != MLAGG_OPT_SGD_NESTEROV && step < 1)) return MLAGG_E_UNSUPPORTED;
+    AdamArgs a{lr, (float)beta1, (float)beta2, eps, weight_decay, max_norm, 1.f, 1.f};
+    if (kind != MLAGG_OPT_SGD_NESTEROV) {
+        a.bias_c1 = (float)(1.0 - pow(beta1, (double)step));
+        a.bias_c2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
+    }
+    return opt_launch(kind, tensor_table, extra_table, work_list, n_work, sumsq, a, beta1, beta2, nullptr, nullptr,
+                      static_cast<hipStream_t>(stream));
+}
+
+// The same with the learning rate and the step counter resident on the device, for a hipGraph capture of the whole step: step_dev is
+// advanced by this call for every kind (SGD does not read it; it is the count of steps a replayed graph has taken).
+extern "C" int mlagg_optimizer_clip_step_dev(int kind, const void *tensor_table, const void *extra_table, const void *work_list,
+                                             int n_work, double *sumsq, const float *lr_dev, int *step_dev, double beta1, double beta2,
+                                             float eps, float weight_decay, float max_norm, void *stream)
+{
+    if (!tensor_table || !work_list || !sumsq || !lr_dev || !step_dev) return MLAGG_E_NULLPTR;
+    if (!opt_kind_ok(kind, extra_table) || n_work <= 0) return MLAGG_E_UNSUPPORTED;
+    AdamArgs a{0.f, (float)beta1, (float)beta2, eps, weight_decay, max_norm, 1.f, 1.f};
+    return opt_launch(kind, tensor_table, extra_table, work_list, n_work, sumsq, a, beta1, beta2, lr_dev, step_dev,
+                      static_cast<hipStream_t>(stream));
 }

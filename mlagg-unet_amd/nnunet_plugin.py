@@ -22,6 +22,10 @@ What the class overrides, and why the inherited method cannot stay (B = nnUNetTr
                     label manager that says ``has_regions`` without naming its ``foreground_regions`` keeps the reference's classes.
                     ``loss=`` of the factories selects one of the reference's loss-variant trainers instead (variants/loss/:
                     top-k cross-entropy on K33, Dice only, CE only, smooth 0): ``trainer.loss_variant_deep_supervision_loss``.
+  * ``configure_optimizers``  T:137-147: AdamW + cosine schedule on K11.  ``optimizer=`` of the factories selects the recipe of the
+                    reference's base trainer (B:448-452: SGD momentum 0.99 Nesterov + PolyLR) or of its optimizer-variant trainers
+                    (variants/optimizer/nnUNetTrainerAdam.py) instead, with the clip and the update fused on the device (K34:
+                    ``trainer.ClipSGD`` / ``trainer.ClipAdam`` + ``trainer.PolyLRSchedule``).
 """
 import os
 
@@ -68,6 +72,18 @@ def _check_loss(loss):
         raise RuntimeError(f"loss {loss!r}: {DEFAULT_LOSS!r} or one of {tuple(trainer.LOSS_VARIANTS)}")
 
 
+def _check_optimizer(optimizer):
+    if optimizer is not None and (optimizer == "adamw" or optimizer not in trainer.OPTIMIZERS):
+        raise RuntimeError(f"optimizer {optimizer!r}: None (the class's own recipe) or one of {trainer.OPTIMIZERS[1:]}")
+
+
+def _variant_optimizers(self, optimizer, capturable):
+    """``configure_optimizers`` of a class built with ``optimizer=``: the fused optimizer of that recipe (K34) plus PolyLR over the
+    trainer's ``num_epochs``; ``initial_lr`` and ``weight_decay`` are the trainer's (the base trainer's 1e-2 / 3e-5 unless a class set them)."""
+    return trainer.configure_optimizers(self.network, getattr(self, "initial_lr", 1e-2), getattr(self, "weight_decay", 3e-5),
+                                        capturable=capturable, optimizer=optimizer, num_epochs=int(getattr(self, "num_epochs", 1000)))
+
+
 def _variant_loss(variant, label_manager, batch_dice, ddp, ignore_label):
     """The loss of one of the reference's loss-variant trainers (variants/loss/nnUNetTrainer{TopkLoss,DiceLoss,CELoss}.py) as
     ``trainer.loss_variant_deep_supervision_loss``.  Region-based label managers: "dice" and "dice_ce_nosmooth" take the fused K29
@@ -87,14 +103,19 @@ def _variant_loss(variant, label_manager, batch_dice, ddp, ignore_label):
     return loss
 
 
-def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAULT_LOSS):
+def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAULT_LOSS, optimizer=None):
     """loss: "dice_ce" (the reference trainer's DC_and_CE_loss / DC_and_BCE_loss) or one of ``trainer.LOSS_VARIANTS`` -- the loss of
     the reference's nnUNetTrainerTopk10Loss ("topk10"), ...Topk10LossLS01 ("topk10_ls01"), ...DiceTopK10Loss ("dice_topk10"),
     ...DiceLoss ("dice"), ...CELoss ("ce") or ...DiceCELoss_noSmooth ("dice_ce_nosmooth").  Every one of them is device-fused, so the
-    step is replayed as a hipGraph with any of them; the choice is kept in ``mlagg_loss_variant``."""
+    step is replayed as a hipGraph with any of them; the choice is kept in ``mlagg_loss_variant``.
+    optimizer: None (the reference trainer's AdamW + cosine schedule on K11) or the recipe of one of the reference's other trainers on
+    K34 with PolyLR: "sgd" (the base trainer's SGD, Nesterov momentum 0.99), "adam" (nnUNetTrainerAdam: AdamW with amsgrad),
+    "vanilla_adam" (nnUNetTrainerVanillaAdam: Adam with L2 decay); ``initial_lr`` is then the base trainer's 1e-2.  Every one of them
+    keeps its learning rate on the device, so the step replays as a hipGraph too; the choice is kept in ``mlagg_optimizer``."""
     if precision not in PRECISIONS:
         raise RuntimeError(f"precision {precision!r}: this build of the MI355X path offers {PRECISIONS}")
     _check_loss(loss)
+    _check_optimizer(optimizer)
     loss_variant = loss
 
     class nnUNetTrainer_MLAgg_2D_dt_MS(nnUNetTrainer):
@@ -102,7 +123,7 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
             super().__init__(plans, configuration, fold, dataset_json, unpack_dataset,
                              device if device is not None else torch.device("cuda"))
             # reference T:52-59
-            self.initial_lr = 5e-4
+            self.initial_lr = 5e-4 if optimizer is None else 1e-2                   # the base trainer's 1e-2 for its recipes (B:146)
             self.weight_decay = 3e-5
             self.oversample_foreground_percent = 0.33
             self.num_iterations_per_epoch = 250
@@ -115,6 +136,7 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
                 self.grad_scaler = None
             self.mlagg_precision = precision
             self.mlagg_loss_variant = loss_variant                                  # for logs and checkpoints
+            self.mlagg_optimizer = optimizer
             self._graphed, self._graph_key, self._graph_eager, self._graph_failed = None, None, 0, None
             # run_training.py:123-125 sets cudnn.benchmark (MIOpen's exhaustive find); here: the committed find-db, which
             # holds the fp32 convolutions of the 256 x 256 step only.  Any other patch size or precision takes MIOpen's
@@ -173,6 +195,8 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
 
         def configure_optimizers(self):                                             # reference T:137-147
             # capturable: learning rate and step counter live on the device, so the same optimizer serves eager and replayed steps
+            if optimizer is not None:
+                return _variant_optimizers(self, optimizer, self._graph_ok())
             return trainer.configure_optimizers(self.network, self.initial_lr, self.weight_decay, capturable=self._graph_ok())
 
         def _to_device(self, batch):                                                # reference B:834-841
@@ -187,7 +211,7 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
             if not isinstance(target, list):
                 target = [target]
             data, target = data.float(), [t.float() for t in target]
-            if self._graph_ok() and isinstance(self.optimizer, trainer.ClipAdamW) and self.optimizer.capturable:
+            if self._graph_ok() and isinstance(self.optimizer, trainer.ClipOptimizer) and self.optimizer.capturable:
                 key = (tuple(data.shape),) + tuple(tuple(t.shape) for t in target)
                 if self._graphed is not None and key == self._graph_key:
                     return {"loss": self._graphed(data, target).cpu().numpy()}      # replay + the reference's per-step host copy
@@ -229,15 +253,19 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
     return nnUNetTrainer_MLAgg_2D_dt_MS
 
 
-def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS):
+def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimizer=None):
     """``nnUNetTrainerUMambaEnc_SS3D`` (reference variants/mamba/nnUNetTrainerUMambaEnc_SS3D.py:8-31) on the MI355X 3-D network
     (model3d.UMambaEnc; BASELINE configs[3]).  The reference class overrides ``build_network_architecture`` only and inherits the
     base trainer's recipe (SGD momentum 0.99 Nesterov + PolyLR, nnUNetTrainer.py:448-452; DC_and_CE deep-supervision loss,
     :330-352); so does this one, plus what the device network needs from the loop: the fp32 step without autocast / GradScaler
     (B:848-858), the fused K9 loss, ``trainer.wrap_ddp``, and the deep-supervision switch on the unwrapped module.
-    loss: as in ``make_trainer_class``."""
+    loss: as in ``make_trainer_class``.
+    optimizer: None inherits the host trainer's ``configure_optimizers`` (torch.optim.SGD behind clip_grad_norm_); "sgd" is the same
+    recipe with the clip and the update fused on the device (K34: ClipSGD + PolyLR), i.e. the reference's class with its step tail on
+    the MI355X; "adam" / "vanilla_adam" as in ``make_trainer_class``.  The 3-D step stays eager.  Kept in ``mlagg_optimizer``."""
     from . import model3d
     _check_loss(loss)
+    _check_optimizer(optimizer)
     loss_variant = loss
 
     class nnUNetTrainerUMambaEnc_SS3D(nnUNetTrainer):
@@ -246,6 +274,7 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS):
                              device if device is not None else torch.device("cuda"))
             self.grad_scaler = None                                                  # fp32 step: no loss scaling (B:152)
             self.mlagg_loss_variant = loss_variant                                   # for logs and checkpoints
+            self.mlagg_optimizer = optimizer
             miopen_tuning.use_tuned_convolutions(enabled=False)                      # no committed records for 3-D convolutions
 
         @staticmethod
@@ -289,6 +318,10 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS):
                 return trainer.deep_supervision_loss(list(output), list(target[:len(output)]), batch_dice, ddp, ignore_label=ignore)
 
             return loss
+
+        if optimizer is not None:
+            def configure_optimizers(self):                                          # reference B:448-452 / nnUNetTrainerAdam.py
+                return _variant_optimizers(self, optimizer, False)                   # the 3-D step is not captured
 
         def train_step(self, batch):                                                 # reference B:833-863
             data = batch["data"].to(self.device, non_blocking=True)

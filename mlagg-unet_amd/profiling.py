@@ -84,3 +84,15 @@ def algorithmic_bytes_sel1(kernel, batch, tokens, C=64, K=12, R=2):
         "sel1_bwd_kernel<2>": K * (8 * C + par + 4 * (2 + R)) + 4 * C,                   # read u, dy, params; write dB, dC, ddtr, merged du
     }
     return int(per_token.get(kernel, 0)) * tokens * batch
+
+
+# the row of the "optimizer variants" timer (K34; csrc/prof.h K_OPT_VARIANTS, the last tag): update bytes per parameter of each kind
+OPTIMIZER_VARIANT_BYTES = {"sgd_nesterov": 20,     # read p, g, momentum_buffer; write p, momentum_buffer
+                           "adamw_amsgrad": 36,    # read p, g, exp_avg, exp_avg_sq, max_exp_avg_sq; write all but g
+                           "adam_l2": 28}          # read p, g, exp_avg, exp_avg_sq; write p, exp_avg, exp_avg_sq (as K11's AdamW)
+
+
+def algorithmic_bytes_optimizer(kind, parameters, clip=True):
+    """Bytes one step of `kind` (a key of OPTIMIZER_VARIANT_BYTES) must move for `parameters` fp32 parameters: the update plus, with
+    clipping, one more read of the gradients for the norm."""
+    return int(parameters) * (OPTIMIZER_VARIANT_BYTES[kind] + (4 if clip else 0))

@@ -5,6 +5,8 @@ Mirrors the reference's trainer surface on the hot path:
                               backward, clip_grad_norm_ 12, optimizer step)
   * ``configure_optimizers``  reference nnUNetTrainer_MLAgg_2D_dt_MS.py:137-147 (AdamW 5e-4 / 3e-5 / eps 1e-4,
                               timm CosineLRScheduler restated: t_initial 500, lr_min 1e-6, warmup 10 @ 1e-4)
+                              and, by ``optimizer=``, the base trainer's SGD + PolyLR (nnUNetTrainer.py:448-452) and the Adam
+                              recipes of variants/optimizer/nnUNetTrainerAdam.py: ``ClipSGD`` / ``ClipAdam`` (K34), ``PolyLRSchedule``
   * ``deep_supervision_loss`` reference loss/deep_supervision.py:17-34 over DC_and_CE_loss
                               (loss/compound_losses.py:31-57, loss/dice.py:73-117, loss/robust_ce_loss.py:12-16)
   * ``region_deep_supervision_loss``  the same wrapper over DC_and_BCE_loss (loss/compound_losses.py:60-100), the loss of
@@ -357,23 +359,29 @@ def region_deep_supervision_loss(outputs, targets, regions=None, batch_dice=True
 # ------------------------------------------------------------------------------------------------
 # optimiser / schedule
 # ------------------------------------------------------------------------------------------------
-class ClipAdamW(torch.optim.Optimizer):
-    """clip_grad_norm_(max_norm) + AdamW in two launches for all parameters (K11).  Same hyper-parameters, arithmetic and
-    ``state_dict`` layout (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``) as ``torch.optim.AdamW``; the clip
-    coefficient is computed on the device (no host synchronisation) and the gradients in memory stay unscaled."""
+class ClipOptimizer(torch.optim.Optimizer):
+    """What the fused clip + update optimizers share (K11: ``ClipAdamW``; K34: ``ClipSGD``, ``ClipAdam``): the pointer table and the work
+    list of the kernels, the pinned upload of the gradient addresses, the device-resident learning rate and step counter of the
+    capturable form with its one capture per optimizer, and a ``load_state_dict`` that keeps the state tensors in place.
+    A subclass names its per-parameter state tensors in ``_STATE`` (in the order of the table: two columns, a third goes into the extra
+    pointer block), says in ``_HAS_STEP`` whether torch's state carries a ``step`` entry, and launches its kernels in ``_launch``."""
+    _STATE = ()
+    _HAS_STEP = True
 
-    def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-4, weight_decay=3e-5, capturable=False):
+    def __init__(self, params, defaults, capturable=False):
         params = list(params)
-        super().__init__(params, dict(lr=float(lr), betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, defaults)
+        self._name = type(self).__name__
         if len(self.param_groups) != 1:
             # the clip norm is the norm over ALL parameters (clip_grad_norm_(network.parameters(), 12), B:855): one group
-            raise RuntimeError("ClipAdamW: one parameter group (the reference passes network.parameters(), T:138)")
+            raise RuntimeError(f"{self._name}: one parameter group (the reference passes network.parameters(), T:138)")
         self.capturable = bool(capturable)
         # hipGraph form (GraphedTrainStep): the step counter and a COPY of the learning rate live on the device.  ``param_groups``
         # keeps the learning rate as the Python float that schedules assign and training loops log, round and pickle; ``sync_lr``
         # carries it to the device copy before a replay
+        lr = float(self.param_groups[0]["lr"])
         self._step_dev = torch.zeros(1, dtype=torch.int32, device=params[0].device) if capturable else None
-        self._lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=params[0].device) if capturable else None
+        self._lr_dev = torch.full((1,), lr, dtype=torch.float32, device=params[0].device) if capturable else None
         self._steps = 0
         self._work = {}
         self._tables = {}                             # capturable: per (parameter set, captured?) (pinned host table, device table)
@@ -383,20 +391,32 @@ class ClipAdamW(torch.optim.Optimizer):
     def _state_of(self, p):
         st = self.state[p]
         if not st:
-            st["step"] = torch.tensor(0.0)
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if self._HAS_STEP:
+                st["step"] = torch.tensor(0.0)
+            for k in self._STATE:
+                st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
         return st
+
+    def _upload_len(self, T):
+        """int64 entries of the upload buffer of T parameter tensors: the rows, and one more pointer each with a third state tensor."""
+        return (6 if len(self._STATE) > 2 else 5) * T
+
+    def _rows_and_third(self, buf, T):
+        """The two named parts of a flat upload buffer (host or device), as views of it: the (T, 5) rows (param, grad, state 0,
+        state 1, numel) the kernels index, and behind them the T pointers to the third state tensor (None for two or fewer).
+        5 T int64 entries keep the second part 8-byte aligned."""
+        return buf[:5 * T].view(T, 5), (buf[5 * T:] if len(self._STATE) > 2 else None)
 
     def steps_done(self):
         """Optimisation steps so far (capturable: read from the device counter the replays advance; that synchronises)."""
         return int(self._step_dev.item()) if self.capturable else self._steps
 
     def state_dict(self):
-        n = float(self.steps_done())
-        for st in self.state.values():
-            if st:
-                st["step"] = torch.tensor(n)
+        if self._HAS_STEP:
+            n = float(self.steps_done())
+            for st in self.state.values():
+                if st:
+                    st["step"] = torch.tensor(n)
         return super().state_dict()
 
     def sync_lr(self):
@@ -407,30 +427,49 @@ class ClipAdamW(torch.optim.Optimizer):
         if self.capturable:
             self._lr_dev.fill_(float(self.param_groups[0]["lr"]))
 
+    def _check_loaded_group(self, group):
+        """Refuse a loaded parameter group that asks for arithmetic the kernels do not implement."""
+
     def load_state_dict(self, sd):
-        # capturable: a captured graph holds the ADDRESSES of the moment tensors, of the work list and of its pointer table, so
-        # the loaded moments are copied into the existing tensors and all of these stay in place
-        keep = {p: (st["exp_avg"], st["exp_avg_sq"]) for p, st in self.state.items() if st} if self.capturable else {}
+        # capturable: a captured graph holds the ADDRESSES of the state tensors, of the work list and of its pointer table, so
+        # the loaded state is copied into the existing tensors and all of these stay in place
+        keep = {p: tuple(st[k] for k in self._STATE) for p, st in self.state.items() if st} if self.capturable else {}
+        for g in sd["param_groups"]:
+            self._check_loaded_group(g)               # before anything of this optimizer changes
         super().load_state_dict(sd)
         for g in self.param_groups:
             g["lr"] = float(g["lr"])                  # a checkpoint written while the learning rate was a device tensor
-        for p, (m, v) in keep.items():
+        for p, st in self.state.items():
+            for k in self._STATE:
+                if st and st.get(k, 0) is None:       # torch.optim.SGD writes ``momentum_buffer: None`` until a buffer exists
+                    st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                elif st and k not in st:
+                    raise RuntimeError(f"{self._name}: the checkpoint holds no {k!r} for a parameter")
+        for p, kept in keep.items():
             st = self.state[p]
-            if st:
-                m.copy_(st["exp_avg"])
-                v.copy_(st["exp_avg_sq"])
-            else:                                     # a checkpoint from before the first step
-                m.zero_()
-                v.zero_()
+            for k, t in zip(self._STATE, kept):
+                if st:
+                    t.copy_(st[k])
+                else:                                 # a checkpoint from before the first step
+                    t.zero_()
+            if not st and self._HAS_STEP:
                 st["step"] = torch.tensor(0.0)
-            st["exp_avg"], st["exp_avg_sq"] = m, v
+            for k, t in zip(self._STATE, kept):
+                st[k] = t
         if not self.capturable:
-            self._work.clear()                        # the moment tensors were replaced: cached addresses are stale
+            self._work.clear()                        # the state tensors were replaced: cached addresses are stale
         self._stepped = None
-        steps = [int(st["step"]) for st in self.state.values() if st and "step" in st]
-        self._steps = max(steps) if steps else 0
-        if self.capturable:
-            self._step_dev.fill_(self._steps)
+        if self._HAS_STEP:
+            steps = [int(st["step"]) for st in self.state.values() if st and "step" in st]
+            self._steps = max(steps) if steps else 0
+            if self.capturable:
+                self._step_dev.fill_(self._steps)
+
+    def _launch(self, group, table, extra, work, max_norm, device_form):
+        """Launch the kernels of one step: ``table`` / ``extra`` / ``work`` are device tensors (``extra`` None without a third state
+        tensor); ``device_form``: read the learning rate and the step from ``_lr_dev`` / ``_step_dev``, else ``group["lr"]`` and
+        ``_steps`` as launch arguments."""
+        raise NotImplementedError
 
     @torch.no_grad()
     def step(self, closure=None, max_norm=0.0):
@@ -443,6 +482,7 @@ class ClipAdamW(torch.optim.Optimizer):
         self._steps += 1
         from . import ops
         ops.invalidate_weight_images()                # the kernels below rewrite the parameters through raw pointers: no version bump
+        name = self._name
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -455,29 +495,39 @@ class ClipAdamW(torch.optim.Optimizer):
             if self._stepped is None:
                 self._stepped = key
             elif key != self._stepped:
-                raise RuntimeError("ClipAdamW: the set of parameters with a gradient changed between steps")
+                raise RuntimeError(f"{name}: the set of parameters with a gradient changed between steps")
+            T = len(ps)
             if key not in self._work:
-                # per parameter set: the work list and the static columns of the pointer table (uploaded once)
+                # per parameter set: the work list and the static columns of the pointer table (uploaded once).  Rows of
+                # (param, grad, state 0, state 1, numel); behind the T rows one pointer per row for a third state tensor
                 for p in ps:
                     self._state_of(p)
                     if not (p.is_cuda and p.is_contiguous() and p.dtype == torch.float32):
-                        raise RuntimeError("ClipAdamW: fp32 contiguous parameters on the MI355X expected")
+                        raise RuntimeError(f"{name}: fp32 contiguous parameters on the MI355X expected")
                 numels = [p.numel() for p in ps]
                 wl = [(i, c) for i, n in enumerate(numels) for c in range((n + chunk - 1) // chunk)]
-                base = torch.tensor([(p.data_ptr(), 0, self.state[p]["exp_avg"].data_ptr(),
-                                      self.state[p]["exp_avg_sq"].data_ptr(), p.numel()) for p in ps], dtype=torch.int64)
+                # ONE flat upload buffer: 5 T entries of rows, then (three state tensors only) T pointers to the third
+                base = torch.zeros(self._upload_len(T), dtype=torch.int64)
+                rows, third = self._rows_and_third(base, T)
+                rows[:, 0] = torch.tensor([p.data_ptr() for p in ps], dtype=torch.int64)
+                rows[:, 4] = torch.tensor(numels, dtype=torch.int64)
+                for i, k in enumerate(self._STATE):
+                    ptrs = torch.tensor([self.state[p][k].data_ptr() for p in ps], dtype=torch.int64)
+                    if i < 2:
+                        rows[:, 2 + i] = ptrs
+                    else:
+                        third.copy_(ptrs)
                 self._work[key] = (torch.tensor(wl, dtype=torch.int32).to(dev), base)
             work, base = self._work[key]
             # only the gradient addresses change from step to step (zero_grad(set_to_none=True)); the table goes up through
             # pinned memory without blocking the host (a pageable copy would make the CPU wait for the GPU every step)
             host = base.clone()
-            host[:, 1] = torch.tensor([p.grad.data_ptr() for p in ps], dtype=torch.int64)
+            self._rows_and_third(host, T)[0][:, 1] = torch.tensor([p.grad.data_ptr() for p in ps], dtype=torch.int64)
             for p in ps:
                 if not (p.grad.is_contiguous() and p.grad.dtype == torch.float32):
-                    raise RuntimeError("ClipAdamW: fp32 contiguous gradients expected")
+                    raise RuntimeError(f"{name}: fp32 contiguous gradients expected")
             if self._sumsq is None or self._sumsq.device != dev or self._sumsq.numel() != 1 + work.shape[0]:
                 self._sumsq = torch.zeros(1 + work.shape[0], dtype=torch.float64, device=dev)       # [0]: total; one partial per work item
-            b1, b2 = group["betas"]
             if self.capturable:
                 # a table that OUTLIVES the call (a replayed graph reads it): one pinned host copy + one device copy per parameter
                 # set, re-uploaded only when a gradient address changed.  Inside a capture the upload becomes a copy node out of
@@ -485,7 +535,7 @@ class ClipAdamW(torch.optim.Optimizer):
                 # steps have a pair of their own, which no eager step -- with its own gradient addresses -- ever writes.  Both
                 # pairs are allocated at the first step, whichever form it is: a capture that follows an eager or warm-up step then
                 # pins no memory (a first step INSIDE a capture still does, as it always did), at the price of one unused pair
-                # (40 bytes per parameter) in an optimizer that is never captured
+                # (40 bytes per parameter tensor, 48 with a third state tensor) in an optimizer that is never captured
                 capturing = torch.cuda.is_current_stream_capturing()
                 for c in (False, True):
                     if (key, c) not in self._tables:
@@ -494,21 +544,17 @@ class ClipAdamW(torch.optim.Optimizer):
                 if not torch.equal(pinned, host):
                     if not capturing:
                         torch.cuda.current_stream().synchronize()      # an earlier upload may still be reading the pinned buffer
-                    elif int(pinned[0, 0]) != -1:      # column 0 holds parameter addresses; -1 is the fill of a table never written
-                        raise RuntimeError("ClipAdamW: a second capture with other gradient addresses would redirect the first "
+                    elif int(pinned.reshape(-1)[0]) != -1:     # the first entry is a parameter address; -1 is the fill of a table never written
+                        raise RuntimeError(f"{name}: a second capture with other gradient addresses would redirect the first "
                                            "graph's update; one captured step per optimizer")
                     pinned.copy_(host)
                     table.copy_(pinned, non_blocking=True)
                 if not capturing:
                     self.sync_lr()
-                _lib.launch("mlagg_adamw_clip_step_dev", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(),
-                            self._lr_dev.data_ptr(), self._step_dev.data_ptr(), float(b1), float(b2), float(group["eps"]),
-                            float(group["weight_decay"]), float(max_norm))
+                self._launch(group, *self._rows_and_third(table, T), work, float(max_norm), True)
                 continue
             table = host.pin_memory().to(dev, non_blocking=True)
-            lr = float(group["lr"])
-            _lib.launch("mlagg_adamw_clip_step", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(), lr, float(b1),
-                        float(b2), float(group["eps"]), float(group["weight_decay"]), float(max_norm), self._steps)
+            self._launch(group, *self._rows_and_third(table, T), work, float(max_norm), False)
             self._keepalive = table                   # the table must outlive the asynchronous launches
         return loss
 
@@ -517,21 +563,180 @@ class ClipAdamW(torch.optim.Optimizer):
         return self._sumsq[:1].sqrt().float()
 
 
-def configure_optimizers(model, initial_lr=5e-4, weight_decay=3e-5, fused=None, capturable=False):
-    """AdamW + cosine schedule of reference T:137-147.  ``capturable=True`` keeps the step counter and a copy of the
-    learning rate on the device so that the whole step can live inside one hipGraph (GraphedTrainStep)."""
+class ClipAdamW(ClipOptimizer):
+    """clip_grad_norm_(max_norm) + AdamW in two launches for all parameters (K11).  Same hyper-parameters, arithmetic and
+    ``state_dict`` layout (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``) as ``torch.optim.AdamW``; the clip
+    coefficient is computed on the device (no host synchronisation) and the gradients in memory stay unscaled."""
+    _STATE = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-4, weight_decay=3e-5, capturable=False):
+        super().__init__(params, dict(lr=float(lr), betas=betas, eps=eps, weight_decay=weight_decay), capturable)
+
+    def _launch(self, group, table, extra, work, max_norm, device_form):
+        from . import _lib
+        b1, b2 = group["betas"]
+        if device_form:
+            _lib.launch("mlagg_adamw_clip_step_dev", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(),
+                        self._lr_dev.data_ptr(), self._step_dev.data_ptr(), float(b1), float(b2), float(group["eps"]),
+                        float(group["weight_decay"]), max_norm)
+        else:
+            _lib.launch("mlagg_adamw_clip_step", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(),
+                        float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), max_norm, self._steps)
+
+
+class _ClipVariant(ClipOptimizer):
+    """K34: the optimizers that go through ``mlagg_optimizer_clip_step`` / ``_dev`` with a kind."""
+    _KIND = None
+
+    def _hyper(self, group):
+        """(beta1 or momentum, beta2, eps) of the group as the kernel takes them."""
+        raise NotImplementedError
+
+    def _launch(self, group, table, extra, work, max_norm, device_form):
+        from . import _lib
+        kind = _lib.CONSTANTS[self._KIND]
+        b1, b2, eps = self._hyper(group)
+        ex = extra.data_ptr() if extra is not None else None
+        if device_form:
+            _lib.launch("mlagg_optimizer_clip_step_dev", kind, table.data_ptr(), ex, work.data_ptr(), work.shape[0],
+                        self._sumsq.data_ptr(), self._lr_dev.data_ptr(), self._step_dev.data_ptr(), b1, b2, eps,
+                        float(group["weight_decay"]), max_norm)
+        else:
+            _lib.launch("mlagg_optimizer_clip_step", kind, table.data_ptr(), ex, work.data_ptr(), work.shape[0],
+                        self._sumsq.data_ptr(), float(group["lr"]), b1, b2, eps, float(group["weight_decay"]), max_norm, self._steps)
+
+
+class ClipSGD(_ClipVariant):
+    """clip_grad_norm_(max_norm) + torch.optim.SGD(momentum, nesterov=True) -- the optimizer of the reference's base trainer
+    (nnUNetTrainer.py:448-452: lr 1e-2, momentum 0.99, weight decay 3e-5) -- in two launches for all parameters (K34).  Hyper-parameters,
+    arithmetic (dampening 0; a zero buffer gives torch's first step) and ``state_dict`` layout (per parameter ``momentum_buffer``; the
+    group keys torch writes) are torch.optim.SGD's: a checkpoint of either loads into the other.  ``capturable=True`` keeps a copy of
+    the learning rate on the device, so a step captured into a hipGraph follows the schedule -- what torch.optim.SGD, whose learning
+    rate is baked into the captured launches, cannot do.  torch's SGD state carries no step count: ``steps_done`` counts the steps of
+    this object and ``load_state_dict`` leaves it alone."""
+    _STATE = ("momentum_buffer",)
+    _HAS_STEP = False
+    _KIND = "MLAGG_OPT_SGD_NESTEROV"
+
+    def __init__(self, params, lr=1e-2, momentum=0.99, weight_decay=3e-5, nesterov=True, capturable=False, *, dampening=0):
+        defaults = dict(lr=float(lr), momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                        maximize=False, foreach=None, differentiable=False, fused=None)
+        self._check_loaded_group(defaults)
+        super().__init__(params, defaults, capturable)
+
+    def _check_loaded_group(self, group):
+        if not group["nesterov"]:
+            raise RuntimeError("ClipSGD: nesterov=False is not implemented (the kernel computes p -= lr (g + momentum buf), the "
+                               "Nesterov step of the reference's trainers)")
+        if group["dampening"] != 0:
+            raise RuntimeError("ClipSGD: dampening must be 0 (torch.optim.SGD itself refuses Nesterov momentum with dampening, "
+                               "and the kernel computes buf = momentum buf + g)")
+        if not group["momentum"] > 0:
+            raise RuntimeError("ClipSGD: Nesterov momentum needs momentum > 0, as torch.optim.SGD says")
+        if group.get("maximize"):
+            raise RuntimeError("ClipSGD: maximize is not implemented")
+
+    def _hyper(self, group):
+        return float(group["momentum"]), 0.0, 0.0
+
+
+class ClipAdam(_ClipVariant):
+    """clip_grad_norm_(max_norm) + Adam in two launches for all parameters (K34), in the two forms the reference's optimizer-variant
+    trainers use (variants/optimizer/nnUNetTrainerAdam.py): ``amsgrad=True, decoupled=True`` is nnUNetTrainerAdam's
+    torch.optim.AdamW(amsgrad=True), ``amsgrad=False, decoupled=False`` nnUNetTrainerVanillaAdam's torch.optim.Adam with L2 weight
+    decay.  State keys and group keys are torch's (``step``, ``exp_avg``, ``exp_avg_sq`` and, with amsgrad, ``max_exp_avg_sq``), so
+    checkpoints go both ways.  The other two combinations have no kernel and are refused (amsgrad off with decoupled decay is
+    ``ClipAdamW``)."""
+    _KINDS = {(True, True): "MLAGG_OPT_ADAMW_AMSGRAD", (False, False): "MLAGG_OPT_ADAM_L2"}
+
+    def __init__(self, params, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, weight_decay=3e-5, amsgrad=True, decoupled=True, capturable=False):
+        defaults = dict(lr=float(lr), betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad), maximize=False,
+                        foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=bool(decoupled))
+        self._check_loaded_group(defaults)
+        self._KIND = self._KINDS[bool(amsgrad), bool(decoupled)]
+        self._STATE = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq") if amsgrad else ("exp_avg", "exp_avg_sq")
+        super().__init__(params, defaults, capturable)
+
+    def _check_loaded_group(self, group):
+        # a torch.optim.Adam / AdamW from before the key existed: the recipe this optimizer was built for
+        decoupled = group["decoupled_weight_decay"] if "decoupled_weight_decay" in group else self.defaults["decoupled_weight_decay"]
+        form = (bool(group["amsgrad"]), bool(decoupled))
+        if form not in self._KINDS:
+            raise RuntimeError(f"ClipAdam: amsgrad={form[0]}, decoupled={form[1]} has no kernel; the reference's recipes are "
+                               "amsgrad=True, decoupled=True (AdamW with amsgrad) and amsgrad=False, decoupled=False (Adam with L2 "
+                               "decay); AdamW without amsgrad is ClipAdamW")
+        if getattr(self, "_KIND", None) is not None and self._KINDS[form] != self._KIND:
+            raise RuntimeError(f"ClipAdam: the checkpoint was written with amsgrad={form[0]}, decoupled={form[1]}, this optimizer "
+                               "was built for the other recipe")
+        if group.get("maximize"):
+            raise RuntimeError("ClipAdam: maximize is not implemented")
+
+    def _hyper(self, group):
+        b1, b2 = group["betas"]
+        return float(b1), float(b2), float(group["eps"])
+
+
+OPTIMIZERS = ("adamw", "sgd", "adam", "vanilla_adam")
+
+
+def configure_optimizers(model, initial_lr=None, weight_decay=3e-5, fused=None, capturable=False, optimizer="adamw", num_epochs=1000):
+    """optimizer "adamw" (the default): AdamW + cosine schedule of reference T:137-147, initial_lr 5e-4.  The reference's other recipes,
+    initial_lr 1e-2 and PolyLR over ``num_epochs`` (nnUNetTrainer.py:146-149):
+      "sgd"           the base trainer's SGD(momentum 0.99, nesterov) (nnUNetTrainer.py:448-452)                 ClipSGD (K34)
+      "adam"          nnUNetTrainerAdam's AdamW(amsgrad=True) (variants/optimizer/nnUNetTrainerAdam.py:9-18)    ClipAdam (K34)
+      "vanilla_adam"  nnUNetTrainerVanillaAdam's Adam with L2 decay (:21-30)                                    ClipAdam (K34)
+    ``capturable=True`` keeps the step counter and a copy of the learning rate on the device so that the whole step can live inside
+    one hipGraph (GraphedTrainStep).  Host parameters get the torch optimizer of the same recipe."""
+    if optimizer not in OPTIMIZERS:
+        raise RuntimeError(f"optimizer {optimizer!r}: one of {OPTIMIZERS}")
     # every parameter, in module order, as the reference's ``AdamW(self.network.parameters(), ...)`` (T:138): the
     # frozen ``dummy_tensor`` keeps its slot, so parameter indices in optimizer checkpoints equal the reference's
     params = list(model.parameters())
     if fused is None:
         fused = all(p.is_cuda for p in params)
-    if fused and all(p.is_cuda for p in params):
+    on_device = fused and all(p.is_cuda for p in params)
+    if optimizer != "adamw":
+        lr = 1e-2 if initial_lr is None else initial_lr
+        if optimizer == "sgd":
+            opt = ClipSGD(params, lr, 0.99, weight_decay, capturable=capturable) if on_device else \
+                torch.optim.SGD(params, lr, weight_decay=weight_decay, momentum=0.99, nesterov=True)
+        elif optimizer == "adam":
+            opt = ClipAdam(params, lr, weight_decay=weight_decay, amsgrad=True, decoupled=True, capturable=capturable) if on_device else \
+                torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay, amsgrad=True)
+        else:
+            opt = ClipAdam(params, lr, weight_decay=weight_decay, amsgrad=False, decoupled=False, capturable=capturable) if on_device else \
+                torch.optim.Adam(params, lr=lr, weight_decay=weight_decay)
+        return opt, PolyLRSchedule(opt, lr, num_epochs)
+    initial_lr = 5e-4 if initial_lr is None else initial_lr
+    if on_device:
         # on the device: clip + AdamW of all parameters in three launches (K11); capturable: lr and step counter device-resident
         opt = ClipAdamW(params, initial_lr, weight_decay=weight_decay, eps=1e-4, capturable=capturable)
         return opt, CosineLRSchedule(opt, t_initial=500, lr_min=1e-6, warmup_t=10, warmup_lr_init=1e-4)
     lr = torch.tensor(initial_lr, device=params[0].device, dtype=torch.float32) if capturable else initial_lr
     opt = torch.optim.AdamW(params, lr, weight_decay=weight_decay, eps=1e-4, fused=fused, capturable=capturable)
     return opt, CosineLRSchedule(opt, t_initial=500, lr_min=1e-6, warmup_t=10, warmup_lr_init=1e-4)
+
+
+class PolyLRSchedule:
+    """PolyLRScheduler of the reference (training/lr_scheduler/polylr.py): lr = initial_lr (1 - step / max_steps) ** exponent, stepped
+    with the epoch index at epoch start (nnUNetTrainer.py:825).  ``step()`` without an epoch -- or with -1 -- takes an internal counter
+    and advances it; as in the reference, whose base class steps once on construction, the constructor takes the counter's step 0.  The
+    learning rate is assigned as a float in ``param_groups`` (``ClipOptimizer.sync_lr`` carries it to a captured graph)."""
+
+    def __init__(self, optimizer, initial_lr, max_steps, exponent=0.9):
+        self.optimizer, self.initial_lr, self.max_steps, self.exponent = optimizer, initial_lr, max_steps, exponent
+        self.ctr = 0
+        self.step()
+
+    def lr_at(self, current_step):
+        return self.initial_lr * (1 - current_step / self.max_steps) ** self.exponent
+
+    def step(self, current_step=None):
+        if current_step is None or current_step == -1:
+            current_step = self.ctr
+            self.ctr += 1
+        for g in self.optimizer.param_groups:
+            g["lr"] = self.lr_at(current_step)
 
 
 class CosineLRSchedule:
@@ -741,7 +946,7 @@ def train_step(network, optimizer, data, target: List[torch.Tensor], batch_dice=
         grad_scaler.scale(loss).backward()
         finish_grad_sync(network)
         grad_scaler.unscale_(optimizer)
-        if isinstance(optimizer, ClipAdamW):
+        if isinstance(optimizer, ClipOptimizer):
             grad_scaler.step(optimizer, max_norm=clip)
         else:
             torch.nn.utils.clip_grad_norm_([p for p in network.parameters() if p.grad is not None], clip)
@@ -750,8 +955,8 @@ def train_step(network, optimizer, data, target: List[torch.Tensor], batch_dice=
         return loss.detach()
     loss.backward()
     finish_grad_sync(network)
-    if isinstance(optimizer, ClipAdamW):
-        optimizer.step(max_norm=clip)                      # norm, clip coefficient and AdamW on the device, two launches
+    if isinstance(optimizer, ClipOptimizer):
+        optimizer.step(max_norm=clip)                      # norm, clip coefficient and update on the device, two launches
     else:
         torch.nn.utils.clip_grad_norm_([p for p in network.parameters() if p.grad is not None], clip)
         optimizer.step()
@@ -797,7 +1002,7 @@ class GraphedTrainStep:
         if target is not None:
             for dst, src in zip(self.target, target):
                 dst.copy_(src, non_blocking=True)
-        if isinstance(self.optimizer, ClipAdamW):
+        if isinstance(self.optimizer, ClipOptimizer):
             self.optimizer.sync_lr()                  # the learning rate the host holds NOW governs this replay
         self.graph.replay()
         # the replay rewrote the parameters through raw pointers and ran no host code: stacked weights and weight images that an
