@@ -782,6 +782,30 @@ int mlagg_optimizer_clip_step_dev(int kind, const void *tensor_table, const void
                                   float weight_decay, float max_norm, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K35: fp16 loss scaling (torch.amp.GradScaler of the reference's default train step, nnUNetTrainer.py:152, :848-858: scaled
+ * backward, unscale_, clip_grad_norm_ 12, step, update) fused into the same three launches of K11 / K34, with nothing decided on the
+ * host.  kind: MLAGG_OPT_ADAMW (K11's AdamW, bias corrections from the betas rounded to float, as K11 forms them) or one of K34's
+ * kinds.  tensor_table, extra_table, work_list, sumsq, lr_dev, step_dev, betas, eps, weight_decay, max_norm: as in
+ * mlagg_optimizer_clip_step_dev.  The gradients of the table carry the loss scale.  Device-resident state, one element each:
+ *   scale (float), growth_tracker (int32), found_inf (float, 0 or 1 as torch keeps it); grad_mult: one scratch float.
+ * 1. sum of squares of the UNSCALED gradients, (g * inv)^2 with inv = (float)(1.0 / (double)scale): the norm the reference clips on;
+ * 2. reduce (fixed order): found_inf = the total is not finite -- any inf / NaN element, and (the one deviation from torch, which
+ *    would step with a zero coefficient) finite elements whose unscaled square, or a work item's fp32 sum of such squares, leaves
+ *    fp32 (|g / scale|, or the norm of a 64 Ki-element chunk of it, above 1.8e19); a good step advances step_dev, a skipped one does not; grad_mult = inv * min(1, max_norm / (norm + 1e-6)) (inv alone with max_norm <= 0);
+ *    then torch._amp_update_scale_: overflow: scale *= backoff_factor, tracker 0; else the tracker counts up and at growth_interval
+ *    scale *= growth_factor if that is finite, tracker 0;
+ * 3. update: returns at once when found_inf is set (parameters and state stay bit-identical), else the arithmetic of the kind with
+ *    grad_mult where the clip coefficient stood.  Gradients stay SCALED and unclipped in memory.
+ * With scale 1.0 and no overflow the results equal those of the unscaled entry points bit for bit.  Nothing that changes between
+ * steps is an argument: the call can be captured into a hipGraph.
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_OPT_ADAMW 3
+int mlagg_scaled_clip_step_dev(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
+                               double *sumsq, const float *lr_dev, int *step_dev, float *scale, int *growth_tracker, float *found_inf,
+                               float *grad_mult, double beta1, double beta2, float eps, float weight_decay, float max_norm,
+                               double growth_factor, double backoff_factor, int growth_interval, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K20: 3-D sliding-window inference (reference nnunetv2/inference/sliding_window_prediction.py:60-210 for a 3-D tile_size).
  * fp32 throughout, Z the contiguous axis, 64-bit volume offsets.  flips: HOST array of the V mirror variants (V in {1, 2, 4, 8}),
  * each a bitmask of flipped tile axes (bit a = axis a), in the reference's order none, 0, 1, 2, (0,1), (0,2), (1,2), (0,1,2)

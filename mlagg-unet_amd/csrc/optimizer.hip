@@ -18,6 +18,12 @@
 // nnUNetTrainer.py:448-452), AdamW with amsgrad (nnUNetTrainerAdam) and Adam with L2 decay (nnUNetTrainerVanillaAdam).  The norm
 // kernels, the table rows and the work list are K11's; the update kernel is instantiated per kind and reads / writes only the state
 // tensors its kind has: 20 (SGD), 36 (amsgrad) and 28 (Adam) bytes per parameter, 4 more for the norm.
+//
+// K35 -- fp16 loss scaling in the same launches, for all four kinds: the norm pass squares g / scale, the reduce decides what
+// torch.amp.GradScaler decides on the host (found_inf, the skipped step, the new scale and growth tracker) and leaves the gradient
+// multiplier (1 / scale) * clip coefficient for the update, which returns at once on a skipped step.  As K11 leaves the gradients
+// unscaled (= unclipped) in memory, K35 leaves them SCALED and unclipped: torch's unscale_ rewrites every one of them, here no byte
+// more than K11 / K34 move.  The unscaled kernels are the SCALED = false instantiations and compute what they always did.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,8 +44,15 @@ struct TensorRow {                    // mirrors the int64 x 5 rows of the host 
     long long n;
 };
 
+// 1 / scale as torch.amp.GradScaler forms it (_scale.double().reciprocal().float())
+__device__ __forceinline__ float inv_scale_of(const float *__restrict__ scale) { return (float)(1.0 / (double)*scale); }
+
+// SCALED (K35): the gradients carry the loss scale *scale; the sum is that of the UNSCALED gradients (g / scale)^2, the norm the
+// reference clips on (unscale_ comes before clip_grad_norm_).  An inf or NaN element, or a square beyond fp32, makes the partial non-finite.
+template <bool SCALED>
 __global__ void __launch_bounds__(OPT_TPB)
-adamw_sumsq_kernel(const TensorRow *__restrict__ table, const int2 *__restrict__ work, double *__restrict__ sumsq)
+adamw_sumsq_kernel(const TensorRow *__restrict__ table, const int2 *__restrict__ work, double *__restrict__ sumsq,
+                   const float *__restrict__ scale)
 {
     __shared__ float red[OPT_TPB / 64];
     const int2 w = work[blockIdx.x];
@@ -48,7 +61,26 @@ adamw_sumsq_kernel(const TensorRow *__restrict__ table, const int2 *__restrict__
     const float *g = t.g + lo;
     const long long n = hi - lo;
     float s = 0.f;
-    if ((((uintptr_t)g) & 15) == 0) {
+    if (SCALED) {
+        const float inv = inv_scale_of(scale);
+        if ((((uintptr_t)g) & 15) == 0) {
+            const long long n4 = n >> 2;
+            for (long long i = threadIdx.x; i < n4; i += OPT_TPB) {
+                float4 a = reinterpret_cast<const float4 *>(g)[i];
+                a.x *= inv, a.y *= inv, a.z *= inv, a.w *= inv;
+                s += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
+            }
+            for (long long i = 4 * n4 + threadIdx.x; i < n; i += OPT_TPB) {
+                const float a = g[i] * inv;
+                s += a * a;
+            }
+        } else {
+            for (long long i = threadIdx.x; i < n; i += OPT_TPB) {
+                const float a = g[i] * inv;
+                s += a * a;
+            }
+        }
+    } else if ((((uintptr_t)g) & 15) == 0) {
         const long long n4 = n >> 2;
         for (long long i = threadIdx.x; i < n4; i += OPT_TPB) {
             const float4 a = reinterpret_cast<const float4 *>(g)[i];
@@ -89,13 +121,63 @@ struct AdamArgs {
 };
 
 // min(1, max_norm / (norm + 1e-6)) from the squared norm the reduce kernel left in *sumsq; 1 without clipping
-__device__ __forceinline__ float clip_coef(float max_norm, const double *__restrict__ sumsq)
+__device__ __forceinline__ float clip_coef_of(float max_norm, double total)
 {
     if (!(max_norm > 0.f)) return 1.f;
-    const float norm = (float)sqrt(*sumsq);
+    const float norm = (float)sqrt(total);
     // a non-finite norm poisons EVERY parameter, as clip_grad_norm_'s NaN coefficient does (fminf(NaN, 1) = 1 would
     // keep stepping the finite gradients and hide the failure)
     return (norm == norm && norm < __builtin_huge_valf()) ? fminf(max_norm / (norm + 1e-6f), 1.f) : __builtin_nanf("");
+}
+
+__device__ __forceinline__ float clip_coef(float max_norm, const double *__restrict__ sumsq) { return clip_coef_of(max_norm, *sumsq); }
+
+// K35 -- the reduce of the loss-scaled step: the same fixed-order total (of the unscaled squares), then, in one thread, everything
+// torch.amp.GradScaler decides on the host between unscale_ and update:
+//   found_inf  1 when the total is not finite (an inf or NaN gradient element; ALSO finite elements whose unscaled square, or a
+//              work item's fp32 sum of such squares, leaves fp32 -- |g / scale|, or the norm of a 64 Ki-element chunk, above
+//              1.8e19 -- where torch would step with a zero coefficient), else 0;
+//   step_dev   advanced on a good step only (torch never calls the optimizer on a skipped one);
+//   grad_mult  (1 / scale) * clip coefficient, formed from the scale the gradients were produced with: what the update kernel
+//              multiplies every gradient by as it reads it;
+//   scale, growth_tracker  torch._amp_update_scale_: backoff and tracker 0 on overflow; else count up and, at growth_interval,
+//              grow if the product is finite and reset the tracker.
+__global__ void __launch_bounds__(OPT_TPB)
+scaled_sumsq_reduce_kernel(double *__restrict__ sumsq, int n_work, int *__restrict__ step_dev, float *__restrict__ scale,
+                           int *__restrict__ growth_tracker, float *__restrict__ found_inf, float *__restrict__ grad_mult,
+                           float max_norm, double growth_factor, double backoff_factor, int growth_interval)
+{
+    __shared__ double red[OPT_TPB];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_work; i += OPT_TPB) s += sumsq[1 + i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = OPT_TPB / 2; off > 0; off >>= 1) {
+        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double total = red[0];
+    sumsq[0] = total;
+    const bool bad = !(total == total) || total >= __builtin_huge_val();
+    const float old_scale = *scale;
+    *found_inf = bad ? 1.f : 0.f;
+    if (bad) {
+        *grad_mult = 0.f;                                 // never read: the update kernel returns on found_inf
+        *scale = (float)((double)old_scale * backoff_factor);
+        *growth_tracker = 0;
+        return;
+    }
+    *step_dev += 1;
+    *grad_mult = (float)(1.0 / (double)old_scale) * clip_coef_of(max_norm, total);
+    const int successful = *growth_tracker + 1;
+    if (successful == growth_interval) {
+        const float grown = (float)((double)old_scale * growth_factor);
+        if (grown == grown && fabsf(grown) < __builtin_huge_valf()) *scale = grown;
+        *growth_tracker = 0;
+    } else {
+        *growth_tracker = successful;
+    }
 }
 
 __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, const AdamArgs &a, float coef)
@@ -108,10 +190,15 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p -= (a.lr / a.bias_c1) * (m / denom);
 }
 
+// SCALED (K35): a skipped step (found_inf set by the reduce) leaves parameters and state untouched; otherwise the gradient multiplier
+// (1 / scale) * clip coefficient stands where the clip coefficient stood.  Gradients stay scaled and unclipped in memory.
+template <bool SCALED>
 __global__ void __launch_bounds__(OPT_TPB)
 adamw_update_kernel(const TensorRow *__restrict__ table, const int2 *__restrict__ work, const double *__restrict__ sumsq,
-                    AdamArgs a, const float *__restrict__ lr_dev, const int *__restrict__ step_dev)
+                    AdamArgs a, const float *__restrict__ lr_dev, const int *__restrict__ step_dev,
+                    const float *__restrict__ found_inf, const float *__restrict__ grad_mult)
 {
+    if (SCALED && *found_inf != 0.f) return;
     if (lr_dev) {
         // learning rate and step live on the device (a captured launch cannot carry them as arguments): the same double-precision
         // bias corrections the host form passes in
@@ -124,7 +211,7 @@ adamw_update_kernel(const TensorRow *__restrict__ table, const int2 *__restrict_
     const TensorRow t = table[w.x];
     const long long lo = (long long)w.y * CHUNK, hi = min(lo + CHUNK, t.n);
     const long long n = hi - lo;
-    const float coef = clip_coef(a.max_norm, sumsq);
+    const float coef = SCALED ? *grad_mult : clip_coef(a.max_norm, sumsq);
     float *p = t.p + lo, *m = t.m + lo, *v = t.v + lo;
     const float *g = t.g + lo;
     const bool al = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
@@ -173,13 +260,14 @@ __device__ __forceinline__ void opt_one(float &p, float g, float &m, float &v, f
     p -= (a.lr / a.bias_c1) * (m / denom);
 }
 
-template <int KIND>
+template <int KIND, bool SCALED>
 __global__ void __launch_bounds__(OPT_TPB)
 opt_update_kernel(const TensorRow *__restrict__ table, float *const *__restrict__ extra, const int2 *__restrict__ work,
                   const double *__restrict__ sumsq, AdamArgs a, double beta1, double beta2, const float *__restrict__ lr_dev,
-                  const int *__restrict__ step_dev)
+                  const int *__restrict__ step_dev, const float *__restrict__ found_inf, const float *__restrict__ grad_mult)
 {
     constexpr bool SGD = KIND == MLAGG_OPT_SGD_NESTEROV, AMS = KIND == MLAGG_OPT_ADAMW_AMSGRAD;
+    if (SCALED && *found_inf != 0.f) return;              // K35: a skipped step writes nothing
     if (lr_dev) {
         a.lr = *lr_dev;
         if (!SGD) {
@@ -194,7 +282,7 @@ opt_update_kernel(const TensorRow *__restrict__ table, float *const *__restrict_
     const TensorRow t = table[w.x];
     const long long lo = (long long)w.y * CHUNK, hi = min(lo + CHUNK, t.n);
     const long long n = hi - lo;
-    const float coef = clip_coef(a.max_norm, sumsq);
+    const float coef = SCALED ? *grad_mult : clip_coef(a.max_norm, sumsq);
     const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
     // a kind reads and writes only the state tensors it has; the others alias m and are never touched
     float *p = t.p + lo, *m = t.m + lo, *v = SGD ? m : t.v + lo, *x = AMS ? extra[w.x] + lo : m;
@@ -226,6 +314,35 @@ opt_update_kernel(const TensorRow *__restrict__ table, float *const *__restrict_
     }
 }
 
+// The state of the loss-scaled step (K35), all device-resident; null `scale`: the unscaled step.
+struct ScaleState {
+    float *scale = nullptr;
+    int *growth_tracker = nullptr;
+    float *found_inf = nullptr, *grad_mult = nullptr;
+    double growth_factor = 2.0, backoff_factor = 0.5;
+    int growth_interval = 2000;
+};
+
+template <bool SCALED>
+void opt_launch_update(int kind, const TensorRow *table, float *const *extra, const int2 *work, int n_work, const double *sumsq,
+                       AdamArgs a, double beta1, double beta2, const float *lr_dev, const int *step, const ScaleState &ss,
+                       hipStream_t st)
+{
+    const float *found = ss.found_inf, *mult = ss.grad_mult;
+    if (kind == MLAGG_OPT_SGD_NESTEROV)
+        hipLaunchKernelGGL((opt_update_kernel<MLAGG_OPT_SGD_NESTEROV, SCALED>), dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work,
+                           sumsq, a, beta1, beta2, lr_dev, step, found, mult);
+    else if (kind == MLAGG_OPT_ADAMW_AMSGRAD)
+        hipLaunchKernelGGL((opt_update_kernel<MLAGG_OPT_ADAMW_AMSGRAD, SCALED>), dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work,
+                           sumsq, a, beta1, beta2, lr_dev, step, found, mult);
+    else if (kind == MLAGG_OPT_ADAM_L2)
+        hipLaunchKernelGGL((opt_update_kernel<MLAGG_OPT_ADAM_L2, SCALED>), dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work, sumsq,
+                           a, beta1, beta2, lr_dev, step, found, mult);
+    else                                                  // MLAGG_OPT_ADAMW: K11's kernel (bias corrections from the float betas)
+        hipLaunchKernelGGL(adamw_update_kernel<SCALED>, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, a, lr_dev, step, found,
+                           mult);
+}
+
 // norm launches (K11's kernels) + the update of `kind`; lr_dev / step_dev null: the launch-argument form
 int opt_launch(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work, double *sumsq,
                AdamArgs a, double beta1, double beta2, const float *lr_dev, int *step_dev, hipStream_t st)
@@ -235,20 +352,27 @@ int opt_launch(int kind, const void *tensor_table, const void *extra_table, cons
     const int2 *work = static_cast<const int2 *>(work_list);
     const bool clip = a.max_norm > 0.f;
     MLAGG_TIMED(K_OPT_VARIANTS, st);
-    if (clip) hipLaunchKernelGGL(adamw_sumsq_kernel, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq);
+    if (clip)
+        hipLaunchKernelGGL(adamw_sumsq_kernel<false>, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, (const float *)nullptr);
     // device form: without clipping the reduce launch still runs (over zero partials) to advance the step counter
     if (clip || step_dev)
         hipLaunchKernelGGL(adamw_sumsq_reduce_kernel, dim3(1), dim3(OPT_TPB), 0, st, sumsq, clip ? n_work : 0, step_dev);
-    const int *step = step_dev;
-    if (kind == MLAGG_OPT_SGD_NESTEROV)
-        hipLaunchKernelGGL(opt_update_kernel<MLAGG_OPT_SGD_NESTEROV>, dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work, sumsq, a,
-                           beta1, beta2, lr_dev, step);
-    else if (kind == MLAGG_OPT_ADAMW_AMSGRAD)
-        hipLaunchKernelGGL(opt_update_kernel<MLAGG_OPT_ADAMW_AMSGRAD>, dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work, sumsq, a,
-                           beta1, beta2, lr_dev, step);
-    else
-        hipLaunchKernelGGL(opt_update_kernel<MLAGG_OPT_ADAM_L2>, dim3(n_work), dim3(OPT_TPB), 0, st, table, extra, work, sumsq, a,
-                           beta1, beta2, lr_dev, step);
+    opt_launch_update<false>(kind, table, extra, work, n_work, sumsq, a, beta1, beta2, lr_dev, step_dev, ScaleState{}, st);
+    return (int)hipGetLastError();
+}
+
+// K35: the loss-scaled step of any kind in the same three launches -- the norm pass always runs (it finds the overflow)
+int scaled_launch(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work, double *sumsq,
+                  AdamArgs a, double beta1, double beta2, const float *lr_dev, int *step_dev, const ScaleState &ss, hipStream_t st)
+{
+    const TensorRow *table = static_cast<const TensorRow *>(tensor_table);
+    float *const *extra = static_cast<float *const *>(extra_table);
+    const int2 *work = static_cast<const int2 *>(work_list);
+    mlagg_prof::Scope mlagg_prof_scope(kind == MLAGG_OPT_ADAMW ? mlagg_prof::K_ADAMW : mlagg_prof::K_OPT_VARIANTS, st);
+    hipLaunchKernelGGL(adamw_sumsq_kernel<true>, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, (const float *)ss.scale);
+    hipLaunchKernelGGL(scaled_sumsq_reduce_kernel, dim3(1), dim3(OPT_TPB), 0, st, sumsq, n_work, step_dev, ss.scale, ss.growth_tracker,
+                       ss.found_inf, ss.grad_mult, a.max_norm, ss.growth_factor, ss.backoff_factor, ss.growth_interval);
+    opt_launch_update<true>(kind, table, extra, work, n_work, sumsq, a, beta1, beta2, lr_dev, step_dev, ss, st);
     return (int)hipGetLastError();
 }
 
@@ -276,11 +400,11 @@ extern "C" int mlagg_adamw_clip_step(const void *tensor_table, const void *work_
     a.bias_c2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     MLAGG_TIMED(K_ADAMW, st);
     if (max_norm > 0.f) {
-        hipLaunchKernelGGL(adamw_sumsq_kernel, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq);
+        hipLaunchKernelGGL(adamw_sumsq_kernel<false>, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, (const float *)nullptr);
         hipLaunchKernelGGL(adamw_sumsq_reduce_kernel, dim3(1), dim3(OPT_TPB), 0, st, sumsq, n_work, (int *)nullptr);
     }
-    hipLaunchKernelGGL(adamw_update_kernel, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, a, (const float *)nullptr,
-                       (const int *)nullptr);
+    hipLaunchKernelGGL(adamw_update_kernel<false>, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, a, (const float *)nullptr,
+                       (const int *)nullptr, (const float *)nullptr, (const float *)nullptr);
     return (int)hipGetLastError();
 }
 
@@ -298,11 +422,12 @@ extern "C" int mlagg_adamw_clip_step_dev(const void *tensor_table, const void *w
     const int2 *work = static_cast<const int2 *>(work_list);
     AdamArgs a{0.f, beta1, beta2, eps, weight_decay, max_norm, 1.f, 1.f};
     MLAGG_TIMED(K_ADAMW, st);
-    if (max_norm > 0.f) hipLaunchKernelGGL(adamw_sumsq_kernel, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq);
+    if (max_norm > 0.f)
+        hipLaunchKernelGGL(adamw_sumsq_kernel<false>, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, (const float *)nullptr);
     // without clipping the reduce launch still runs (over zero partials) to advance the step counter
     hipLaunchKernelGGL(adamw_sumsq_reduce_kernel, dim3(1), dim3(OPT_TPB), 0, st, sumsq, max_norm > 0.f ? n_work : 0, step_dev);
-    hipLaunchKernelGGL(adamw_update_kernel, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, a, lr_dev,
-                       (const int *)step_dev);
+    hipLaunchKernelGGL(adamw_update_kernel<false>, dim3(n_work), dim3(OPT_TPB), 0, st, table, work, sumsq, a, lr_dev,
+                       (const int *)step_dev, (const float *)nullptr, (const float *)nullptr);
     return (int)hipGetLastError();
 }
 
@@ -335,4 +460,25 @@ extern "C" int mlagg_optimizer_clip_step_dev(int kind, const void *tensor_table,
     AdamArgs a{0.f, (float)beta1, (float)beta2, eps, weight_decay, max_norm, 1.f, 1.f};
     return opt_launch(kind, tensor_table, extra_table, work_list, n_work, sumsq, a, beta1, beta2, lr_dev, step_dev,
                       static_cast<hipStream_t>(stream));
+}
+
+// K35 -- fp16 loss scaling fused into the step tail: the clip + update of `kind` (MLAGG_OPT_ADAMW: K11's AdamW; the others K34's) on
+// gradients that carry the loss scale, with everything torch.amp.GradScaler decides between unscale_ and update formed on the device.
+// scale, growth_tracker, found_inf, lr_dev and step_dev are device-resident; grad_mult is one scratch float.  Device form only: the
+// call can be captured into a hipGraph and replayed.
+extern "C" int mlagg_scaled_clip_step_dev(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
+                                          double *sumsq, const float *lr_dev, int *step_dev, float *scale, int *growth_tracker,
+                                          float *found_inf, float *grad_mult, double beta1, double beta2, float eps, float weight_decay,
+                                          float max_norm, double growth_factor, double backoff_factor, int growth_interval,
+                                          void *stream)
+{
+    if (!tensor_table || !work_list || !sumsq || !lr_dev || !step_dev || !scale || !growth_tracker || !found_inf || !grad_mult)
+        return MLAGG_E_NULLPTR;
+    if ((kind != MLAGG_OPT_ADAMW && !opt_kind_ok(kind, extra_table)) || n_work <= 0 || growth_interval < 1) return MLAGG_E_UNSUPPORTED;
+    AdamArgs a{0.f, (float)beta1, (float)beta2, eps, weight_decay, max_norm, 1.f, 1.f};
+    ScaleState ss;
+    ss.scale = scale, ss.growth_tracker = growth_tracker, ss.found_inf = found_inf, ss.grad_mult = grad_mult;
+    ss.growth_factor = growth_factor, ss.backoff_factor = backoff_factor, ss.growth_interval = growth_interval;
+    return scaled_launch(kind, tensor_table, extra_table, work_list, n_work, sumsq, a, beta1, beta2, lr_dev, step_dev, ss,
+                         static_cast<hipStream_t>(stream));
 }

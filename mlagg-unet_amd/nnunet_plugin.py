@@ -12,7 +12,9 @@ What the class overrides, and why the inherited method cannot stay (B = nnUNetTr
                     operands of every Linear and convolution with fp32 sums, i.e. what autocast does to those layers),
                     whatever the ambient autocast state, so the step is ``trainer.train_step`` (zero_grad, forward, loss,
                     backward, clip 12, AdamW).  The ``GradScaler`` of B:152 is kept for "fp16" only (as in the reference,
-                    small gradients would otherwise flush to zero in the 16-bit operands) and dropped otherwise; the
+                    small gradients would otherwise flush to zero in the 16-bit operands) and dropped otherwise;
+                    ``loss_scaling="device"`` replaces it with ``trainer.DeviceGradScaler`` (K35: the scaler's decisions on the
+                    device, inside the optimizer's launches, so that the fp16 step replays as a hipGraph too); the
                     returned dictionary and the per-step host copy of the loss are the reference's (B:863).
   * ``initialize``  B:193-215 wraps with a plain ``DDP(...)``; here ``trainer.wrap_ddp`` (bucket views, no buffer
                     broadcast) and the loss is rebuilt so that it knows about DDP.
@@ -38,7 +40,8 @@ PRECISIONS = ("fp32", "bf16", "fp16")
 # costs its ~30 ms of Python / launch time ON TOP of a part of its GPU time (41.6 against 37.7 ms per step at 256 x 256, batch 10:
 # profiles/round4_e_bench_with_mfma_roofline.json.log).  After GRAPH_AFTER eager steps on one batch geometry the plugin therefore
 # captures the whole step (zero_grad, forward, loss, backward, clip, AdamW: trainer.GraphedTrainStep) and replays it: 38.4 ms with
-# the read-back.  Single-process fp32 / bf16 training only; MLAGG_PLUGIN_GRAPH=0 keeps every step eager.
+# the read-back.  Single-process training: fp32 / bf16, and fp16 with loss_scaling="device" (torch's GradScaler reads found_inf on the
+# host and cannot be captured); MLAGG_PLUGIN_GRAPH=0 keeps every step eager.
 PLUGIN_GRAPH = os.environ.get("MLAGG_PLUGIN_GRAPH", "1") == "1"
 GRAPH_AFTER = 3
 
@@ -77,6 +80,14 @@ def _check_optimizer(optimizer):
         raise RuntimeError(f"optimizer {optimizer!r}: None (the class's own recipe) or one of {trainer.OPTIMIZERS[1:]}")
 
 
+LOSS_SCALINGS = ("torch", "device")
+
+
+def _check_loss_scaling(loss_scaling):
+    if loss_scaling not in LOSS_SCALINGS:
+        raise RuntimeError(f"loss_scaling {loss_scaling!r}: one of {LOSS_SCALINGS}")
+
+
 def _variant_optimizers(self, optimizer, capturable):
     """``configure_optimizers`` of a class built with ``optimizer=``: the fused optimizer of that recipe (K34) plus PolyLR over the
     trainer's ``num_epochs``; ``initial_lr`` and ``weight_decay`` are the trainer's (the base trainer's 1e-2 / 3e-5 unless a class set them)."""
@@ -103,7 +114,7 @@ def _variant_loss(variant, label_manager, batch_dice, ddp, ignore_label):
     return loss
 
 
-def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAULT_LOSS, optimizer=None):
+def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAULT_LOSS, optimizer=None, loss_scaling="torch"):
     """loss: "dice_ce" (the reference trainer's DC_and_CE_loss / DC_and_BCE_loss) or one of ``trainer.LOSS_VARIANTS`` -- the loss of
     the reference's nnUNetTrainerTopk10Loss ("topk10"), ...Topk10LossLS01 ("topk10_ls01"), ...DiceTopK10Loss ("dice_topk10"),
     ...DiceLoss ("dice"), ...CELoss ("ce") or ...DiceCELoss_noSmooth ("dice_ce_nosmooth").  Every one of them is device-fused, so the
@@ -111,11 +122,16 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
     optimizer: None (the reference trainer's AdamW + cosine schedule on K11) or the recipe of one of the reference's other trainers on
     K34 with PolyLR: "sgd" (the base trainer's SGD, Nesterov momentum 0.99), "adam" (nnUNetTrainerAdam: AdamW with amsgrad),
     "vanilla_adam" (nnUNetTrainerVanillaAdam: Adam with L2 decay); ``initial_lr`` is then the base trainer's 1e-2.  Every one of them
-    keeps its learning rate on the device, so the step replays as a hipGraph too; the choice is kept in ``mlagg_optimizer``."""
+    keeps its learning rate on the device, so the step replays as a hipGraph too; the choice is kept in ``mlagg_optimizer``.
+    loss_scaling: who scales the loss of ``precision="fp16"`` (the other precisions do not scale it).  "torch" (the default): the
+    ``torch.amp.GradScaler`` of B:152, eager steps.  "device": ``trainer.DeviceGradScaler`` (K35) with a capturable optimizer -- no host
+    synchronisation, no rewrite of the gradients, and the step replays as a hipGraph like every other precision's.  Checkpoints carry
+    ``grad_scaler_state`` with torch's keys either way and load into either.  Kept in ``mlagg_loss_scaling``."""
     if precision not in PRECISIONS:
         raise RuntimeError(f"precision {precision!r}: this build of the MI355X path offers {PRECISIONS}")
     _check_loss(loss)
     _check_optimizer(optimizer)
+    _check_loss_scaling(loss_scaling)
     loss_variant = loss
 
     class nnUNetTrainer_MLAgg_2D_dt_MS(nnUNetTrainer):
@@ -134,7 +150,10 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
             # then carry ``grad_scaler_state: None`` exactly as the reference's CPU runs do (B:1018, 1047-1049).
             if precision != "fp16":
                 self.grad_scaler = None
+            elif loss_scaling == "device" and self.device.type == "cuda":
+                self.grad_scaler = trainer.DeviceGradScaler(self.device)            # K35: GradScaler's defaults, decided on the device
             self.mlagg_precision = precision
+            self.mlagg_loss_scaling = loss_scaling
             self.mlagg_loss_variant = loss_variant                                  # for logs and checkpoints
             self.mlagg_optimizer = optimizer
             self._graphed, self._graph_key, self._graph_eager, self._graph_failed = None, None, 0, None
@@ -188,16 +207,21 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
             return loss
 
         def _graph_ok(self):
-            """The step may be replayed as a hipGraph: one process, no GradScaler, the fused device loss, a device network."""
+            """The step may be replayed as a hipGraph: one process, no torch GradScaler (its step reads found_inf on the host; a
+            DeviceGradScaler is captured with the step), the fused device loss, a device network."""
             lm = self.label_manager
-            return bool(PLUGIN_GRAPH and self._graph_failed is None and not self.is_ddp and self.grad_scaler is None
+            scaler_ok = self.grad_scaler is None or isinstance(self.grad_scaler, trainer.DeviceGradScaler)
+            return bool(PLUGIN_GRAPH and self._graph_failed is None and not self.is_ddp and scaler_ok
                         and self.device.type == "cuda" and (not getattr(lm, "has_regions", False) or _describes_regions(lm)))
 
         def configure_optimizers(self):                                             # reference T:137-147
-            # capturable: learning rate and step counter live on the device, so the same optimizer serves eager and replayed steps
+            # capturable: learning rate and step counter live on the device, so the same optimizer serves eager and replayed steps.  A
+            # DeviceGradScaler needs that form whether or not the step is replayed (MLAGG_PLUGIN_GRAPH=0, DDP, a region dataset the
+            # fused loss does not describe): only the device step counter can leave a skipped step uncounted without a synchronisation
+            capturable = self._graph_ok() or isinstance(self.grad_scaler, trainer.DeviceGradScaler)
             if optimizer is not None:
-                return _variant_optimizers(self, optimizer, self._graph_ok())
-            return trainer.configure_optimizers(self.network, self.initial_lr, self.weight_decay, capturable=self._graph_ok())
+                return _variant_optimizers(self, optimizer, capturable)
+            return trainer.configure_optimizers(self.network, self.initial_lr, self.weight_decay, capturable=capturable)
 
         def _to_device(self, batch):                                                # reference B:834-841
             data = batch["data"].to(self.device, non_blocking=True)
@@ -223,7 +247,7 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
                             # warmup=0: the eager steps above were the warm-up; the capture itself executes nothing, so the first
                             # replay IS this step (no batch is trained on twice)
                             self._graphed = trainer.GraphedTrainStep(self.network, self.optimizer, data, target, clip=12.0,
-                                                                     warmup=0, loss_fn=self.loss)
+                                                                     warmup=0, loss_fn=self.loss, grad_scaler=self.grad_scaler)
                             return {"loss": self._graphed().cpu().numpy()}
                         except Exception as e:                                      # noqa: BLE001  (stay eager, say why once)
                             self._graphed, self._graph_failed = None, repr(e)
@@ -253,7 +277,7 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
     return nnUNetTrainer_MLAgg_2D_dt_MS
 
 
-def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimizer=None):
+def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimizer=None, loss_scaling="torch"):
     """``nnUNetTrainerUMambaEnc_SS3D`` (reference variants/mamba/nnUNetTrainerUMambaEnc_SS3D.py:8-31) on the MI355X 3-D network
     (model3d.UMambaEnc; BASELINE configs[3]).  The reference class overrides ``build_network_architecture`` only and inherits the
     base trainer's recipe (SGD momentum 0.99 Nesterov + PolyLR, nnUNetTrainer.py:448-452; DC_and_CE deep-supervision loss,
@@ -262,10 +286,13 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimiz
     loss: as in ``make_trainer_class``.
     optimizer: None inherits the host trainer's ``configure_optimizers`` (torch.optim.SGD behind clip_grad_norm_); "sgd" is the same
     recipe with the clip and the update fused on the device (K34: ClipSGD + PolyLR), i.e. the reference's class with its step tail on
-    the MI355X; "adam" / "vanilla_adam" as in ``make_trainer_class``.  The 3-D step stays eager.  Kept in ``mlagg_optimizer``."""
+    the MI355X; "adam" / "vanilla_adam" as in ``make_trainer_class``.  The 3-D step stays eager.  Kept in ``mlagg_optimizer``.
+    loss_scaling: as in ``make_trainer_class``; the 3-D network computes in fp32 and scales no loss, so the choice is checked, kept in
+    ``mlagg_loss_scaling`` and has no further effect."""
     from . import model3d
     _check_loss(loss)
     _check_optimizer(optimizer)
+    _check_loss_scaling(loss_scaling)
     loss_variant = loss
 
     class nnUNetTrainerUMambaEnc_SS3D(nnUNetTrainer):
@@ -275,6 +302,7 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimiz
             self.grad_scaler = None                                                  # fp32 step: no loss scaling (B:152)
             self.mlagg_loss_variant = loss_variant                                   # for logs and checkpoints
             self.mlagg_optimizer = optimizer
+            self.mlagg_loss_scaling = loss_scaling
             miopen_tuning.use_tuned_convolutions(enabled=False)                      # no committed records for 3-D convolutions
 
         @staticmethod

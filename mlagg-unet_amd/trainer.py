@@ -471,15 +471,37 @@ class ClipOptimizer(torch.optim.Optimizer):
         ``_steps`` as launch arguments."""
         raise NotImplementedError
 
-    @torch.no_grad()
-    def step(self, closure=None, max_norm=0.0):
+    def _scaled_hyper(self, group):
+        """(kind constant of the header, beta1 or momentum, beta2, eps) of the group for the loss-scaled step (K35)."""
+        raise NotImplementedError
+
+    def _launch_scaled(self, group, table, extra, work, max_norm, scaler):
+        """The loss-scaled step (K35) of ``DeviceGradScaler.step``: the device form alone, with the scaler's device state."""
         from . import _lib
+        kind, b1, b2, eps = self._scaled_hyper(group)
+        _lib.launch("mlagg_scaled_clip_step_dev", _lib.CONSTANTS[kind], table.data_ptr(), extra.data_ptr() if extra is not None else None,
+                    work.data_ptr(), work.shape[0], self._sumsq.data_ptr(), self._lr_dev.data_ptr(), self._step_dev.data_ptr(),
+                    scaler._scale.data_ptr(), scaler._growth_tracker.data_ptr(), scaler.found_inf.data_ptr(), scaler._mult.data_ptr(),
+                    b1, b2, eps, float(group["weight_decay"]), max_norm, scaler.growth_factor, scaler.backoff_factor,
+                    scaler.growth_interval)
+
+    @torch.no_grad()
+    def step(self, closure=None, max_norm=0.0, _grad_scaler=None):
+        """``_grad_scaler`` is private to ``DeviceGradScaler.step``, which passes itself: the loss-scaled step of K35 on gradients that
+        carry its scale, capturable form only.  The scaler checks the device and keeps the one-optimizer-per-iteration bookkeeping;
+        nobody else passes the argument."""
+        from . import _lib
+        grad_scaler = _grad_scaler
+        if grad_scaler is not None and not self.capturable:
+            raise RuntimeError(f"{type(self).__name__}: DeviceGradScaler needs capturable=True (a skipped step can be left uncounted "
+                               "without a host synchronisation only in the device-resident step counter)")
         chunk = _lib.lib().mlagg_adamw_chunk_elements()
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        self._steps += 1
+        if grad_scaler is None:
+            self._steps += 1                          # (the scaled step counts on the device, and only the applied steps)
         from . import ops
         ops.invalidate_weight_images()                # the kernels below rewrite the parameters through raw pointers: no version bump
         name = self._name
@@ -551,7 +573,10 @@ class ClipOptimizer(torch.optim.Optimizer):
                     table.copy_(pinned, non_blocking=True)
                 if not capturing:
                     self.sync_lr()
-                self._launch(group, *self._rows_and_third(table, T), work, float(max_norm), True)
+                if grad_scaler is not None:
+                    self._launch_scaled(group, *self._rows_and_third(table, T), work, float(max_norm), grad_scaler)
+                else:
+                    self._launch(group, *self._rows_and_third(table, T), work, float(max_norm), True)
                 continue
             table = host.pin_memory().to(dev, non_blocking=True)
             self._launch(group, *self._rows_and_third(table, T), work, float(max_norm), False)
@@ -572,6 +597,10 @@ class ClipAdamW(ClipOptimizer):
     def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-4, weight_decay=3e-5, capturable=False):
         super().__init__(params, dict(lr=float(lr), betas=betas, eps=eps, weight_decay=weight_decay), capturable)
 
+    def _scaled_hyper(self, group):
+        b1, b2 = group["betas"]
+        return "MLAGG_OPT_ADAMW", float(b1), float(b2), float(group["eps"])
+
     def _launch(self, group, table, extra, work, max_norm, device_form):
         from . import _lib
         b1, b2 = group["betas"]
@@ -591,6 +620,9 @@ class _ClipVariant(ClipOptimizer):
     def _hyper(self, group):
         """(beta1 or momentum, beta2, eps) of the group as the kernel takes them."""
         raise NotImplementedError
+
+    def _scaled_hyper(self, group):
+        return (self._KIND,) + tuple(self._hyper(group))
 
     def _launch(self, group, table, extra, work, max_norm, device_form):
         from . import _lib
@@ -674,6 +706,109 @@ class ClipAdam(_ClipVariant):
     def _hyper(self, group):
         b1, b2 = group["betas"]
         return float(b1), float(b2), float(group["eps"])
+
+
+class DeviceGradScaler:
+    """``torch.amp.GradScaler`` of the reference's fp16 step (nnUNetTrainer.py:152, :848-858) with its decisions on the device (K35):
+    the scale, the growth tracker and ``found_inf`` are device tensors, and ``step`` with a capturable ``ClipOptimizer`` is that
+    optimizer's three launches -- the norm of the unscaled gradients, the overflow test, the skipped or applied step, the new scale --
+    with no host synchronisation (``GradScaler.step`` reads ``found_inf.item()``), no rewrite of the gradients (``unscale_``; they stay
+    scaled and unclipped in memory) and nothing a hipGraph capture cannot record.  One deviation from torch: finite gradients whose
+    unscaled square -- or a 64 Ki-element chunk's fp32 sum of squares -- leaves fp32 (|g / scale| or the chunk norm > 1.8e19) count as an overflow and skip the step; torch would step with a zero coefficient.
+
+    ``step`` does the update of the scale as well; ``update`` is kept for the reference's call shape and closes the iteration: one
+    optimizer per iteration.  With a ``ClipOptimizer`` it requires ``capturable=True``: the device step counter is the only place a
+    skipped step can be left uncounted without a synchronisation, and ``steps_done()`` then counts the applied steps.  A plain torch
+    optimizer (the one ``configure_optimizers`` gives host parameters) takes the same decisions through torch ops (unscale, norm, skip,
+    ``torch._amp_update_scale_``), with torch's synchronisation; a ``ClipOptimizer`` over host parameters is refused, its kernels
+    have no host form.  ``state_dict`` / ``load_state_dict`` carry ``torch.amp.GradScaler``'s keys, so a checkpoint's
+    ``grad_scaler_state`` loads into either class; loading writes into the existing device tensors (a captured graph holds their
+    addresses)."""
+
+    def __init__(self, device, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        if not growth_factor > 1.0:
+            raise RuntimeError("DeviceGradScaler: growth_factor must be > 1")
+        if not 0.0 < backoff_factor < 1.0:
+            raise RuntimeError("DeviceGradScaler: backoff_factor must be in (0, 1)")
+        if int(growth_interval) < 1:
+            raise RuntimeError("DeviceGradScaler: growth_interval must be at least 1")
+        self.device = torch.device(device)
+        self.growth_factor, self.backoff_factor = float(growth_factor), float(backoff_factor)
+        self.growth_interval = int(growth_interval)
+        self._scale = torch.full((1,), float(init_scale), dtype=torch.float32, device=self.device)
+        self._growth_tracker = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.found_inf = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._mult = torch.zeros(1, dtype=torch.float32, device=self.device)      # scratch: (1 / scale) * clip coefficient
+        self._open = False                                                         # a step since the last update()
+
+    def scale(self, loss):
+        return loss * self._scale.reshape(())
+
+    def get_scale(self):
+        """The scale as a Python float (synchronises)."""
+        return float(self._scale.item())
+
+    def get_growth_tracker(self):
+        return int(self._growth_tracker.item())
+
+    def is_enabled(self):
+        return True
+
+    @torch.no_grad()
+    def step(self, optimizer, max_norm=0.0):
+        """Unscale, clip to ``max_norm`` (<= 0: no clipping), step unless a gradient overflowed, update the scale."""
+        if self._open:
+            raise RuntimeError("DeviceGradScaler: one optimizer per iteration (step() already ran since the last update())")
+        params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
+        if isinstance(optimizer, ClipOptimizer):
+            if not all(p.is_cuda for p in params):
+                raise RuntimeError(f"DeviceGradScaler: {type(optimizer).__name__} has no host form; host parameters take the torch "
+                                   "optimizer of the recipe (configure_optimizers returns it for a host model)")
+            if not optimizer.capturable:
+                raise RuntimeError(f"DeviceGradScaler: {type(optimizer).__name__} must be built with capturable=True (the device step "
+                                   "counter is the only place a skipped step can be left uncounted without a synchronisation)")
+            if any(p.device != self._scale.device for p in params):
+                raise RuntimeError("DeviceGradScaler: the parameters live on another device than the scale")
+            optimizer.step(max_norm=max_norm, _grad_scaler=self)
+            self._open = True
+            return None
+        # a plain torch optimizer (host or device parameters): the same decisions through torch ops, as torch orders them
+        inv = self._scale.double().reciprocal().float()
+        total = torch.zeros((), dtype=torch.float64, device=self._scale.device)
+        for p in params:
+            p.grad.mul_(inv.to(p.grad.device).reshape(()))                         # unscale_: rewrites the gradients
+            total += p.grad.float().pow(2).sum().double().to(total.device)
+        bad = not bool(torch.isfinite(total))                                      # synchronises, as GradScaler.step does
+        self.found_inf.fill_(1.0 if bad else 0.0)
+        out = None
+        if not bad:
+            if max_norm > 0:
+                coef = torch.clamp(max_norm / (total.sqrt().float() + 1e-6), max=1.0)
+                for p in params:
+                    p.grad.mul_(coef.to(p.grad.device))
+            out = optimizer.step()
+        torch._amp_update_scale_(self._scale, self._growth_tracker, self.found_inf, self.growth_factor, self.backoff_factor,
+                                 self.growth_interval)
+        self._open = True
+        return out
+
+    def update(self):
+        """Closes the iteration; the scale was updated by ``step`` already (on the device, behind the overflow test)."""
+        self._open = False
+
+    def state_dict(self):
+        return {"scale": self.get_scale(), "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": self.get_growth_tracker()}
+
+    def load_state_dict(self, state_dict):
+        """The scale and the tracker go into the existing device tensors.  The two factors and the interval are launch arguments: a
+        step captured before the load keeps the ones it was captured with."""
+        if len(state_dict) == 0:
+            raise RuntimeError("DeviceGradScaler: the source state dict is empty, possibly because it was saved from a disabled GradScaler")
+        self._scale.fill_(float(state_dict["scale"]))                              # in place: a captured graph holds the addresses
+        self._growth_tracker.fill_(int(state_dict["_growth_tracker"]))
+        self.growth_factor, self.backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self.growth_interval = int(state_dict["growth_interval"])
 
 
 OPTIMIZERS = ("adamw", "sgd", "adam", "vanilla_adam")
@@ -938,10 +1073,19 @@ def train_step(network, optimizer, data, target: List[torch.Tensor], batch_dice=
     decides when to synchronise -- the reference's ``.cpu()`` per step, B:863, is a host sync).
     ``loss_fn(output, target)`` replaces the Dice + CE deep-supervision loss (the trainer plugin passes ``self.loss``).
     ``grad_scaler``: the reference's fp16 branch (B:853-858): scaled backward, unscale, clip, step, update -- for networks
-    built with ``precision="fp16"``, whose 16-bit GEMM operands would flush small gradients to zero unscaled."""
+    built with ``precision="fp16"``, whose 16-bit GEMM operands would flush small gradients to zero unscaled.  A
+    ``torch.amp.GradScaler`` takes torch's path (``found_inf.item()`` on the host); a ``DeviceGradScaler`` the fused one (K35): scaled
+    backward, then unscale, clip, skip-or-step and the new scale in the optimizer's own launches.  Under DDP every rank sees the
+    same reduced gradients and so takes the same decision."""
     optimizer.zero_grad(set_to_none=True)
     output = network(data)
     loss = deep_supervision_loss(output, target, batch_dice, ddp) if loss_fn is None else loss_fn(output, target)
+    if isinstance(grad_scaler, DeviceGradScaler):
+        grad_scaler.scale(loss).backward()
+        finish_grad_sync(network)
+        grad_scaler.step(optimizer, max_norm=clip)
+        grad_scaler.update()
+        return loss.detach()
     if grad_scaler is not None:
         grad_scaler.scale(loss).backward()
         finish_grad_sync(network)
@@ -974,15 +1118,21 @@ class GraphedTrainStep:
     profiles/round3_ddp_graph_capture_segfault.log), so a DistributedDataParallel network is refused here.
     One captured step per optimizer: the graph reads ClipAdamW's pointer table for captured steps, and a second capture whose
     gradients sit at other addresses would redirect the first graph's update, so ClipAdamW refuses it.  Eager ``train_step``
-    calls with the same optimizer may be mixed with replays freely."""
+    calls with the same optimizer may be mixed with replays freely.
+    ``grad_scaler``: a ``DeviceGradScaler`` -- the fp16 step with loss scaling (K35) is captured whole; its scale, growth tracker and
+    the optimizer's step counter advance inside the replays."""
 
-    def __init__(self, network, optimizer, data, target, batch_dice=True, clip=12.0, warmup=3, loss_fn=None):
+    def __init__(self, network, optimizer, data, target, batch_dice=True, clip=12.0, warmup=3, loss_fn=None, grad_scaler=None):
+        if grad_scaler is not None and not isinstance(grad_scaler, DeviceGradScaler):
+            raise RuntimeError("GraphedTrainStep: only a DeviceGradScaler can be captured (torch.amp.GradScaler.step reads found_inf "
+                               "on the host)")
         if isinstance(network, torch.nn.parallel.DistributedDataParallel) or getattr(network, "_mlagg_grad_sync", None) is not None:
             raise RuntimeError("GraphedTrainStep: a DistributedDataParallel network cannot be captured on this build "
                                "(segmentation fault inside the capture); run the data-parallel step eagerly")
         self.data = data.clone()
         self.target = [t.clone() for t in target]
-        body = lambda: train_step(network, optimizer, self.data, self.target, batch_dice, False, clip, loss_fn=loss_fn)  # noqa: E731
+        body = lambda: train_step(network, optimizer, self.data, self.target, batch_dice, False, clip, loss_fn=loss_fn,  # noqa: E731
+                                  grad_scaler=grad_scaler)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
