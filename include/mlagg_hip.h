@@ -733,60 +733,42 @@ int mlagg_linear_x3(const float *x, int x_stride, const void *w_image, const flo
                     const float *pre, int pre_stride, int M, int N, int K, int epilogue, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * K11: clip_grad_norm_ + AdamW.step() of the train step (nnUNetTrainer.py:855-857; optimizer of
- * nnUNetTrainer_MLAgg_2D_dt_MS.py:137-147) for every parameter in two launches.
- * tensor_table: device array of rows {param*, grad*, exp_avg*, exp_avg_sq*, int64 numel} (5 x 8 bytes each);
- * work_list: device array of int32 pairs (tensor index, chunk index), one per mlagg_adamw_chunk_elements() elements;
+ * K11 / K34 / K35: clip_grad_norm_(parameters, 12) + optimizer.step() of the train step (nnUNetTrainer.py:855-857) for every
+ * parameter in three launches: sum of squares per work item, their fixed-order total, update.
+ * tensor_table: device array of rows {param*, grad*, state0*, state1*, int64 numel} (5 x 8 bytes each): state0 is exp_avg or
+ * SGD's momentum_buffer, state1 exp_avg_sq (not read by SGD: may be null).  extra_table: device array of one pointer per table row,
+ * the third state tensor max_exp_avg_sq of ADAMW_AMSGRAD; not read by the other kinds (may be null).
+ * work_list: device array of int32 pairs (tensor index, chunk index), one per mlagg_adamw_chunk_elements() elements.  The float4
+ * path is taken by a work item whose param, grad and state pointers (those its kind has) are all 16-byte aligned.
  * sumsq: 1 + n_work device doubles (scratch: [0] the squared global norm, then one partial per work item, summed in a fixed
- * order: bit-reproducible).  max_norm > 0: gradients are scaled by min(1, max_norm / (||g||_2 + 1e-6)) as they are
+ * order: bit-reproducible).  max_norm > 0: gradients are scaled by coef = min(1, max_norm / (||g||_2 + 1e-6)) as they are
  * read (the global norm is formed on the device; no host synchronisation; gradients in memory stay unscaled); <= 0: no clipping.
- * step: 1-based step count for the bias corrections.  Arithmetic of torch.optim.AdamW (decoupled decay, amsgrad off).
- * ------------------------------------------------------------------------------------------ */
-int mlagg_adamw_chunk_elements(void);
-int mlagg_adamw_clip_step(const void *tensor_table, const void *work_list, int n_work, double *sumsq, float lr, float beta1,
-                          float beta2, float eps, float weight_decay, float max_norm, int step, void *stream);
-/* The same step for a hipGraph capture of the whole train step (B:833-863 replayed as one graph): nothing that changes between steps
- * is a launch argument.  lr_dev: one device float (the cosine schedule writes it between replays, B:825); step_dev: one device int32,
- * advanced by this call before the bias corrections read it.  With max_norm <= 0 the norm pass is skipped, the counter still moves. */
-int mlagg_adamw_clip_step_dev(const void *tensor_table, const void *work_list, int n_work, double *sumsq, const float *lr_dev,
-                              int *step_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm, void *stream);
-
-/* ------------------------------------------------------------------------------------------
- * K34: clip_grad_norm_ + the step of the OTHER optimizers of the reference's trainers, for every parameter in two launches (three
- * with the norm's fixed-order reduce).  Replaces clip_grad_norm_(parameters, 12) + optimizer.step() (nnUNetTrainer.py:855-857) with
+ * kind:
  *   MLAGG_OPT_SGD_NESTEROV   torch.optim.SGD(momentum, nesterov=True, dampening 0, L2 weight decay): the base trainer's optimizer
- *                            (nnUNetTrainer.py:448-452).  g = coef g + wd p; buf = momentum buf + g; p -= lr (g + momentum buf); a
- *                            zero buffer gives torch's first step (buf = g).  beta1 carries the momentum; beta2, eps, step unused.
- *   MLAGG_OPT_ADAMW_AMSGRAD  torch.optim.AdamW(amsgrad=True) of nnUNetTrainerAdam (variants/optimizer/nnUNetTrainerAdam.py):
- *                            decoupled decay, moments and double-precision bias corrections as K11; vmax = max(vmax, v);
- *                            denom = sqrt(vmax) / sqrt(bias_c2) + eps.
- *   MLAGG_OPT_ADAM_L2        torch.optim.Adam of nnUNetTrainerVanillaAdam: g = coef g + wd p before the moments, no decoupled decay.
- * tensor_table, work_list, sumsq, max_norm: K11's, with the SAME 5 x 8-byte rows {param*, grad*, state0*, state1*, int64 numel}:
- * state0 is momentum_buffer (SGD) or exp_avg, state1 exp_avg_sq (not read by SGD: may be null).  extra_table: device array of one
- * pointer per table row, the third state tensor max_exp_avg_sq of ADAMW_AMSGRAD; not read by the other kinds (may be null).  The
- * float4 path is taken by a work item whose param, grad and state pointers (those its kind has) are all 16-byte aligned.
- * beta1, beta2 are doubles: the bias corrections 1 - beta^step are formed from them in double, as torch does (K11 forms them from the
- * float values; beta2 = 0.999 rounded to float is 1.3e-8 off, its 1000th power 1.3e-5, which a learning rate of 1e-2 carries into the
- * parameters); the moment updates use beta and 1 - beta each rounded to float from the double, the weights torch hands to its kernels.
- * The _dev form is for a hipGraph capture: lr_dev one device float, step_dev one device int32 advanced by the call for every kind
- * (SGD does not read it: it counts the steps that replays have taken).
- * ------------------------------------------------------------------------------------------ */
-#define MLAGG_OPT_SGD_NESTEROV 0
-#define MLAGG_OPT_ADAMW_AMSGRAD 1
-#define MLAGG_OPT_ADAM_L2 2
-int mlagg_optimizer_clip_step(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
-                              double *sumsq, float lr, double beta1, double beta2, float eps, float weight_decay, float max_norm, int step,
-                              void *stream);
-int mlagg_optimizer_clip_step_dev(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
-                                  double *sumsq, const float *lr_dev, int *step_dev, double beta1, double beta2, float eps,
-                                  float weight_decay, float max_norm, void *stream);
-
-/* ------------------------------------------------------------------------------------------
- * K35: fp16 loss scaling (torch.amp.GradScaler of the reference's default train step, nnUNetTrainer.py:152, :848-858: scaled
- * backward, unscale_, clip_grad_norm_ 12, step, update) fused into the same three launches of K11 / K34, with nothing decided on the
- * host.  kind: MLAGG_OPT_ADAMW (K11's AdamW, bias corrections from the betas rounded to float, as K11 forms them) or one of K34's
- * kinds.  tensor_table, extra_table, work_list, sumsq, lr_dev, step_dev, betas, eps, weight_decay, max_norm: as in
- * mlagg_optimizer_clip_step_dev.  The gradients of the table carry the loss scale.  Device-resident state, one element each:
+ *                            (nnUNetTrainer.py:448-452; K34).  g = coef g + wd p; buf = momentum buf + g; p -= lr (g + momentum buf);
+ *                            a zero buffer gives torch's first step (buf = g).  beta1 carries the momentum; beta2, eps, step unused.
+ *   MLAGG_OPT_ADAMW_AMSGRAD  torch.optim.AdamW(amsgrad=True) of nnUNetTrainerAdam (variants/optimizer/nnUNetTrainerAdam.py; K34):
+ *                            decoupled decay; vmax = max(vmax, v); denom = sqrt(vmax) / sqrt(bias_c2) + eps.
+ *   MLAGG_OPT_ADAM_L2        torch.optim.Adam of nnUNetTrainerVanillaAdam (K34): g = coef g + wd p before the moments, no decoupled
+ *                            decay.
+ *   MLAGG_OPT_ADAMW          torch.optim.AdamW, amsgrad off, of nnUNetTrainer_MLAgg_2D_dt_MS.py:137-147 (K11): decoupled decay;
+ *                            extra_table is not read.
+ * beta1, beta2 are doubles.  ADAMW rounds them to float first and forms everything from the float values: the moment weights beta and
+ * 1.f - beta, the bias corrections 1 - pow((double)(float)beta, step).  ADAMW_AMSGRAD and ADAM_L2 form the bias corrections
+ * 1 - beta^step from the doubles, as torch does (beta2 = 0.999 rounded to float is 1.3e-8 off, its 1000th power 1.3e-5, which a
+ * learning rate of 1e-2 carries into the parameters), and use beta and 1 - beta each rounded to float from the double in the moment
+ * updates, the weights torch hands to its kernels.
+ * mlagg_optimizer_clip_step is the launch-argument form: step is the 1-based step count for the bias corrections (>= 1 for the Adam
+ * kinds; ignored by SGD).  mlagg_optimizer_clip_step_dev is the form for a hipGraph capture of the whole train step (B:833-863
+ * replayed as one graph): nothing that changes between steps is a launch argument.  lr_dev: one device float (the schedule writes it
+ * between replays, B:825); step_dev: one device int32, advanced by the call for every kind before the bias corrections read it (SGD
+ * does not read it: it counts the steps that replays have taken).  With max_norm <= 0 the norm pass is skipped, the counter still
+ * moves.
+ *
+ * mlagg_scaled_clip_step_dev (K35) is the device form with fp16 loss scaling (torch.amp.GradScaler of the reference's default train
+ * step, nnUNetTrainer.py:152, :848-858: scaled backward, unscale_, clip_grad_norm_ 12, step, update) fused into the same three
+ * launches, for every kind, with nothing decided on the host.  The gradients of the table carry the loss scale.  Device-resident
+ * state, one element each:
  *   scale (float), growth_tracker (int32), found_inf (float, 0 or 1 as torch keeps it); grad_mult: one scratch float.
  * 1. sum of squares of the UNSCALED gradients, (g * inv)^2 with inv = (float)(1.0 / (double)scale): the norm the reference clips on;
  * 2. reduce (fixed order): found_inf = the total is not finite -- any inf / NaN element, and (the one deviation from torch, which
@@ -796,10 +778,19 @@ int mlagg_optimizer_clip_step_dev(int kind, const void *tensor_table, const void
  *    scale *= growth_factor if that is finite, tracker 0;
  * 3. update: returns at once when found_inf is set (parameters and state stay bit-identical), else the arithmetic of the kind with
  *    grad_mult where the clip coefficient stood.  Gradients stay SCALED and unclipped in memory.
- * With scale 1.0 and no overflow the results equal those of the unscaled entry points bit for bit.  Nothing that changes between
- * steps is an argument: the call can be captured into a hipGraph.
+ * With scale 1.0 and no overflow the results equal those of the unscaled entry points bit for bit.
  * ------------------------------------------------------------------------------------------ */
+#define MLAGG_OPT_SGD_NESTEROV 0
+#define MLAGG_OPT_ADAMW_AMSGRAD 1
+#define MLAGG_OPT_ADAM_L2 2
 #define MLAGG_OPT_ADAMW 3
+int mlagg_adamw_chunk_elements(void);
+int mlagg_optimizer_clip_step(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
+                              double *sumsq, float lr, double beta1, double beta2, float eps, float weight_decay, float max_norm, int step,
+                              void *stream);
+int mlagg_optimizer_clip_step_dev(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
+                                  double *sumsq, const float *lr_dev, int *step_dev, double beta1, double beta2, float eps,
+                                  float weight_decay, float max_norm, void *stream);
 int mlagg_scaled_clip_step_dev(int kind, const void *tensor_table, const void *extra_table, const void *work_list, int n_work,
                                double *sumsq, const float *lr_dev, int *step_dev, float *scale, int *growth_tracker, float *found_inf,
                                float *grad_mult, double beta1, double beta2, float eps, float weight_decay, float max_norm,

@@ -86,7 +86,9 @@ def algorithmic_bytes_sel1(kernel, batch, tokens, C=64, K=12, R=2):
     return int(per_token.get(kernel, 0)) * tokens * batch
 
 
-# the row of the "optimizer variants" timer (K34; csrc/prof.h K_OPT_VARIANTS, the last tag): update bytes per parameter of each kind
+# the row of the "optimizer variants" timer (csrc/prof.h K_OPT_VARIANTS, the last tag): mlagg_optimizer_clip_step / _dev and
+# mlagg_scaled_clip_step_dev time under it for every kind but MLAGG_OPT_ADAMW, which keeps K11's row (K_ADAMW).  Update bytes per
+# parameter of each kind
 OPTIMIZER_VARIANT_BYTES = {"sgd_nesterov": 20,     # read p, g, momentum_buffer; write p, momentum_buffer
                            "adamw_amsgrad": 36,    # read p, g, exp_avg, exp_avg_sq, max_exp_avg_sq; write all but g
                            "adam_l2": 28}          # read p, g, exp_avg, exp_avg_sq; write p, exp_avg, exp_avg_sq (as K11's AdamW)

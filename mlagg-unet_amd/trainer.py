@@ -364,9 +364,11 @@ class ClipOptimizer(torch.optim.Optimizer):
     list of the kernels, the pinned upload of the gradient addresses, the device-resident learning rate and step counter of the
     capturable form with its one capture per optimizer, and a ``load_state_dict`` that keeps the state tensors in place.
     A subclass names its per-parameter state tensors in ``_STATE`` (in the order of the table: two columns, a third goes into the extra
-    pointer block), says in ``_HAS_STEP`` whether torch's state carries a ``step`` entry, and launches its kernels in ``_launch``."""
+    pointer block), says in ``_HAS_STEP`` whether torch's state carries a ``step`` entry, names its kernel's kind constant of the header
+    (``MLAGG_OPT_*``) in ``_KIND`` and gives the group's hyper-parameters in ``_hyper``."""
     _STATE = ()
     _HAS_STEP = True
+    _KIND = None
 
     def __init__(self, params, defaults, capturable=False):
         params = list(params)
@@ -465,25 +467,28 @@ class ClipOptimizer(torch.optim.Optimizer):
             if self.capturable:
                 self._step_dev.fill_(self._steps)
 
-    def _launch(self, group, table, extra, work, max_norm, device_form):
+    def _hyper(self, group):
+        """(beta1 or momentum, beta2, eps) of the group as the kernel takes them."""
+        raise NotImplementedError
+
+    def _launch(self, group, table, extra, work, max_norm, device_form, scaler=None):
         """Launch the kernels of one step: ``table`` / ``extra`` / ``work`` are device tensors (``extra`` None without a third state
         tensor); ``device_form``: read the learning rate and the step from ``_lr_dev`` / ``_step_dev``, else ``group["lr"]`` and
-        ``_steps`` as launch arguments."""
-        raise NotImplementedError
-
-    def _scaled_hyper(self, group):
-        """(kind constant of the header, beta1 or momentum, beta2, eps) of the group for the loss-scaled step (K35)."""
-        raise NotImplementedError
-
-    def _launch_scaled(self, group, table, extra, work, max_norm, scaler):
-        """The loss-scaled step (K35) of ``DeviceGradScaler.step``: the device form alone, with the scaler's device state."""
+        ``_steps`` as launch arguments.  ``scaler``: the loss-scaled step (K35) of ``DeviceGradScaler.step``, the device form alone,
+        with the scaler's device state."""
         from . import _lib
-        kind, b1, b2, eps = self._scaled_hyper(group)
-        _lib.launch("mlagg_scaled_clip_step_dev", _lib.CONSTANTS[kind], table.data_ptr(), extra.data_ptr() if extra is not None else None,
-                    work.data_ptr(), work.shape[0], self._sumsq.data_ptr(), self._lr_dev.data_ptr(), self._step_dev.data_ptr(),
-                    scaler._scale.data_ptr(), scaler._growth_tracker.data_ptr(), scaler.found_inf.data_ptr(), scaler._mult.data_ptr(),
-                    b1, b2, eps, float(group["weight_decay"]), max_norm, scaler.growth_factor, scaler.backoff_factor,
-                    scaler.growth_interval)
+        b1, b2, eps = self._hyper(group)
+        head = (_lib.CONSTANTS[self._KIND], table.data_ptr(), extra.data_ptr() if extra is not None else None, work.data_ptr(),
+                work.shape[0], self._sumsq.data_ptr())
+        tail = (b1, b2, eps, float(group["weight_decay"]), max_norm)
+        if scaler is not None:
+            _lib.launch("mlagg_scaled_clip_step_dev", *head, self._lr_dev.data_ptr(), self._step_dev.data_ptr(), scaler._scale.data_ptr(),
+                        scaler._growth_tracker.data_ptr(), scaler.found_inf.data_ptr(), scaler._mult.data_ptr(), *tail,
+                        scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval)
+        elif device_form:
+            _lib.launch("mlagg_optimizer_clip_step_dev", *head, self._lr_dev.data_ptr(), self._step_dev.data_ptr(), *tail)
+        else:
+            _lib.launch("mlagg_optimizer_clip_step", *head, float(group["lr"]), *tail, self._steps)
 
     @torch.no_grad()
     def step(self, closure=None, max_norm=0.0, _grad_scaler=None):
@@ -573,10 +578,7 @@ class ClipOptimizer(torch.optim.Optimizer):
                     table.copy_(pinned, non_blocking=True)
                 if not capturing:
                     self.sync_lr()
-                if grad_scaler is not None:
-                    self._launch_scaled(group, *self._rows_and_third(table, T), work, float(max_norm), grad_scaler)
-                else:
-                    self._launch(group, *self._rows_and_third(table, T), work, float(max_norm), True)
+                self._launch(group, *self._rows_and_third(table, T), work, float(max_norm), True, grad_scaler)
                 continue
             table = host.pin_memory().to(dev, non_blocking=True)
             self._launch(group, *self._rows_and_third(table, T), work, float(max_norm), False)
@@ -593,52 +595,17 @@ class ClipAdamW(ClipOptimizer):
     ``state_dict`` layout (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``) as ``torch.optim.AdamW``; the clip
     coefficient is computed on the device (no host synchronisation) and the gradients in memory stay unscaled."""
     _STATE = ("exp_avg", "exp_avg_sq")
+    _KIND = "MLAGG_OPT_ADAMW"
 
     def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-4, weight_decay=3e-5, capturable=False):
         super().__init__(params, dict(lr=float(lr), betas=betas, eps=eps, weight_decay=weight_decay), capturable)
 
-    def _scaled_hyper(self, group):
-        b1, b2 = group["betas"]
-        return "MLAGG_OPT_ADAMW", float(b1), float(b2), float(group["eps"])
-
-    def _launch(self, group, table, extra, work, max_norm, device_form):
-        from . import _lib
-        b1, b2 = group["betas"]
-        if device_form:
-            _lib.launch("mlagg_adamw_clip_step_dev", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(),
-                        self._lr_dev.data_ptr(), self._step_dev.data_ptr(), float(b1), float(b2), float(group["eps"]),
-                        float(group["weight_decay"]), max_norm)
-        else:
-            _lib.launch("mlagg_adamw_clip_step", table.data_ptr(), work.data_ptr(), work.shape[0], self._sumsq.data_ptr(),
-                        float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), max_norm, self._steps)
-
-
-class _ClipVariant(ClipOptimizer):
-    """K34: the optimizers that go through ``mlagg_optimizer_clip_step`` / ``_dev`` with a kind."""
-    _KIND = None
-
     def _hyper(self, group):
-        """(beta1 or momentum, beta2, eps) of the group as the kernel takes them."""
-        raise NotImplementedError
-
-    def _scaled_hyper(self, group):
-        return (self._KIND,) + tuple(self._hyper(group))
-
-    def _launch(self, group, table, extra, work, max_norm, device_form):
-        from . import _lib
-        kind = _lib.CONSTANTS[self._KIND]
-        b1, b2, eps = self._hyper(group)
-        ex = extra.data_ptr() if extra is not None else None
-        if device_form:
-            _lib.launch("mlagg_optimizer_clip_step_dev", kind, table.data_ptr(), ex, work.data_ptr(), work.shape[0],
-                        self._sumsq.data_ptr(), self._lr_dev.data_ptr(), self._step_dev.data_ptr(), b1, b2, eps,
-                        float(group["weight_decay"]), max_norm)
-        else:
-            _lib.launch("mlagg_optimizer_clip_step", kind, table.data_ptr(), ex, work.data_ptr(), work.shape[0],
-                        self._sumsq.data_ptr(), float(group["lr"]), b1, b2, eps, float(group["weight_decay"]), max_norm, self._steps)
+        b1, b2 = group["betas"]
+        return float(b1), float(b2), float(group["eps"])
 
 
-class ClipSGD(_ClipVariant):
+class ClipSGD(ClipOptimizer):
     """clip_grad_norm_(max_norm) + torch.optim.SGD(momentum, nesterov=True) -- the optimizer of the reference's base trainer
     (nnUNetTrainer.py:448-452: lr 1e-2, momentum 0.99, weight decay 3e-5) -- in two launches for all parameters (K34).  Hyper-parameters,
     arithmetic (dampening 0; a zero buffer gives torch's first step) and ``state_dict`` layout (per parameter ``momentum_buffer``; the
@@ -672,7 +639,7 @@ class ClipSGD(_ClipVariant):
         return float(group["momentum"]), 0.0, 0.0
 
 
-class ClipAdam(_ClipVariant):
+class ClipAdam(ClipOptimizer):
     """clip_grad_norm_(max_norm) + Adam in two launches for all parameters (K34), in the two forms the reference's optimizer-variant
     trainers use (variants/optimizer/nnUNetTrainerAdam.py): ``amsgrad=True, decoupled=True`` is nnUNetTrainerAdam's
     torch.optim.AdamW(amsgrad=True), ``amsgrad=False, decoupled=False`` nnUNetTrainerVanillaAdam's torch.optim.Adam with L2 weight

@@ -604,7 +604,7 @@ def test_clip_adamw_matches_torch(max_norm):
 @gpu
 @pytest.mark.parametrize("max_norm", [12.0, 0.0])
 def test_capturable_clip_adamw_is_bit_identical_to_the_eager_form_and_replays(max_norm):
-    """The hipGraph form of K11 (step counter and a copy of the learning rate device-resident, mlagg_adamw_clip_step_dev): bit-identical parameters to
+    """The hipGraph form of K11 (step counter and a copy of the learning rate device-resident, mlagg_optimizer_clip_step_dev with MLAGG_OPT_ADAMW): bit-identical parameters to
     the launch-argument form over eager steps, a captured step replays with a NEW learning rate and advancing bias corrections, and the
     state_dict carries the device counter."""
     from mlagg_unet_amd import trainer as TR

@@ -269,16 +269,21 @@ def test_factories_build_the_optimizer_variant(stub_model, name, cls_want):
 # ABI
 # ---------------------------------------------------------------------------------------------------------------------
 def test_abi_symbols_exist_and_check_their_arguments():
-    """The entry points of K34 reject NULL pointers and unknown kinds on the host: no kernel is launched, no GPU is needed."""
+    """The entry points of the optimizer step reject NULL pointers and unknown kinds on the host: no kernel is launched, no GPU is
+    needed."""
     lib = _lib.lib()
     C = _lib.CONSTANTS
-    assert (C["MLAGG_OPT_SGD_NESTEROV"], C["MLAGG_OPT_ADAMW_AMSGRAD"], C["MLAGG_OPT_ADAM_L2"]) == (0, 1, 2)
+    assert (C["MLAGG_OPT_SGD_NESTEROV"], C["MLAGG_OPT_ADAMW_AMSGRAD"], C["MLAGG_OPT_ADAM_L2"], C["MLAGG_OPT_ADAMW"]) == (0, 1, 2, 3)
+    assert "mlagg_adamw_clip_step" not in _lib.SIGNATURES and "mlagg_adamw_clip_step_dev" not in _lib.SIGNATURES
     buf = ctypes.create_string_buffer(64)
     ptr = ctypes.addressof(buf)
     hyper = (1e-2, 0.9, 0.999, 1e-8, 3e-5, 12.0)
     assert lib.mlagg_optimizer_clip_step(0, None, None, ptr, 1, ptr, *hyper, 1, None) == C["MLAGG_E_NULLPTR"]
     assert lib.mlagg_optimizer_clip_step(0, ptr, None, ptr, 0, ptr, *hyper, 1, None) == C["MLAGG_E_UNSUPPORTED"]
-    assert lib.mlagg_optimizer_clip_step(3, ptr, ptr, ptr, 1, ptr, *hyper, 1, None) == C["MLAGG_E_UNSUPPORTED"]
+    for kind in (4, -1):
+        assert lib.mlagg_optimizer_clip_step(kind, ptr, ptr, ptr, 1, ptr, *hyper, 1, None) == C["MLAGG_E_UNSUPPORTED"]
+    assert lib.mlagg_optimizer_clip_step(3, ptr, None, ptr, 1, ptr, *hyper, 0, None) == C["MLAGG_E_UNSUPPORTED"]      # AdamW at step 0
+    assert lib.mlagg_optimizer_clip_step(3, None, None, ptr, 1, ptr, *hyper, 1, None) == C["MLAGG_E_NULLPTR"]
     assert lib.mlagg_optimizer_clip_step(1, ptr, None, ptr, 1, ptr, *hyper, 1, None) == C["MLAGG_E_UNSUPPORTED"]      # amsgrad without its table
     assert lib.mlagg_optimizer_clip_step(2, ptr, None, ptr, 1, ptr, *hyper, 0, None) == C["MLAGG_E_UNSUPPORTED"]      # Adam at step 0
     assert lib.mlagg_optimizer_clip_step_dev(0, ptr, None, ptr, 1, ptr, None, ptr, *hyper[1:], None) == C["MLAGG_E_NULLPTR"]

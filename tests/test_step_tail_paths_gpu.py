@@ -176,8 +176,9 @@ def test_clip_adamw_paths_match_float64(case, capturable):
 
 @pytest.mark.parametrize("case", K.K11_ABI_CASES, ids=_ids(K.K11_ABI_CASES))
 def test_adamw_c_abi_with_one_misaligned_pointer(case):
-    """mlagg_adamw_clip_step on a hand-built table and work list: each of p, g, m, v four bytes off a 16-byte boundary alone sends the
-    update kernel down its scalar path (g: the norm kernel too); nothing is written beside the tensors."""
+    """mlagg_optimizer_clip_step with MLAGG_OPT_ADAMW (no extra table) on a hand-built table and work list: each of p, g, m, v four bytes
+    off a 16-byte boundary alone sends the update kernel down its scalar path (g: the norm kernel too); nothing is written beside the
+    tensors."""
     from mlagg_unet_amd import _lib
     t = K.inputs(case)
     n = case.n
@@ -199,8 +200,8 @@ def test_adamw_c_abi_with_one_misaligned_pointer(case):
     work = _dev(torch.tensor([(0, c) for c in range(chunks)], dtype=torch.int32))
     sumsq = torch.zeros(1 + chunks, dtype=torch.float64, device=DEV)
     g_before = views["g"].clone()
-    _lib.launch("mlagg_adamw_clip_step", table.data_ptr(), work.data_ptr(), chunks, sumsq.data_ptr(), K.K11_LR, K.K11_BETAS[0],
-                K.K11_BETAS[1], K.K11_EPS, K.K11_WD, K.K11_ABI_MAX_NORM, step0 + 1)
+    _lib.launch("mlagg_optimizer_clip_step", _lib.CONSTANTS["MLAGG_OPT_ADAMW"], table.data_ptr(), None, work.data_ptr(), chunks,
+                sumsq.data_ptr(), K.K11_LR, K.K11_BETAS[0], K.K11_BETAS[1], K.K11_EPS, K.K11_WD, K.K11_ABI_MAX_NORM, step0 + 1)
     torch.cuda.synchronize()
     for name, (buf, lo) in bufs.items():
         assert float((buf[:lo] - 7.0).abs().max()) == 0.0 and float((buf[lo + n:] - 7.0).abs().max()) == 0.0, name

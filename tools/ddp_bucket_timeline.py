@@ -5,7 +5,7 @@ kernel for a one-rank all-reduce, so what the trace can show is the ENQUEUE poin
 issued from the post-accumulate-grad hook of the bucket's last gradient, directly in front of `dist.all_reduce(async_op=True)`).
 
     python tools/ddp_bucket_timeline.py trace.csv --steps 5 > profiles/roundN_ddp_bucket_timeline.md
-A step runs from the loss gradient kernel (dice_ce_grad_kernel, first kernel of backward) to the optimizer (adamw_update_kernel)."""
+A step runs from the loss gradient kernel (dice_ce_grad_kernel, first kernel of backward) to the optimizer (opt_update_kernel)."""
 import argparse
 import csv
 import re
@@ -16,7 +16,7 @@ ap.add_argument("--steps", type=int, default=5)
 a = ap.parse_args()
 rows = list(csv.DictReader(open(a.trace)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-upd = [i for i, r in enumerate(rows) if "adamw_update_kernel" in r["Kernel_Name"]]
+upd = [i for i, r in enumerate(rows) if "opt_update_kernel" in r["Kernel_Name"]]
 print("# Gradient-bucket enqueue points inside the backward pass (single-rank RCCL run)\n")
 print("One line per bucket gather (`multi_tensor_apply_kernel<... copy ...>` issued by trainer.BucketedGradSync's hook); times in ms from the "
       "first backward kernel of the step; `backward done` = start of the clip / AdamW kernels.\n")
