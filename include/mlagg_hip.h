@@ -1193,6 +1193,37 @@ int mlagg_cascade_cc_stats(const unsigned long long *planes, int P, int X, int Y
 int mlagg_cascade_cc_remove(unsigned long long *planes, int P, int X, int Y, int Z, double thresh, const int *parent, const int *size,
                             const int *blockcnt, const int *rank, const int *fill, int *target, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K36: the tail of the training / validation transform chain in one launch, from the augmented (data, seg) to what the loss consumes:
+ * MaskTransform (custom_transforms/masking.py:18-22), RemoveLabelTransform(-1, 0), ConvertSegmentationToRegionsTransform
+ * (custom_transforms/region_based_training.py:23-38) and DownsampleSegForDSTransform2 with order 0, as nnUNetTrainer.py:697-731
+ * (training) and :742-757 (validation, no mask) chain them.  nd = 2 or 3 spatial axes.
+ *   data (B, C, *S) fp32, DEVICE, written in place: data[b, c, p] = 0 where seg[b, 0, p] < 0 (the value BEFORE the mapping below) for
+ *        every c of mask_channels (HOST array of n_mask ints in 0 .. min(C, 64) - 1; n_mask == 0: data is not touched and may be NULL).
+ *        No other element of data is written, none is read.  A mask needs level 0 to be the identity (all its tables NULL).
+ *   seg  (B, Sc, *S), DEVICE, fp32 (seg_kind MLAGG_TAIL_SEG_F32) or int16 (MLAGG_TAIL_SEG_INT16); only channel 0 is read.
+ *   sizes: HOST array of nd ints S.  level_sizes: HOST array of L x nd ints S_l, 1 <= L <= MLAGG_TAIL_MAX_LEVELS.
+ *   tables: HOST array of L x nd DEVICE pointers: tables[l * nd + a] holds S_l[a] int32 source indices into axis a (output voxel i of
+ *        level l copies source voxel table[i]; an index outside 0 .. S[a] - 1 is clamped into it).  NULL: the identity on that axis,
+ *        which needs S_l[a] == S[a].
+ *   out: HOST array of L DEVICE pointers to fp32 maps, every element of which is written:
+ *        member == NULL  (label mode)  (B, 1, *S_l): w = v < 0 ? 0 : v of the source voxel.
+ *        member != NULL  (region mode) (B, R', *S_l), R' = R + (ignore_label >= 0), 1 <= R <= MLAGG_TAIL_MAX_REGIONS.  member (DEVICE,
+ *                        256 uint32): bit r of member[w] says that label w belongs to region r (np.isin; a label that is no integer in
+ *                        0 .. 255 has no bits).  Plane r < R is 1.0f where that bit is set, else 0.0f; plane R is w == ignore_label.
+ *                        The layout K29 takes with member == NULL.
+ * One launch: the grid is the concatenation of the levels' output index spaces, a thread owns four consecutive output voxels of one
+ * row of one level and writes all their planes (16-byte loads and stores where the row length and the alignment allow; scalar ones
+ * otherwise); level-0 threads also write the mask.  64-bit offsets, no atomics, no LDS, no workspace, no synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+#define MLAGG_TAIL_SEG_F32   0
+#define MLAGG_TAIL_SEG_INT16 1
+#define MLAGG_TAIL_MAX_LEVELS 8
+#define MLAGG_TAIL_MAX_REGIONS 32
+int mlagg_batch_tail(float *data, int B, int C, const void *seg, int seg_kind, int Sc, int nd, const int *sizes,
+                     const int *mask_channels, int n_mask, int L, const int *level_sizes, const void *const *tables, void *const *out,
+                     const unsigned int *member, int R, int ignore_label, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,7 +43,7 @@ const char *const kNames[K_COUNT] = {
     "aug3d_resample_kernel", "pt_seg_crop_kernel", "pt_seg_resize_kernel", "pt_rank_count_kernel (+ scan)", "pt_rank_select_kernel",
     "cl_local_kernel", "cl_merge_kernel", "cl_compress_kernel", "cl_flag_kernel", "cl_scan (count + offsets + apply)", "cl_rewrite_kernel",
     "cl_overlap_kernel", "cl_match_kernel", "ens_mean_kernel", "label_confusion_kernel", "dice_bce_stats_kernel", "dice_bce_grad_kernel",
-    "aug3d_planar_kernel", "sw_gather_onehot_kernel", "topk_ce stats (dice_ce_stats_kernel<true, .> + reduce)",
+    "aug3d_planar_kernel", "sw_gather_onehot_kernel", "batch_tail_kernel", "topk_ce stats (dice_ce_stats_kernel<true, .> + reduce)",
     "topk_ce select (init + 3 x (hist + pick) + sum + finish)", "topk_ce grad (dice_ce_grad_kernel<true, .>)",
     "optimizer variants (K34: sumsq + opt_update_kernel<SGD-Nesterov / AdamW-amsgrad / Adam-L2>)"};
 }  // namespace

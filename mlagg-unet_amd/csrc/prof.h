@@ -12,6 +12,7 @@ enum KernelId {
     K_SEL1_BWD, K_SEL1_PREFIX, K_SEL1_REDUCE, K_CONV_PAD, K_CONV_WGRAD, K_CONV_WGRAD_REDUCE, K_CONV_TAPS, K_GELU_POOL, K_CONV1X1, K_CONV3X3, K_TOK_FWD_LOCAL, K_TOK_FWD_FINAL, K_TOK_BWD_LOCAL, K_TOK_BWD_GROUP, K_SW_GATHER, K_SW_FOLD, K_SW_FINALIZE, K_RESAMPLE_LINEAR, K_EXPORT_SEG, K_PP_BOX, K_PP_STATS, K_PP_NORMALIZE, K_PP_MINMAX, K_PP_CUBIC, K_PP_GATHER, K_CC_LOCAL, K_CC_MERGE, K_CC_COMPRESS, K_CC_SIZE, K_CC_MAX, K_CC_WRITE, K_SF_STATS, K_SF_CODES, K_SF_ZPASS, K_SF_YPASS, K_SF_XPASS, K_SF_SUM, K_AUG3D_RESAMPLE, K_PT_SEG_CROP, K_PT_SEG_RESIZE, K_PT_RANK_COUNTS, K_PT_RANK_SELECT,
     K_CL_LOCAL, K_CL_MERGE, K_CL_COMPRESS, K_CL_FLAG, K_CL_SCAN, K_CL_REWRITE, K_CL_OVERLAP, K_CL_MATCH,
     K_ENS_MEAN, K_LABEL_CONFUSION, K_REGION_LOSS_STATS, K_REGION_LOSS_GRAD, K_AUG3D_PLANAR, K_SW_GATHER_ONEHOT,
+    K_BATCH_TAIL,
     K_TOPK_STATS, K_TOPK_SELECT, K_TOPK_GRAD, K_OPT_VARIANTS, K_COUNT
 };
 

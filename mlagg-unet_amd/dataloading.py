@@ -18,7 +18,12 @@ and augmentation3d.py (3-D).
 
 A cascade's second stage (3d_cascade_fullres) gives `Dataset` the folder with the previous stage's predictions
 (nnunet_dataset.py:48-49, 104-109): every case then has a second seg channel, which the loaders crop with the same box and
-pad with -1, and which augmentation3d turns into one-hot input channels on the device."""
+pad with -1, and which augmentation3d turns into one-hot input channels on the device.
+
+With `mask_channels` / `regions` / `ignore_label` the feed ends in K36 (ops.batch_tail): MaskTransform, the region planes and every
+deep-supervision level in one launch; `DeviceBatchIterator` puts the protocol of nnU-Net's generators on a `PrefetchLoader`
+(nnunet_plugin's ``data_pipeline="device"``)."""
+import contextlib
 import os
 import pickle
 import queue
@@ -249,35 +254,96 @@ class DataLoader3D(DataLoader2D):
         return {"data": data_t, "seg": seg_t, "keys": keys}
 
 
+_NEAREST = {}
+
+
+def nearest_index(n, m):
+    """The source index along an axis of n voxels for each of the m voxels that ``F.interpolate(..., size=m, mode="nearest-exact")``
+    makes of it, as m int32 (host): THE index rule of the deep-supervision targets.  It is read off torch itself (an arange is
+    interpolated once per (n, m)), not restated, so whatever gathers with it (K36, ops.batch_tail) is `targets_from_seg` to the bit."""
+    key = (int(n), int(m))
+    if key not in _NEAREST:
+        if key[0] < 1 or key[1] < 1 or key[0] >= 1 << 24:
+            raise RuntimeError(f"nearest_index: an axis of {key[0]} voxels resized to {key[1]}")
+        ramp = torch.arange(key[0], dtype=torch.float32).view(1, 1, -1)          # exact in fp32 below 2^24
+        _NEAREST[key] = torch.nn.functional.interpolate(ramp, size=key[1], mode="nearest-exact").view(-1).to(torch.int32)
+    return _NEAREST[key]
+
+
+def level_sizes(spatial, n_levels=5, ds_scales=None):
+    """The spatial shapes of the deep-supervision targets of a `spatial` map, as `targets_from_seg` makes them: n_levels halvings of
+    the two axes of a 2-D map, or round(shape * scale) per level of `ds_scales`."""
+    spatial = tuple(int(v) for v in spatial)
+    if ds_scales is None:
+        if n_levels > 1 and len(spatial) != 2:
+            raise RuntimeError(f"level_sizes: {n_levels} halvings are for 2-D maps, got {spatial}: give ds_scales")
+        return [spatial] + [tuple(v >> s for v in spatial) for s in range(1, n_levels)]
+    sizes = []
+    for sc in ds_scales:
+        if len(sc) != len(spatial):
+            raise RuntimeError(f"deep-supervision scale {list(sc)} for a {len(spatial)}-D segmentation")
+        sizes.append(tuple(int(v) for v in np.round(np.array(spatial, dtype=float) * np.array(sc, dtype=float))))
+    return sizes
+
+
 def targets_from_seg(seg, n_levels=5, ds_scales=None):
     """RemoveLabelTransform(-1, 0) (B:701) + DownsampleSegForDSTransform2, order 0 (B:730): the deep-supervision targets.
     2-D: n_levels halvings of both axes.  `ds_scales` (the trainer's _get_deep_supervision_scales(), one per-axis scale
     list per level, e.g. [1, .5, .5]): level shape round(shape * scale), nearest-exact; an all-ones scale is the map itself."""
     seg = torch.where(seg < 0, torch.zeros_like(seg), seg)
-    if ds_scales is None:
-        targets = [seg]
-        for s in range(1, n_levels):
-            size = (seg.shape[2] >> s, seg.shape[3] >> s)
-            targets.append(torch.nn.functional.interpolate(seg, size=size, mode="nearest-exact"))
-        return targets
+    return [seg if size == tuple(seg.shape[2:]) else torch.nn.functional.interpolate(seg, size=size, mode="nearest-exact")
+            for size in level_sizes(seg.shape[2:], n_levels, ds_scales)]
+
+
+def batch_tail_host(data, seg, sizes, mask_channels=(), member=None, n_regions=0, ignore_label=None, tables=None):
+    """What K36 computes (ops.batch_tail, which checks the arguments), as a torch composition on whatever device the tensors live on:
+    the reference's MaskTransform (masking.py:18-22) as an indexed fill of `data`, then per level of `sizes` the map of
+    `targets_from_seg` (the same where + nearest-exact interpolate; with `tables`, a gather by the given per-axis indices) and, with
+    the `member` table of ops.region_member_table, the planes of ConvertSegmentationToRegionsTransform
+    (region_based_training.py:23-38) by table look-up, the ignore label as one more region (B:722-726)."""
+    raw = seg[:, :1]
+    if len(mask_channels):
+        outside = (raw[:, 0] < 0).unsqueeze(1).expand(-1, len(mask_channels), *raw.shape[2:])
+        data[:, list(mask_channels)] = data[:, list(mask_channels)].masked_fill(outside, 0.0)
+    labels = raw.float()
+    labels = torch.where(labels < 0, torch.zeros_like(labels), labels)
     targets = []
-    for sc in ds_scales:
-        if len(sc) != seg.dim() - 2:
-            raise RuntimeError(f"deep-supervision scale {list(sc)} for a {seg.dim() - 2}-D segmentation")
-        if all(float(v) == 1.0 for v in sc):
-            targets.append(seg)
-            continue
-        size = tuple(int(v) for v in np.round(np.array(seg.shape[2:], dtype=float) * np.array(sc, dtype=float)))
-        targets.append(torch.nn.functional.interpolate(seg, size=size, mode="nearest-exact"))
-    return targets
+    for lvl, size in enumerate(sizes):
+        level = labels
+        if tables is not None and any(t is not None for t in tables[lvl]):
+            for axis, tab in enumerate(tables[lvl]):
+                if tab is not None:
+                    level = level.index_select(2 + axis, tab.long().clamp(0, labels.shape[2 + axis] - 1))
+        elif tuple(size) != tuple(labels.shape[2:]):
+            level = torch.nn.functional.interpolate(labels, size=tuple(size), mode="nearest-exact")
+        if member is not None:
+            whole = (level >= 0) & (level < 256) & (level == level.floor())        # np.isin: other values are in no region
+            bits = torch.where(whole, member.long()[torch.where(whole, level, torch.zeros_like(level)).long()] & 0xFFFFFFFF,
+                               torch.zeros_like(level, dtype=torch.int64))
+            planes = [(bits >> r) & 1 for r in range(n_regions)]
+            if ignore_label is not None:
+                planes.append(level == float(ignore_label))
+            level = torch.cat(planes, 1).float()
+        targets.append(level.contiguous())
+    return data, targets
 
 
-def to_device(batch, device, n_levels=5, stream=None, augmenter=None, ds_scales=None, cascade_labels=None):
+def _tail_wanted(mask_channels, regions, ignore_label):
+    return mask_channels is not None or regions is not None or ignore_label is not None
+
+
+def to_device(batch, device, n_levels=5, stream=None, augmenter=None, ds_scales=None, cascade_labels=None, mask_channels=None,
+              regions=None, ignore_label=None):
     """Host batch -> (data (B, C, *spatial) fp32, [target_s (B, 1, *spatial_s) fp32 labels]) on `device`; with an
     `augmenter` (augmentation.GpuAugmenter / augmentation3d.GpuAugmenter3D) the training transforms run on the device in
     between.  2-D: n_levels halvings; `ds_scales`: per-axis scales (targets_from_seg), for 3-D batches.  A cascade batch
     (two seg channels) goes through an augmenter built with `cascade_labels`, or, without an augmenter (validation), through
-    augmentation3d.move_seg_as_one_hot with the `cascade_labels` given here: data gains one input channel per label."""
+    augmentation3d.move_seg_as_one_hot with the `cascade_labels` given here: data gains one input channel per label.
+    With any of `mask_channels` (indices of the data channels of ``use_mask_for_norm``), `regions` (the label manager's
+    ``foreground_regions``) and `ignore_label` given, the rest of the reference's chain (B:697-731) runs as ONE kernel (K36,
+    ops.batch_tail) instead of `targets_from_seg`: the mask on `data` (training only: the validation chain has no MaskTransform, so
+    without an augmenter no mask is applied), and targets that are region planes (B, R (+ 1 with an ignore label), *spatial_s) when
+    there are regions."""
     device = torch.device(device)
     ctx = torch.cuda.stream(stream) if stream is not None else _Null()
     with ctx:
@@ -292,7 +358,15 @@ def to_device(batch, device, n_levels=5, stream=None, augmenter=None, ds_scales=
                 raise RuntimeError("to_device: a cascade batch (two seg channels) needs an augmenter or cascade_labels")
             from .augmentation3d import move_seg_as_one_hot
             data, seg = move_seg_as_one_hot(data, seg, cascade_labels)
-        targets = targets_from_seg(seg.float(), n_levels, ds_scales)
+        if _tail_wanted(mask_channels, regions, ignore_label):
+            from . import ops
+            masked = tuple(mask_channels or ()) if augmenter is not None else ()
+            if seg.dtype not in (torch.float32, torch.int16):
+                seg = seg.float()
+            data, targets = ops.batch_tail(data.contiguous(), seg.contiguous(), level_sizes(seg.shape[2:], n_levels, ds_scales),
+                                           masked, regions, ignore_label)
+        else:
+            targets = targets_from_seg(seg.float(), n_levels, ds_scales)
     return data, targets
 
 
@@ -310,8 +384,10 @@ class PrefetchLoader:
     caller's current stream wait for that copy only."""
 
     def __init__(self, loader, device, num_workers=4, depth=6, seed=1234, n_levels=5, augmenter=None, ds_scales=None,
-                 cascade_labels=None):
+                 cascade_labels=None, mask_channels=None, regions=None, ignore_label=None):
         self.cascade_labels = cascade_labels
+        self.tail = dict(mask_channels=mask_channels, regions=regions, ignore_label=ignore_label)      # K36: see to_device
+        self._gate, self._busy, self._paused = threading.Condition(), 0, False                           # see quiesced()
         self.device = torch.device(device)
         self.q = queue.Queue(maxsize=depth)
         self.stop = threading.Event()
@@ -328,20 +404,29 @@ class PrefetchLoader:
 
     def _work(self, loader, augmenter=None):
         while not self.stop.is_set():
+            with self._gate:
+                while self._paused and not self.stop.is_set():
+                    self._gate.wait(0.2)
+                self._busy += 1
             try:
                 b = loader.generate_train_batch()
                 if self.copy_stream is not None:
                     data, targets = to_device(b, self.device, self.n_levels, self.copy_stream, augmenter, self.ds_scales,
-                                              self.cascade_labels)
+                                              self.cascade_labels, **self.tail)
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
                 else:
-                    data, targets = to_device(b, self.device, self.n_levels, None, augmenter, self.ds_scales, self.cascade_labels)
+                    data, targets = to_device(b, self.device, self.n_levels, None, augmenter, self.ds_scales, self.cascade_labels,
+                                              **self.tail)
                     ev = None
                 item = (data, targets, ev, b)                 # keep the pinned host batch alive until consumed
             except BaseException as e:                        # missing .pkl, bad .npz, out of memory on the copy stream ...
                 item = e                                      # handed to the consumer: next() re-raises it
                 self.stop.set()
+            finally:
+                with self._gate:
+                    self._busy -= 1
+                    self._gate.notify_all()
             while True:
                 try:
                     self.q.put(item, timeout=0.2)
@@ -349,6 +434,22 @@ class PrefetchLoader:
                 except queue.Full:
                     if self.stop.is_set() and not isinstance(item, BaseException):
                         break
+
+    @contextlib.contextmanager
+    def quiesced(self):
+        """Inside the block no worker assembles a batch or talks to the device (batches already queued stay available): for the
+        moments in which the consumer captures a hipGraph, when allocations, synchronous copies and event queries of OTHER threads
+        are errors in the runtime's default capture mode.  Waits for the batches in assembly to finish."""
+        with self._gate:
+            self._paused = True
+            while self._busy:
+                self._gate.wait(0.2)
+        try:
+            yield self
+        finally:
+            with self._gate:
+                self._paused = False
+                self._gate.notify_all()
 
     def next(self):
         while True:
@@ -377,3 +478,28 @@ class PrefetchLoader:
                 break
         for t in self.workers:
             t.join(timeout=2)
+
+
+class DeviceBatchIterator:
+    """A `PrefetchLoader` behind the protocol ``nnUNetTrainer.run_training`` drives its data generators with (the reference's
+    NonDetMultiThreadedAugmenter / SingleThreadedAugmenter, nnUNetTrainer.py:600-610): ``next(it)`` is
+    ``{"data": tensor, "target": list of tensors}`` -- on the device already, so the trainer's ``.to(device)`` is a no-op -- and
+    `target` is a single tensor when the loader has no `ds_scales`, as NumpyToTensor delivers it without deep supervision.  Infinite,
+    like the reference's generators: the trainer counts the iterations of an epoch itself.  ``_finish()`` (the name the reference
+    calls on its generators when training ends) stops and joins the workers."""
+
+    def __init__(self, prefetch_loader):
+        self.loader = prefetch_loader
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        data, targets = self.loader.next()
+        return {"data": data, "target": list(targets) if self.loader.ds_scales is not None else targets[0]}
+
+    def quiesced(self):
+        return self.loader.quiesced()
+
+    def _finish(self, timeout=None):
+        self.loader.close()

@@ -28,12 +28,18 @@ What the class overrides, and why the inherited method cannot stay (B = nnUNetTr
                     reference's base trainer (B:448-452: SGD momentum 0.99 Nesterov + PolyLR) or of its optimizer-variant trainers
                     (variants/optimizer/nnUNetTrainerAdam.py) instead, with the clip and the update fused on the device (K34:
                     ``trainer.ClipSGD`` / ``trainer.ClipAdam`` + ``trainer.PolyLRSchedule``).
+  * ``get_dataloaders``  B:566-610, only with ``data_pipeline="device"`` of the factories: the loaders in threads, the base trainer's
+                    transform chain on the device (the augmenters, then K36 for the mask, the regions and the deep-supervision levels),
+                    batches that arrive on the MI355X (``_device_dataloaders``).  The default inherits the reference's generators.
 """
+import contextlib
+import math
 import os
 
+import numpy as np
 import torch
 
-from . import evaluation, miopen_tuning, model, trainer
+from . import augmentation, augmentation3d, dataloading, evaluation, miopen_tuning, model, trainer
 
 PRECISIONS = ("fp32", "bf16", "fp16")
 # The reference loop reads the loss back every step (B:863), so the host cannot run ahead of the device: an eagerly enqueued step then
@@ -88,6 +94,101 @@ def _check_loss_scaling(loss_scaling):
         raise RuntimeError(f"loss_scaling {loss_scaling!r}: one of {LOSS_SCALINGS}")
 
 
+DATA_PIPELINES = ("reference", "device")
+
+
+def _check_data_pipeline(data_pipeline):
+    if data_pipeline not in DATA_PIPELINES:
+        raise RuntimeError(f"data_pipeline {data_pipeline!r}: one of {DATA_PIPELINES}")
+
+
+def _same_ranges(a, b):
+    return len(a) == len(b) and all(len(p) == 2 and len(q) == 2 and math.isclose(p[0], q[0], rel_tol=1e-9, abs_tol=1e-12)
+                                    and math.isclose(p[1], q[1], rel_tol=1e-9, abs_tol=1e-12) for p, q in zip(a, b))
+
+
+def _device_dataloaders(self):
+    """``get_dataloaders`` (reference B:566-610) of a class built with ``data_pipeline="device"``: the loaders of
+    ``get_plain_dataloaders`` (B:612-641) as `dataloading.DataLoader2D` / `DataLoader3D` in worker threads, the transforms of
+    ``get_training_transforms`` / ``get_validation_transforms`` (B:644-760) on the device (GpuAugmenter / GpuAugmenter3D, then K36 for
+    the mask, the regions and the deep-supervision levels), delivered through `dataloading.PrefetchLoader` with the protocol of the
+    reference's generators (`dataloading.DeviceBatchIterator`).  Returns (training iterator, validation iterator).
+    The device chain restates the BASE trainer's transforms: a trainer whose ``configure_rotation_dummyDA_mirroring_and_inital_patch_size``
+    answers anything else (the DA5, NoDA, DAOrd0, NoMirroring variants) is refused here instead of being trained on another augmentation."""
+    cm, lm = self.configuration_manager, self.label_manager
+    patch = tuple(int(v) for v in cm.patch_size)
+    dim = len(patch)
+    ds_scales = self._get_deep_supervision_scales()
+    # B:576: also sets self.inference_allowed_mirroring_axes
+    rotation_for_DA, dummy_2d, initial_patch_size, mirror_axes = self.configure_rotation_dummyDA_mirroring_and_inital_patch_size()
+    got = ([tuple(float(v) for v in rotation_for_DA[k]) for k in ("x", "y", "z")], bool(dummy_2d),
+           tuple(int(v) for v in initial_patch_size), None if mirror_axes is None else tuple(int(v) for v in mirror_axes))
+    labels = [int(v) for v in lm.all_labels]
+    ignore_label = getattr(lm, "ignore_label", None)
+    # every value the loaders' segmentation holds: LabelManager.all_labels leaves the ignore label out (label_handling.py:88-102)
+    seg_values = labels + ([int(ignore_label)] if ignore_label is not None and int(ignore_label) not in labels else [])
+    rank = int(self.local_rank) if self.is_ddp else 0
+    seed = getattr(self, "mlagg_data_seed", None)              # None: fresh entropy, as the reference's seeds=None; an int pins every draw
+    seed = int(np.random.SeedSequence().entropy % (1 << 30)) if seed is None else int(seed)
+    seed += 1000003 * rank
+    cascade_labels = None
+    if dim == 2:
+        rotation = augmentation.rotation_for_2d(patch)
+        augmenter = augmentation.GpuAugmenter(patch, self.device, rotation=rotation, mirror_axes=(0, 1), seed=seed, labels=seg_values)
+        want = ([tuple(rotation), (0.0, 0.0), (0.0, 0.0)], False, augmenter.initial_patch_size(), (0, 1))
+        loader_class = dataloading.DataLoader2D
+    elif dim == 3:
+        rotation, want_dummy, want_initial, want_mirror = augmentation3d.configure_3d(patch)
+        if self.is_cascaded:
+            cascade_labels = [int(v) for v in lm.foreground_labels]
+        augmenter = augmentation3d.GpuAugmenter3D(patch, self.device, rotation=rotation, mirror_axes=want_mirror, seed=seed,
+                                                  labels=seg_values, cascade_labels=cascade_labels, dummy_2d=bool(dummy_2d))
+        want = ([tuple(float(v) for v in r) for r in rotation], want_dummy, tuple(want_initial), tuple(want_mirror))
+        loader_class = dataloading.DataLoader3D
+    else:
+        raise RuntimeError(f"data_pipeline='device': a 2-D or 3-D patch, got {patch}")
+    if not (_same_ranges(got[0], want[0]) and got[1:] == want[1:]):
+        raise RuntimeError("data_pipeline='device' restates the base trainer's training transforms; this trainer asks for (rotation x / y / z, "
+                           f"dummy 2-D, initial patch size, mirror axes) = {got}, the device chain would use {want}")
+    regions = None
+    if getattr(lm, "has_regions", False):
+        if not _describes_regions(lm):
+            raise RuntimeError("data_pipeline='device': the label manager says has_regions without naming its foreground_regions")
+        regions = list(lm.foreground_regions)
+    tail = dict(mask_channels=[i for i, m in enumerate(cm.use_mask_for_norm or ()) if m], regions=regions,
+                ignore_label=ignore_label)
+    levels = dict(ds_scales=ds_scales) if ds_scales is not None else dict(n_levels=1)       # no deep supervision: the map itself
+
+    tr_keys, val_keys = self.do_split()                                             # B:543-564
+    previous = self.folder_with_segs_from_previous_stage
+    has_ignore = bool(getattr(lm, "has_ignore_label", tail["ignore_label"] is not None))
+
+    def loader(keys, loader_patch):
+        dataset = dataloading.Dataset(self.preprocessed_dataset_folder, keys, folder_with_segs_from_previous_stage=previous)
+        return loader_class(dataset, self.batch_size, loader_patch, patch, labels, self.oversample_foreground_percent,
+                            has_ignore=has_ignore)
+
+    workers = min(max(int(os.environ.get("nnUNet_n_proc_DA", 4)), 1), 16)          # get_allowed_n_proc_DA, at least one thread
+    train = dataloading.PrefetchLoader(loader(tr_keys, want[2]), self.device, num_workers=workers, depth=6, seed=seed + 1,
+                                       augmenter=augmenter, **levels, **tail)
+    try:
+        val = dataloading.PrefetchLoader(loader(val_keys, patch), self.device, num_workers=max(1, workers // 2), depth=3,
+                                         seed=seed + 500009, cascade_labels=cascade_labels, **levels, **tail)
+    except BaseException:
+        train.close()
+        raise
+    self.mlagg_feeds = (dataloading.DeviceBatchIterator(train), dataloading.DeviceBatchIterator(val))
+    return self.mlagg_feeds
+
+
+def _feeds_quiesced(self):
+    """The device iterators of `_device_dataloaders` held still (`PrefetchLoader.quiesced`) while the step is captured as a hipGraph."""
+    stack = contextlib.ExitStack()
+    for feed in getattr(self, "mlagg_feeds", ()):
+        stack.enter_context(feed.quiesced())
+    return stack
+
+
 def _variant_optimizers(self, optimizer, capturable):
     """``configure_optimizers`` of a class built with ``optimizer=``: the fused optimizer of that recipe (K34) plus PolyLR over the
     trainer's ``num_epochs``; ``initial_lr`` and ``weight_decay`` are the trainer's (the base trainer's 1e-2 / 3e-5 unless a class set them)."""
@@ -114,7 +215,8 @@ def _variant_loss(variant, label_manager, batch_dice, ddp, ignore_label):
     return loss
 
 
-def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAULT_LOSS, optimizer=None, loss_scaling="torch"):
+def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAULT_LOSS, optimizer=None, loss_scaling="torch",
+                       data_pipeline="reference"):
     """loss: "dice_ce" (the reference trainer's DC_and_CE_loss / DC_and_BCE_loss) or one of ``trainer.LOSS_VARIANTS`` -- the loss of
     the reference's nnUNetTrainerTopk10Loss ("topk10"), ...Topk10LossLS01 ("topk10_ls01"), ...DiceTopK10Loss ("dice_topk10"),
     ...DiceLoss ("dice"), ...CELoss ("ce") or ...DiceCELoss_noSmooth ("dice_ce_nosmooth").  Every one of them is device-fused, so the
@@ -126,12 +228,16 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
     loss_scaling: who scales the loss of ``precision="fp16"`` (the other precisions do not scale it).  "torch" (the default): the
     ``torch.amp.GradScaler`` of B:152, eager steps.  "device": ``trainer.DeviceGradScaler`` (K35) with a capturable optimizer -- no host
     synchronisation, no rewrite of the gradients, and the step replays as a hipGraph like every other precision's.  Checkpoints carry
-    ``grad_scaler_state`` with torch's keys either way and load into either.  Kept in ``mlagg_loss_scaling``."""
+    ``grad_scaler_state`` with torch's keys either way and load into either.  Kept in ``mlagg_loss_scaling``.
+    data_pipeline: "reference" (the default) inherits ``get_dataloaders``: batchgenerators worker processes on the CPU (B:566-610).
+    "device": `_device_dataloaders` -- the loaders in threads, every transform of the base trainer's chain on the MI355X (the
+    augmenters, then K36), batches that arrive on the device.  Kept in ``mlagg_data_pipeline``."""
     if precision not in PRECISIONS:
         raise RuntimeError(f"precision {precision!r}: this build of the MI355X path offers {PRECISIONS}")
     _check_loss(loss)
     _check_optimizer(optimizer)
     _check_loss_scaling(loss_scaling)
+    _check_data_pipeline(data_pipeline)
     loss_variant = loss
 
     class nnUNetTrainer_MLAgg_2D_dt_MS(nnUNetTrainer):
@@ -156,6 +262,7 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
             self.mlagg_loss_scaling = loss_scaling
             self.mlagg_loss_variant = loss_variant                                  # for logs and checkpoints
             self.mlagg_optimizer = optimizer
+            self.mlagg_data_pipeline = data_pipeline
             self._graphed, self._graph_key, self._graph_eager, self._graph_failed = None, None, 0, None
             # run_training.py:123-125 sets cudnn.benchmark (MIOpen's exhaustive find); here: the committed find-db, which
             # holds the fp32 convolutions of the 256 x 256 step only.  Any other patch size or precision takes MIOpen's
@@ -223,6 +330,9 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
                 return _variant_optimizers(self, optimizer, capturable)
             return trainer.configure_optimizers(self.network, self.initial_lr, self.weight_decay, capturable=capturable)
 
+        if data_pipeline == "device":
+            get_dataloaders = _device_dataloaders                                   # reference B:566-610
+
         def _to_device(self, batch):                                                # reference B:834-841
             data = batch["data"].to(self.device, non_blocking=True)
             target = batch["target"]
@@ -246,8 +356,9 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
                         try:
                             # warmup=0: the eager steps above were the warm-up; the capture itself executes nothing, so the first
                             # replay IS this step (no batch is trained on twice)
-                            self._graphed = trainer.GraphedTrainStep(self.network, self.optimizer, data, target, clip=12.0,
-                                                                     warmup=0, loss_fn=self.loss, grad_scaler=self.grad_scaler)
+                            with _feeds_quiesced(self):                             # no loader thread calls the runtime meanwhile
+                                self._graphed = trainer.GraphedTrainStep(self.network, self.optimizer, data, target, clip=12.0,
+                                                                         warmup=0, loss_fn=self.loss, grad_scaler=self.grad_scaler)
                             return {"loss": self._graphed().cpu().numpy()}
                         except Exception as e:                                      # noqa: BLE001  (stay eager, say why once)
                             self._graphed, self._graph_failed = None, repr(e)
@@ -277,7 +388,8 @@ def make_trainer_class(nnUNetTrainer, variant="B", precision="fp32", loss=DEFAUL
     return nnUNetTrainer_MLAgg_2D_dt_MS
 
 
-def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimizer=None, loss_scaling="torch"):
+def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimizer=None, loss_scaling="torch",
+                                       data_pipeline="reference"):
     """``nnUNetTrainerUMambaEnc_SS3D`` (reference variants/mamba/nnUNetTrainerUMambaEnc_SS3D.py:8-31) on the MI355X 3-D network
     (model3d.UMambaEnc; BASELINE configs[3]).  The reference class overrides ``build_network_architecture`` only and inherits the
     base trainer's recipe (SGD momentum 0.99 Nesterov + PolyLR, nnUNetTrainer.py:448-452; DC_and_CE deep-supervision loss,
@@ -288,11 +400,13 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimiz
     recipe with the clip and the update fused on the device (K34: ClipSGD + PolyLR), i.e. the reference's class with its step tail on
     the MI355X; "adam" / "vanilla_adam" as in ``make_trainer_class``.  The 3-D step stays eager.  Kept in ``mlagg_optimizer``.
     loss_scaling: as in ``make_trainer_class``; the 3-D network computes in fp32 and scales no loss, so the choice is checked, kept in
-    ``mlagg_loss_scaling`` and has no further effect."""
+    ``mlagg_loss_scaling`` and has no further effect.
+    data_pipeline: as in ``make_trainer_class`` (3-D: GpuAugmenter3D with the dummy-2-D and cascade chains where the plan asks for them)."""
     from . import model3d
     _check_loss(loss)
     _check_optimizer(optimizer)
     _check_loss_scaling(loss_scaling)
+    _check_data_pipeline(data_pipeline)
     loss_variant = loss
 
     class nnUNetTrainerUMambaEnc_SS3D(nnUNetTrainer):
@@ -303,6 +417,7 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimiz
             self.mlagg_loss_variant = loss_variant                                   # for logs and checkpoints
             self.mlagg_optimizer = optimizer
             self.mlagg_loss_scaling = loss_scaling
+            self.mlagg_data_pipeline = data_pipeline
             miopen_tuning.use_tuned_convolutions(enabled=False)                      # no committed records for 3-D convolutions
 
         @staticmethod
@@ -346,6 +461,9 @@ def make_umamba_enc_ss3d_trainer_class(nnUNetTrainer, loss=DEFAULT_LOSS, optimiz
                 return trainer.deep_supervision_loss(list(output), list(target[:len(output)]), batch_dice, ddp, ignore_label=ignore)
 
             return loss
+
+        if data_pipeline == "device":
+            get_dataloaders = _device_dataloaders                                    # reference B:566-610
 
         if optimizer is not None:
             def configure_optimizers(self):                                          # reference B:448-452 / nnUNetTrainerAdam.py

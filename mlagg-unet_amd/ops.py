@@ -3713,3 +3713,86 @@ def cascade_cc_remove(planes, Z, state, rank, fill=None):
     target = torch.empty(P, dtype=torch.int32, device=planes.device)
     _launch("mlagg_cascade_cc_remove", _ptr(planes), P, X, Y, Z, thresh, _ptr(parent), _ptr(size), _ptr(blockcnt), _ptr(args[0]),
             _ptr(args[1]), _ptr(target))
+
+
+# ------------------------------------------------------------------------------------------------
+# K36: the tail of the training transform chain (mask, -1 -> 0, region planes, deep-supervision levels) in one launch
+# ------------------------------------------------------------------------------------------------
+TAIL_MAX_LEVELS = _C["MLAGG_TAIL_MAX_LEVELS"]
+TAIL_MAX_REGIONS = _C["MLAGG_TAIL_MAX_REGIONS"]
+_TAIL_SEG_KIND = {torch.float32: _C["MLAGG_TAIL_SEG_F32"], torch.int16: _C["MLAGG_TAIL_SEG_INT16"]}
+_TAIL_TABLES = {}
+
+
+def _tail_table(n, m, device):
+    """dataloading.nearest_index(n, m) on `device` (uploaded once per (n, m, device)); None for n == m, where it is the identity."""
+    if n == m:
+        return None
+    key = (n, m, str(device))
+    if key not in _TAIL_TABLES:
+        from .dataloading import nearest_index
+        _TAIL_TABLES[key] = nearest_index(n, m).to(device)
+    return _TAIL_TABLES[key]
+
+
+def batch_tail(data, seg, level_sizes, mask_channels=(), regions=None, ignore_label=None, tables=None):
+    """K36: from the augmented batch to what the loss consumes, the reference's MaskTransform, RemoveLabelTransform(-1, 0),
+    ConvertSegmentationToRegionsTransform and DownsampleSegForDSTransform2 (nnUNetTrainer.py:697-731) in one launch.
+    data (B, C, *S) fp32, contiguous, MODIFIED IN PLACE: zero in the channels `mask_channels` wherever seg[:, 0] < 0.
+    seg (B, Sc, *S) fp32 or int16, contiguous; channel 0 is read.  level_sizes: 1 to 8 spatial shapes (dataloading.level_sizes).
+    Returns (data, [target_l]): target_l (B, 1, *S_l) fp32 labels with negatives as 0, each voxel that of the source voxel
+    ``interpolate(mode="nearest-exact")`` picks (dataloading.nearest_index) -- `dataloading.targets_from_seg` to the bit -- or, with
+    `regions` (a label manager's ``foreground_regions``), (B, R (+ 1), *S_l) 0 / 1 planes, the last one `ignore_label`'s when given:
+    the layout K29 takes with member=None.  `tables` (tests, other index rules): per level and axis an int32 tensor of source
+    indices on the tensors' device, or None for the identity, instead of the nearest-exact ones.
+    CPU tensors take the same steps as a torch composition (dataloading.batch_tail_host); device tensors have no other path than K36."""
+    from . import dataloading
+    if not (isinstance(data, torch.Tensor) and isinstance(seg, torch.Tensor) and data.dtype == torch.float32
+            and seg.dtype in _TAIL_SEG_KIND and data.device == seg.device and data.dim() in (4, 5) and seg.dim() == data.dim()):
+        raise RuntimeError(f"batch_tail: data (B, C, *S) float32 and seg (B, Sc, *S) float32 or int16 on one device, 2-D or 3-D, got "
+                           f"{getattr(data, 'dtype', type(data))} {tuple(getattr(data, 'shape', ()))} on {getattr(data, 'device', '?')}"
+                           f" and {getattr(seg, 'dtype', type(seg))} {tuple(getattr(seg, 'shape', ()))} on {getattr(seg, 'device', '?')}")
+    if not (data.is_contiguous() and seg.is_contiguous()):
+        raise RuntimeError("batch_tail: data and seg must be contiguous (data is written in place)")
+    nd, S = data.dim() - 2, tuple(int(v) for v in data.shape[2:])
+    B, C, Sc = int(data.shape[0]), int(data.shape[1]), int(seg.shape[1])
+    if tuple(seg.shape[2:]) != S or seg.shape[0] != B or min((B, C, Sc) + S) < 1:
+        raise RuntimeError(f"batch_tail: data {tuple(data.shape)} and seg {tuple(seg.shape)} do not describe one non-empty batch")
+    sizes = [tuple(int(v) for v in s) for s in level_sizes]
+    if not 1 <= len(sizes) <= TAIL_MAX_LEVELS or any(len(s) != nd or min(s) < 1 for s in sizes):
+        raise RuntimeError(f"batch_tail: level sizes {sizes}: 1 to {TAIL_MAX_LEVELS} non-empty {nd}-D shapes")
+    mask = sorted({int(c) for c in mask_channels})
+    if mask and not (0 <= mask[0] and mask[-1] < min(C, 64)):
+        raise RuntimeError(f"batch_tail: mask_channels {mask} of {C} data channels (indices 0 to {min(C, 64) - 1})")
+    if ignore_label is not None and int(ignore_label) < 0:
+        raise RuntimeError(f"batch_tail: ignore_label {ignore_label}: None or a label value >= 0")
+    member = n_regions = None
+    if regions is not None:
+        member, n_regions = region_member_table(regions, data.device), len(regions)      # refuses 0 or more than 32 regions
+    if tables is None:
+        tables = [[_tail_table(n, m, data.device) for n, m in zip(S, s)] for s in sizes]
+    else:
+        tables = [list(t) for t in tables]
+        if len(tables) != len(sizes) or any(len(t) != nd for t in tables):
+            raise RuntimeError(f"batch_tail: tables for {len(tables)} levels, {len(sizes)} levels of {nd} axes expected")
+    for lvl, (tabs, s) in enumerate(zip(tables, sizes)):
+        for axis, (tab, m) in enumerate(zip(tabs, s)):
+            if tab is None:
+                if m != S[axis]:
+                    raise RuntimeError(f"batch_tail: level {lvl} axis {axis}: no table (the identity) for {S[axis]} -> {m} voxels")
+            elif not (isinstance(tab, torch.Tensor) and tab.dtype == torch.int32 and tab.dim() == 1 and tab.is_contiguous()
+                      and tab.device == data.device and tab.numel() == m):
+                raise RuntimeError(f"batch_tail: level {lvl} axis {axis}: the table is {m} contiguous int32 source indices on "
+                                   f"{data.device}, got {getattr(tab, 'dtype', type(tab))} {tuple(getattr(tab, 'shape', ()))}")
+    if mask and any(t is not None for t in tables[0]):
+        raise RuntimeError(f"batch_tail: a mask needs the first level to be the map itself, got {sizes[0]} for {S}")
+    if not data.is_cuda:
+        return dataloading.batch_tail_host(data, seg, sizes, mask, member, n_regions, ignore_label, tables)
+    planes = 1 if member is None else n_regions + (ignore_label is not None)
+    out = [torch.empty((B, planes) + s, dtype=torch.float32, device=data.device) for s in sizes]
+    pointers = lambda ts: (ctypes.c_void_p * len(ts))(*[_ptr(t) for t in ts])      # noqa: E731
+    with torch.cuda.device(data.device):
+        _launch("mlagg_batch_tail", _ptr(data), B, C, _ptr(seg), _TAIL_SEG_KIND[seg.dtype], Sc, nd, _int_array(S), _int_array(mask),
+                len(mask), len(sizes), _int_array([v for s in sizes for v in s]), pointers([t for tabs in tables for t in tabs]),
+                pointers(out), _ptr(member), n_regions or 0, -1 if ignore_label is None else int(ignore_label))
+    return data, out
